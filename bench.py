@@ -32,7 +32,21 @@ Environment: every BENOR_* variable set is recorded in the line ("env"); a
          the planner picks by itself.
 cpu_baseline: the oracle's bit-plane restatement (oracle/benor_oracle.c,
          OpenMP over trials) on a bounded sample, rank 0 at N = 1 only, on
-         every host thread and on one core.
+         every host thread and on one core (--full only).
+
+A plain run does what the headline needs and no more: plan, clock ramp,
+warm-up, the timed steps, the result line.  --full adds the side
+measurements to the same line: the matrix-core / popcount peak probe
+(roofline.peak_probe), other_configs (the other BASELINE configs, each with
+its roofline, the network API latencies, random delivery, the C5 sweep) and
+cpu_baseline.
+--dump-outputs DIR writes what the last timed step returned, as float64 .npy
+         files (rank 0): step_hist.npy, that step's merged outcome histogram
+         (bin layout of include/benor.h, then the count of ranks merged), and
+         hist.npy, the sum of the merged histograms of all timed steps.  The
+         inputs are a function of the arguments alone (Philox keyed by --seed
+         and the global trial id), so two builds run with the same arguments
+         can be compared bin for bin.
 
 Launch: python bench.py [--gpus N --steps K --warmup W].  For N > 1 the
 driver starts it under torch.distributed.run (one process per GPU, backend
@@ -97,13 +111,21 @@ def parse(argv=None):
     ap.add_argument("--trials", type=int, default=100_000_000)
     ap.add_argument("--k-max", type=int, default=16)
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x243F6A8885A308D3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: peak probe, other_configs, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's merged histogram and the timed steps' sum as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
-                    help="CPU-baseline sample budget on all host threads (0 = skip); the 1-core leg gets 2/3 of it")
-    ap.add_argument("--no-peak-probe", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the configs[1]/[2] side measurements")
+                    help="--full: CPU-baseline sample budget on all host threads (0 = skip); the 1-core leg gets 2/3 of it")
+    ap.add_argument("--no-peak-probe", action="store_true", help="skip the clock ramp (and --full's peak probe)")
+    ap.add_argument("--no-other-configs", action="store_true",
+                    help="--full: skip the configs[1]/[2] side measurements")
     ap.add_argument("--dry-run", action="store_true",
                     help="print this rank's place in the launch (world, rank, trial shards) and exit before any GPU work")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def node_rounds(hist, m, k_max):
@@ -485,26 +507,31 @@ def main():
         merge_histogram(step_hist)              # RCCL merge of the outcome histograms
         hist.add_(step_hist)
 
-    # Clock ramp before the warm-up steps: ~0.3 s of the matrix-core (or
-    # popcount) peak probe, whose figure is reported as roofline.peak_probe,
-    # then ~0.6 s of a neighbouring shape's kernel (F - 1: the same kernel
-    # family and instruction mix under another template instance, so a kernel
-    # trace keeps it apart from the bench kernel).  Without the ramp the first
+    # Clock ramp before the warm-up steps, ~0.9 s: with --full ~0.3 s of the
+    # matrix-core (or popcount) peak probe, whose figure is reported as
+    # roofline.peak_probe, then a neighbouring shape's kernel for the rest
+    # (F - 1: the same kernel family and instruction mix under another template
+    # instance, so a kernel trace keeps it apart from the bench kernel); a
+    # plain run ramps on that kernel alone.  Without the ramp the first
     # two bench launches run 6-15 % slower while clocks and power settle, and a
     # kernel trace of this command averages them in (profiles/r03-v0_summary.md,
     # profiles/r03-v1_summary.md).
     mfma = plan.kernel == benor.BO_KERNEL_MFMA
     peak_measured = None
     if not args.no_peak_probe:
-        t_ramp = time.perf_counter()
-        while time.perf_counter() - t_ramp < 0.3:
-            peak_measured = 2 * benor.mfma_peak(10) if mfma else benor.popc_peak(10)
+        ramp_s = 0.9
+        if args.full or F == 0:
+            t_ramp = time.perf_counter()
+            while time.perf_counter() - t_ramp < 0.3:
+                peak = 2 * benor.mfma_peak(10) if mfma else benor.popc_peak(10)
+                peak_measured = peak if args.full else None
+            ramp_s = 0.6
         if F > 0:
             ramp = benor.TrialsPlan(N, F - 1, [i < F - 1 for i in range(N)], seed=args.seed ^ 0x5A5A, k_max=k_max)
             ramp_hist = torch.zeros(ramp.hist_len, dtype=torch.int64, device="cuda")
             t_ramp = time.perf_counter()
             r = 0
-            while time.perf_counter() - t_ramp < 0.6:     # back to back, two launches in flight
+            while time.perf_counter() - t_ramp < ramp_s:  # back to back, two launches in flight
                 ramp.launch(r * T, T, ramp_hist.data_ptr(), stream.cuda_stream)
                 if r:
                     ev_ramp.synchronize()
@@ -562,7 +589,7 @@ def main():
     out = {
         "metric": METRIC, "value": value, "unit": "node-rounds/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": elapsed * 1e3 / args.steps, "higher_is_better": True,
-        "scaling": args.scaling, "vs_baseline": None,
+        "scaling": args.scaling, "full": args.full, "vs_baseline": None,
         "dtype": "e2m1 0/1 votes -> f32 exact integer counts" if mfma else "u32",
         "data": "synthetic (Philox initial values)",
         "config": {"workload": f"N={N},F={F} lockstep crash faults, {T} trials {per_gpu} per step, k_max={k_max}",
@@ -596,13 +623,18 @@ def main():
         "agreement_violations": int(h[-1]),
         "env": env,
     }
-    if world == 1 and not args.no_other_configs:
+    if rank == 0 and args.dump_outputs:
+        # exact in float64: a bin counts at most steps * world * trials < 2^53
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "step_hist.npy"), step_hist.cpu().numpy().astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "hist.npy"), hh.astype(np.float64))
+    if args.full and world == 1 and not args.no_other_configs:
         out["other_configs"] = other_configs(benor, torch, k_max, args.seed)
         out["other_configs"]["C1 N=5,F=1 network API"] = network_latency(benor)
         out["other_configs"]["C4 N=1024,F=341,f=0 random delivery"] = random_delivery_config(benor, torch, k_max, args.seed)
         out["other_configs"]["C4 N=1024,F=341 network API, mid-run /stop"] = event_network(benor)
         out["other_configs"]["C5 sweep (2^30 trials, 224 cells)"] = c5_sweep()
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         out["cpu_baseline"] = cpu_baseline(N, F, k_max, args.seed, args.cpu_seconds)
     if rank == 0:
         print(json.dumps(out), flush=True)

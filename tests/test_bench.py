@@ -1,5 +1,5 @@
-"""bench.py contract: one JSON line with the BASELINE metric, roofline and
-(at N=1) cpu_baseline; the multi-rank path (trial sharding + histogram
+"""bench.py contract: one JSON line with the BASELINE metric and roofline, with
+--full also (at N=1) other_configs and cpu_baseline; the multi-rank path (trial sharding + histogram
 all-reduce + max-over-ranks timing) rehearsed with two ranks on one GPU over
 gloo (the driver's 8-GPU runs use the same code with backend nccl = RCCL)."""
 import json
@@ -89,7 +89,8 @@ def _run_bench(args, env_extra=None, launcher=None, timeout=300):
 
 @pytest.mark.gpu
 def test_bench_single_gpu_line():
-    d = _run_bench(["--steps", "2", "--warmup", "1", "--trials", "4000000", "--cpu-seconds", "1", "--no-peak-probe"])
+    d = _run_bench(["--full", "--steps", "2", "--warmup", "1", "--trials", "4000000", "--cpu-seconds", "1",
+                    "--no-peak-probe"])
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["unit"] == "node-rounds/s" and d["scaling"] == "strong"
     assert 0 < d["roofline"]["frac"] < 1.0
     assert d["dist"]["world"] == 1 and d["dist"]["backend"] is None and d["agreement_violations"] == 0
@@ -125,6 +126,43 @@ def test_bench_single_gpu_line():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_dumps_last_step(tmp_path):
+    """A plain run reports the headline alone (no side measurements) and
+    --dump-outputs writes the last timed step's merged histogram and the timed
+    steps' sum as float64: the last step equals a launch of its trial ids
+    made here, so the dump is a function of the arguments."""
+    import numpy as np
+    import torch
+
+    import benor
+
+    T, steps, warmup = 1_000_003, 3, 1
+    d = _run_bench(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--trials", str(T),
+                    "--no-peak-probe", "--dump-outputs", str(tmp_path / "out")])
+    assert d["steps"] == steps and d["full"] is False and d["ms_per_step"] > 0
+    assert "other_configs" not in d and "cpu_baseline" not in d and d["roofline"]["peak_probe"] is None
+    assert d["trials_per_s"] * d["ms_per_step"] * 1e-3 == pytest.approx(T, rel=1e-6)
+    assert sorted(os.listdir(tmp_path / "out")) == ["hist.npy", "step_hist.npy"]
+    last, total = np.load(tmp_path / "out" / "step_hist.npy"), np.load(tmp_path / "out" / "hist.npy")
+    assert last.dtype == total.dtype == np.float64 and last.shape == total.shape
+    N, F = d["config"]["N"], d["config"]["F"]
+    plan = benor.TrialsPlan(N, F, [i < F for i in range(N)], seed=0x243F6A8885A308D3, k_max=d["config"]["k_max"])
+    h = torch.zeros(plan.hist_len, dtype=torch.int64, device="cuda")
+    plan.launch((warmup + steps - 1) * T, T, h.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert np.array_equal(last[:-1], h.cpu().numpy().astype(np.float64)) and last[-1] == 1
+    assert last[:-2].sum() == T and total[:-2].sum() == steps * T and total[-1] == steps
+    assert bench_digest(total[:-1]) == d["dist"]["hist_sha256"]
+
+
+def bench_digest(hist):
+    sys.path.insert(0, ROOT)
+    import bench
+
+    return bench.hist_digest(hist.astype("uint64"))
+
+
+@pytest.mark.gpu
 def test_bench_nccl_world_one_under_launcher():
     """The RCCL branch: torch.distributed.run with one rank, backend nccl."""
     d = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--trials", "1000000", "--no-peak-probe",
@@ -155,7 +193,7 @@ def test_bench_self_launched_ranks_match_one_rank(scaling):
 
 @pytest.mark.gpu
 def test_bench_four_ranks_gloo_one_gpu():
-    d = _run_bench(["--gpus", "4", "--steps", "2", "--warmup", "1", "--trials", "1000000", "--no-peak-probe"],
+    d = _run_bench(["--gpus", "4", "--full", "--steps", "2", "--warmup", "1", "--trials", "1000000", "--no-peak-probe"],
                    env_extra={"BENOR_DIST_BACKEND": "gloo"},
                    launcher=["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
                              "--master-addr", "127.0.0.1", "--master-port", str(_free_port())])

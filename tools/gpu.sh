@@ -13,7 +13,8 @@
 #   tests           pytest -m gpu (PYTEST_ARGS: test paths / options, default the whole GPU suite;
 #                   PYTEST_K: a -k expression, spaces allowed)
 #   probe           tools/mfma_fp4_layout_probe (e2m1 MFMA K pairing)
-#   bench           python bench.py (BENCH_ARGS, default the driver's --steps 20 --warmup 5)
+#   bench           python bench.py (BENCH_ARGS, default the driver's --steps 20 --warmup 5 with --full:
+#                   the side measurements the summaries reconcile)
 #   trace           rocprofv3 --kernel-trace --stats of the same bench command
 #   pmc:<shape>     PMC passes (PMC_GROUPS, '|'-separated, one rocprofv3 run each) over one
 #                   tools/perf_matrix.py shape; <shape> is a key of SHAPES below or N,F,f,mode,trials
@@ -53,7 +54,7 @@ declare -A SHAPES=(
   [ev256]="256,85,85,2,20000"          # event level
 )
 PMC_GROUPS=${PMC_GROUPS:-"SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE GRBM_COUNT|SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INST_CYCLES_VMEM SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA|SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_VALU_MFMA_COEXEC_CYCLES SQ_INSTS_VALU SQ_WAVES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE|FETCH_SIZE|WRITE_SIZE"}
-BENCH_ARGS=${BENCH_ARGS:---steps 20 --warmup 5}
+BENCH_ARGS=${BENCH_ARGS:---full --steps 20 --warmup 5}
 
 chk() {  # rc name
   echo "== $2 rc=$1"

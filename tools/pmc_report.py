@@ -160,7 +160,7 @@ def main(tag):
 
 
 def bench_args():
-    return os.environ.get("BENCH_ARGS", "--steps 20 --warmup 5")
+    return os.environ.get("BENCH_ARGS", "--full --steps 20 --warmup 5")
 
 
 def bench_kernel(durs, bench=None, steps=None):
