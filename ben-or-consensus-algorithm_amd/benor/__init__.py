@@ -37,6 +37,7 @@ BO_ERR_ALREADY_STARTED = 8
 BO_MODE_LOCKSTEP = 0
 BO_MODE_RANDOM_DELIVERY = 1
 BO_MODE_EVENT = 2
+BO_MODE_RANDOM_TALLY = 3       # random delivery at the level of counts (odd quorum, no "?" initial value)
 NEVER = 0xFFFFFFFF             # crash_at entry: never stopped
 BO_INIT_RANDOM = 0
 BO_INIT_FIXED = 1
@@ -48,9 +49,11 @@ BO_KERNEL_EVENT = 4
 BO_KERNEL_LANE = 6
 BO_KERNEL_MFMA = 7
 BO_KERNEL_MFMA_SMALL = 8
+BO_KERNEL_TALLY = 9
 KERNEL_NAMES = {BO_KERNEL_NONE: "none", BO_KERNEL_BLOCKED: "blocked popcount", BO_KERNEL_W: "W popcount",
                 BO_KERNEL_RANDOM: "random delivery", BO_KERNEL_EVENT: "event level", BO_KERNEL_LANE: "lane",
-                BO_KERNEL_MFMA: "matrix core (e2m1 MFMA)", BO_KERNEL_MFMA_SMALL: "packed matrix core (e2m1 MFMA, m <= 32)"}
+                BO_KERNEL_MFMA: "matrix core (e2m1 MFMA)", BO_KERNEL_MFMA_SMALL: "packed matrix core (e2m1 MFMA, m <= 32)",
+                BO_KERNEL_TALLY: "count-level random delivery (hypergeometric tallies)"}
 BO_MAX_N = 4096
 BO_MAX_K = 1024
 
@@ -76,6 +79,7 @@ EXPORTED_SYMBOLS = (
     "bo_popc_peak", "bo_last_error", "bo_abi_version", "bo_kernel_version", "bo_plan_kernel", "bo_kernel_for",
     "bo_mfma_peak", "bo_consensus_start_sched", "bo_plan_check",
     "bo_consensus_start_live", "bo_consensus_wait", "bo_live_stop_events", "bo_get_states", "bo_consensus_poll",
+    "bo_tally_cdf",
 )
 
 
@@ -159,6 +163,8 @@ def lib() -> ctypes.CDLL:
     L.bo_plan_kernel.argtypes = [ctypes.c_void_p]
     L.bo_plan_kernel.restype = ctypes.c_int
     L.bo_kernel_for.argtypes = [P(TrialsCfgC), P(ctypes.c_int)]
+    L.bo_tally_cdf.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P(ctypes.c_uint32),
+                               P(ctypes.c_uint64), ctypes.c_uint32, P(ctypes.c_uint32)]
     L.bo_last_error.restype = ctypes.c_char_p
     L.bo_abi_version.restype = ctypes.c_int
     L.bo_kernel_version.restype = ctypes.c_char_p
@@ -535,6 +541,17 @@ def run_trial_states(N: int, F: int, faulty: Sequence[bool], *, seed: int = 0, t
     rounds = ctypes.c_uint32(0)
     _check(lib().bo_run_trial_states(ctypes.byref(cfg), trial, st, ctypes.byref(rounds)))
     return int(rounds.value), [_state_dict(st[i]) for i in range(N)]
+
+
+def tally_cdf(m: int, q: int, K: int) -> tuple[int, list[int]]:
+    """Row K of the BO_MODE_RANDOM_TALLY table for (m, q) (bo_tally_cdf; host only):
+    (lo, thresholds).  With K of m senders holding a 1, a 64-bit draw u gives the
+    receiver's count of 1s among its q arrivals as lo + #{j : thresholds[j] <= u}."""
+    cap = max(1, min(K, q))
+    thr = (ctypes.c_uint64 * cap)()
+    lo, n = ctypes.c_uint32(), ctypes.c_uint32()
+    _check(lib().bo_tally_cdf(m, q, K, ctypes.byref(lo), thr, cap, ctypes.byref(n)))
+    return int(lo.value), [int(v) for v in thr[:n.value]]
 
 
 def kernel_version() -> str:

@@ -2,6 +2,7 @@
 
     python -m benor.cli start [--N 10 --faulty 0,1,2,3 --init 1,1,...]   # src/start.ts
     python -m benor.cli trials --N 1024 --F 341 --trials 1000000          # one batch, JSON summary
+    python -m benor.cli trials --N 1024 --F 341 --mode tally --crashed 0  # f = 0 crashed, count-level random delivery
     python -m benor.cli sweep --N 64,128,...,4096 --steps 32 --trials 2**30 --out sweep.csv
                                                                           # C5 phase diagram
     python -m benor.cli sweep --cells 4096:0,4096:1984 --per-cell 4793490  # two cells of it
@@ -75,11 +76,16 @@ def cmd_start(a) -> int:
 def cmd_trials(a) -> int:
     import benor
 
-    plan = benor.TrialsPlan(a.N, a.F, seed=a.seed, k_max=a.k_max)
+    mode = {"lockstep": benor.BO_MODE_LOCKSTEP, "random": benor.BO_MODE_RANDOM_DELIVERY,
+            "tally": benor.BO_MODE_RANDOM_TALLY}[a.mode]
+    crashed = a.F if a.crashed is None else a.crashed            # the first f nodes (start.ts:7-18 placement)
+    plan = benor.TrialsPlan(a.N, a.F, [i < crashed for i in range(a.N)], seed=a.seed, k_max=a.k_max, mode=mode)
     t0 = time.perf_counter()
     h = plan.run(a.begin, a.trials)
     dt = time.perf_counter() - t0
     row = summarize(h, a.N, a.F, a.k_max)
+    if a.mode != "lockstep" or a.crashed is not None:
+        row.update(m=a.N - crashed, mode=a.mode, crashed=crashed, hist=[int(v) for v in h])
     row["seconds"] = dt
     print(json.dumps(row))
     return 0
@@ -191,6 +197,10 @@ def main(argv=None) -> int:
     t.add_argument("--begin", type=int, default=0)
     t.add_argument("--seed", type=int, default=0x243F6A8885A308D3)
     t.add_argument("--k-max", type=int, default=16)
+    t.add_argument("--mode", choices=["lockstep", "random", "tally"], default="lockstep",
+                   help="delivery model: lockstep, random (mask-level) or tally (count-level random delivery)")
+    t.add_argument("--crashed", type=int, default=None,
+                   help="crash the first f nodes (default F; random and tally take f <= F)")
     w = sub.add_parser("sweep", help="C5 decision-round phase diagram")
     w.add_argument("--N", default="64,128,256,512,1024,2048,4096")
     w.add_argument("--steps", type=int, default=32)

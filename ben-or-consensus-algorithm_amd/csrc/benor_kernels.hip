@@ -643,6 +643,16 @@ void plan_geometry(KParams &p) {
     p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
     return;
   }
+  if (p.mode == BO_MODE_RANDOM_TALLY) {             // count-level random delivery (benor_tally.hip)
+    p.G = 1;
+    p.nblocks = W;
+    p.variant = 9;
+    const uint32_t e = p.m - p.q;
+    p.tally_cap = p.q <= e ? p.q : e;               // the widest row of HG(m, ., q)
+    p.wave_bytes = (tally_wave_bytes(W, p.tally_cap) + 15u) & ~15u;   // x ballots + one staged row
+    p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
+    return;
+  }
   if (p.m <= kMaxLaneM) {                           // lane kernel: one trial per lane
     const uint32_t M1 = p.m - p.init_q;
     const bool odd = (p.m & 1u) && (M1 & 1u);        // every vote count odd: no tie, no coin
@@ -774,6 +784,7 @@ hipError_t launch_lockstep(const KParams &p, int grid, hipStream_t s) {
     q.lds_bytes = q.hist_bytes + kWavesPerBlock * q.wave_bytes;
     return launch_lockstep(q, grid, s);
   }
+  if (p.variant == 9) return launch_tally(p, grid, s);
   if (p.variant == 2 && p.rd_a) return launch_random_bern(p, grid, s);
   if (p.variant == 2) {                      // Floyd sampler
     if (p.lds_bytes > 64u * 1024u) {
@@ -879,6 +890,10 @@ int lockstep_grid(const KParams &p, int device) {
   if (lds > 0) {
     const uint64_t lds_fit = lds_groups_per_cu(lds);
     if (lds_fit < per_cu) per_cu = lds_fit ? lds_fit : 1;
+  }
+  if (p.variant == 9) {                      // count-level random delivery: its unrolled forms are register-bound
+    const uint64_t fit = (uint64_t)tally_blocks_per_cu(p);
+    if (fit >= 1u && fit < per_cu) per_cu = fit;
   }
   // Lane kernel: a short launch spread over every wave slot (~2 trials per
   // lane at 10^6 trials) spends most of its time in per-wave overhead (ring

@@ -19,6 +19,7 @@
 #include <mutex>
 #include <thread>
 #include <chrono>
+#include <cmath>
 #include <vector>
 
 #include "benor.h"
@@ -141,6 +142,7 @@ struct bo_plan {
   uint64_t defer_words = 0;
   uint32_t *d_flag = nullptr;      // KParams::overflow (bo_plan_check)
   uint64_t *d_stops = nullptr;     // event level, N > 256: sorted /stop schedule
+  unsigned char *d_tally = nullptr;   // RANDOM_TALLY: u32 row offsets [m + 2] (padded to 8 bytes), u64 thresholds
   int device = 0;
 };
 
@@ -448,6 +450,54 @@ int bo_consensus_start_sched(bo_network *net, uint64_t seed, uint32_t k_max, con
   return BO_OK;
 }
 
+// ------------------------------------------------ RANDOM_TALLY table (host)
+// Row K of the threshold table of Hypergeometric(m, K, q), the count of 1s in
+// a uniform q-subset of m senders of which K hold a 1: support [lo, hi],
+// lo = max(0, q - (m - K)), hi = min(K, q), and hi - lo thresholds
+// T[j] = min(2^64 - 1, floor(CDF(lo + j) * 2^64)) appended to `thr`.  In double:
+// weights by the ratio recurrence pmf(c + 1) / pmf(c) =
+// (K - c)(q - c) / ((c + 1)(m - K - q + c + 1)) outward from the mode (weight 1,
+// so nothing overflows and the far tails underflow harmlessly), then running
+// sums over their total.  The sums never decrease, so neither do the
+// thresholds.
+static uint32_t tally_row(uint32_t m, uint32_t q, uint32_t K, std::vector<uint64_t> &thr, std::vector<double> &w) {
+  const uint32_t lo = K + q > m ? K + q - m : 0u, hi = K < q ? K : q, n = hi - lo;
+  if (n == 0u) return lo;
+  uint32_t mode = (uint32_t)(((uint64_t)q + 1u) * ((uint64_t)K + 1u) / ((uint64_t)m + 2u));
+  mode = mode < lo ? lo : (mode > hi ? hi : mode);
+  w.assign(n + 1u, 0.0);
+  auto ratio = [&](uint32_t c) {                 // pmf(c + 1) / pmf(c), lo <= c < hi
+    return ((double)(K - c) * (double)(q - c)) / ((double)(c + 1u) * (double)(m - K - q + c + 1u));
+  };
+  w[mode - lo] = 1.0;
+  for (uint32_t c = mode; c < hi; ++c) w[c + 1u - lo] = w[c - lo] * ratio(c);
+  for (uint32_t c = mode; c > lo; --c) w[c - 1u - lo] = w[c - lo] / ratio(c - 1u);
+  double total = 0.0;
+  for (uint32_t i = 0; i <= n; ++i) total += w[i];
+  double run = 0.0;
+  for (uint32_t j = 0; j < n; ++j) {
+    run += w[j];
+    const double t = std::ldexp(run / total, 64);
+    thr.push_back(t >= 18446744073709551616.0 ? ~0ull : (uint64_t)t);
+  }
+  return lo;
+}
+
+int bo_tally_cdf(uint32_t m, uint32_t q, uint32_t K, uint32_t *lo_out, uint64_t *thr_out, uint32_t cap,
+                 uint32_t *n_out) {
+  if (!lo_out || !n_out) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (K > m || q > m) return fail(BO_ERR_INVALID_ARGUMENT, "bo_tally_cdf needs K <= m and q <= m");
+  const uint32_t n = (K < q ? K : q) - (K + q > m ? K + q - m : 0u);   // hi - lo: checked before the row is built
+  if (n > cap || (n && !thr_out)) return fail(BO_ERR_INVALID_ARGUMENT, "bo_tally_cdf: thr_out is too short for the row");
+  std::vector<uint64_t> thr;
+  std::vector<double> w;
+  const uint32_t lo = tally_row(m, q, K, thr, w);
+  *lo_out = lo;
+  *n_out = (uint32_t)thr.size();
+  if (!thr.empty()) std::memcpy(thr_out, thr.data(), sizeof(uint64_t) * thr.size());
+  return BO_OK;
+}
+
 // -------------------------------------------------------------- batch API
 // Validation and kernel planning of a trial configuration, host only: the
 // live-node map, the fixed-init plane and the KParams shape (no device fields).
@@ -456,8 +506,10 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   if (!cfg) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
   if (cfg->N < 1 || cfg->N > BO_MAX_N) return fail(BO_ERR_UNSUPPORTED, "N must be in [1, 4096]");
   if (cfg->k_max < 1 || cfg->k_max > BO_MAX_K) return fail(BO_ERR_INVALID_ARGUMENT, "k_max must be in [1, 1024]");
-  if (cfg->mode != BO_MODE_LOCKSTEP && cfg->mode != BO_MODE_RANDOM_DELIVERY && cfg->mode != BO_MODE_EVENT)
+  if (cfg->mode != BO_MODE_LOCKSTEP && cfg->mode != BO_MODE_RANDOM_DELIVERY && cfg->mode != BO_MODE_EVENT &&
+      cfg->mode != BO_MODE_RANDOM_TALLY)
     return fail(BO_ERR_UNSUPPORTED, "unknown delivery mode");
+  const bool random_mode = cfg->mode == BO_MODE_RANDOM_DELIVERY || cfg->mode == BO_MODE_RANDOM_TALLY;
   if (cfg->init_mode != BO_INIT_RANDOM && cfg->init_mode != BO_INIT_FIXED)
     return fail(BO_ERR_INVALID_ARGUMENT, "unknown init_mode");
   if (!cfg->faulty) return fail(BO_ERR_INVALID_ARGUMENT, "faulty is NULL");
@@ -466,9 +518,9 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   for (uint32_t i = 0; i < cfg->N; ++i) f += cfg->faulty[i] ? 1u : 0u;
   // Lockstep = the reference's admissible inputs: exactly F crash faults
   // (launchNodes.ts:12-13).  Random delivery admits f <= F.
-  if (cfg->mode != BO_MODE_RANDOM_DELIVERY && f != cfg->F)
+  if (!random_mode && f != cfg->F)
     return fail(BO_ERR_FAULTY_COUNT, "faultyList doesnt have F faulties");
-  if (cfg->mode == BO_MODE_RANDOM_DELIVERY && f > cfg->F)
+  if (random_mode && f > cfg->F)
     return fail(BO_ERR_FAULTY_COUNT, "random delivery needs at most F crash-faulty nodes");
   live.clear();
   for (uint32_t i = 0; i < cfg->N; ++i)
@@ -509,6 +561,12 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
     }
     kp.init_tie = n0 == n1 ? 1u : 0u;
   }
+  // Count-level random delivery draws two-category counts: every vote binary
+  // and no tally tie, i.e. an odd quorum and no "?" initial value.
+  if (cfg->mode == BO_MODE_RANDOM_TALLY && !(kp.q & 1u))
+    return fail(BO_ERR_UNSUPPORTED, "BO_MODE_RANDOM_TALLY needs an odd quorum N - F: use BO_MODE_RANDOM_DELIVERY");
+  if (cfg->mode == BO_MODE_RANDOM_TALLY && kp.init_q)
+    return fail(BO_ERR_UNSUPPORTED, "BO_MODE_RANDOM_TALLY takes no \"?\" initial value: use BO_MODE_RANDOM_DELIVERY");
   benor::plan_geometry(kp);   // after init_q: the kernel choice depends on the round-1 vote parity
   return BO_OK;
 }
@@ -627,6 +685,24 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
       kp.init_x = pl->d_init_x;
       kp.crash_at = pl->d_crash;
       kp.scratch = pl->d_scratch;
+    } else if (cfg->mode == BO_MODE_RANDOM_TALLY) {
+      // the whole table HG(m, K, q), K = 0..m: at most ~3.7 * 10^6 thresholds (30 MB) at m = 4096
+      std::vector<uint32_t> off(m + 2u, 0u);
+      std::vector<uint64_t> thr;
+      std::vector<double> w;
+      for (uint32_t K = 0; K <= m; ++K) {
+        off[K] = (uint32_t)thr.size();
+        (void)tally_row(m, kp.q, K, thr, w);
+      }
+      off[m + 1u] = (uint32_t)thr.size();
+      const size_t off_bytes = (sizeof(uint32_t) * off.size() + 7u) & ~size_t(7);
+      e = hipMalloc(&pl->d_tally, off_bytes + sizeof(uint64_t) * std::max<size_t>(thr.size(), 1u));
+      if (e == hipSuccess) e = hipMemcpy(pl->d_tally, off.data(), sizeof(uint32_t) * off.size(), hipMemcpyHostToDevice);
+      if (e == hipSuccess && !thr.empty())
+        e = hipMemcpy(pl->d_tally + off_bytes, thr.data(), sizeof(uint64_t) * thr.size(), hipMemcpyHostToDevice);
+      if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "tally table upload"); }
+      kp.tally_off = reinterpret_cast<const uint32_t *>(pl->d_tally);
+      kp.tally_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + off_bytes);
     }
   }
   *out = pl;
@@ -645,6 +721,7 @@ void bo_plan_destroy(bo_plan *pl) {
   if (pl->d_defer) (void)hipFree(pl->d_defer);
   if (pl->d_flag) (void)hipFree(pl->d_flag);
   if (pl->d_stops) (void)hipFree(pl->d_stops);
+  if (pl->d_tally) (void)hipFree(pl->d_tally);
   delete pl;
 }
 
@@ -660,11 +737,12 @@ int bo_plan_kernel(const bo_plan *pl) {
 // is odd: then no R-phase count can tie, no proposal is "?" (node.ts:63-69),
 // and c0 = m - c1.  So 2 counts of ceil(m/32) words for odd M (the bench's
 // m = 683), 3 for even M (round-1 parity: M = m - init_q).  Random delivery
-// counts both values in both phases: 4.
+// counts both values in both phases: 4 (the count-level mode answers the same
+// unit: the work it stands in for).
 uint64_t bo_plan_popc_words_per_node_round(const bo_plan *pl) {
   if (!pl) return 0;
   uint64_t counts = 4ull;
-  if (pl->kp.mode != BO_MODE_RANDOM_DELIVERY) counts = ((pl->kp.m - pl->kp.init_q) & 1u) ? 2ull : 3ull;
+  if (pl->kp.mode != BO_MODE_RANDOM_DELIVERY && pl->kp.mode != BO_MODE_RANDOM_TALLY) counts = ((pl->kp.m - pl->kp.init_q) & 1u) ? 2ull : 3ull;
   return counts * ((pl->kp.m + 31ull) / 32ull);
 }
 

@@ -83,14 +83,21 @@ export interface TrialsConfig {
   kMax?: number;
   trialBegin?: bigint | number;
   trialCount?: bigint | number;
-  /** 0 lockstep (default), 1 random delivery (f <= F), 2 event level (N <= 4096) */
-  mode?: 0 | 1 | 2;
+  /** 0 lockstep (default), 1 random delivery (f <= F), 2 event level (N <= 4096),
+   *  3 random delivery at the level of counts (MODE_RANDOM_TALLY: f <= F, N - F odd, no "?" initial value) */
+  mode?: 0 | 1 | 2 | 3;
   /** event mode: deliveries after which node i is stopped (null = never) */
   crashAt?: (number | null)[];
   /** event mode, random schedule: stop crashCount live nodes at uniform delivery counts in [0, crashWindow) */
   crashCount?: number;
   crashWindow?: number;
 }
+
+/** TrialsConfig.mode values (include/benor.h BO_MODE_*). */
+export declare const MODE_LOCKSTEP: 0;
+export declare const MODE_RANDOM_DELIVERY: 1;
+export declare const MODE_EVENT: 2;
+export declare const MODE_RANDOM_TALLY: 3;
 
 /** Outcome histogram, (kMax + 1) * 3 + 1 bins (include/benor.h). */
 export declare function runTrials(cfg: TrialsConfig): Promise<BigUint64Array>;

@@ -60,7 +60,20 @@ enum {
  * trial up to N = 256, one wave per trial above).  Both /stop schedules --
  * explicit (crash_at) and random (crash_count, crash_window) -- work at every
  * N <= 4096. */
-enum { BO_MODE_LOCKSTEP = 0, BO_MODE_RANDOM_DELIVERY = 1, BO_MODE_EVENT = 2 };
+/* RANDOM_TALLY is RANDOM_DELIVERY at the level of counts.  A receiver's rule
+ * (node.ts:52-69, :88-113) reads only how many 0s and 1s its inbox holds, and
+ * the inbox is a uniform (N-F)-subset of the m = N-f live senders, independent
+ * per (receiver, round, phase): with K senders holding a 1, its count of 1s is
+ * Hypergeometric(m, K, N-F).  The mode draws that count directly, from one
+ * Philox block per receiver-round (stream 5) and a host-built table of 64-bit
+ * CDF thresholds (bo_tally_cdf), so the law over histograms and per-node states
+ * is RANDOM_DELIVERY's (thresholds rounded at 2^-64) while the random stream,
+ * and so each seed's outcome, differs.  Scope: the quorum N-F must be odd and
+ * no initial value may be "?" (every vote is then binary, no tally ties, no
+ * coin is drawn); other configurations return BO_ERR_UNSUPPORTED -- run them in
+ * BO_MODE_RANDOM_DELIVERY.  Validation is RANDOM_DELIVERY's (at most F
+ * faulty).  At f == F it equals LOCKSTEP bit for bit. */
+enum { BO_MODE_LOCKSTEP = 0, BO_MODE_RANDOM_DELIVERY = 1, BO_MODE_EVENT = 2, BO_MODE_RANDOM_TALLY = 3 };
 
 enum { BO_INIT_RANDOM = 0, BO_INIT_FIXED = 1 };
 
@@ -191,10 +204,10 @@ typedef struct bo_trials_cfg {
     uint32_t N, F;            /* network size; fault parameter (quorum N-F, decide on > F) */
     uint32_t k_max;           /* round cap, 1..BO_MAX_K */
     uint32_t init_mode;       /* BO_INIT_RANDOM: iid Bernoulli(1/2) per live node; BO_INIT_FIXED */
-    uint32_t mode;            /* BO_MODE_LOCKSTEP or BO_MODE_RANDOM_DELIVERY */
+    uint32_t mode;            /* BO_MODE_* */
     uint32_t reserved;
     uint64_t seed;            /* Philox4x32-10 key */
-    const uint8_t *faulty;    /* host [N]; exactly F set (LOCKSTEP, EVENT), at most F (RANDOM_DELIVERY) */
+    const uint8_t *faulty;    /* host [N]; exactly F set (LOCKSTEP, EVENT), at most F (RANDOM_DELIVERY, RANDOM_TALLY) */
     const int8_t *init;       /* host [N]; used when init_mode == BO_INIT_FIXED */
     /* EVENT mode only: GET /stop schedule.  crash_at[i] = number of deliveries
      * after which node i is stopped (UINT32_MAX = never), or, when crash_at is
@@ -243,7 +256,8 @@ int bo_plan_check(bo_plan *plan);
  * initial values) binary votes.  LOCKSTEP / EVENT: the R-phase counts c1
  * (c0 = M - c1); the P-phase counts c1 when M is odd (no tie, so no "?"
  * proposal: c0 = m - c1) and c0, c1 otherwise -- 2 or 3 x ceil(m/32).
- * RANDOM_DELIVERY: both values in both phases, 4 x ceil(m/32). */
+ * RANDOM_DELIVERY: both values in both phases, 4 x ceil(m/32).  RANDOM_TALLY
+ * answers RANDOM_DELIVERY's unit, the work it stands in for. */
 uint64_t bo_plan_popc_words_per_node_round(const bo_plan *plan);
 uint32_t bo_plan_live_nodes(const bo_plan *plan);
 
@@ -259,10 +273,13 @@ enum {
   BO_KERNEL_EVENT = 4,  /* event level: one lane per trial (N <= 256), one wave per trial (N > 256, live runs) */
   BO_KERNEL_LANE = 6,
   BO_KERNEL_MFMA = 7,
-  BO_KERNEL_MFMA_SMALL = 8 /* packed matrix-core kernel: 2 <= m <= 32, m > F, no "?" initial value;
+  BO_KERNEL_MFMA_SMALL = 8, /* packed matrix-core kernel: 2 <= m <= 32, m > F, no "?" initial value;
                               64 * min(32/m, 8) trials per wave iteration, block-diagonal e2m1 products;
                               launches of fewer than 5 * 10^5 trials run the lane kernel
                               (BENOR_SMALL_MIN_TRIALS overrides) */
+  BO_KERNEL_TALLY = 9       /* BO_MODE_RANDOM_TALLY: one wave per trial, per-receiver hypergeometric counts
+                              by binary search in a table row staged in LDS; batch and per-node-state
+                              launches alike, no overflow or deferral state */
 };
 
 /* The kernel family bo_plan_launch runs for this plan.  (The per-node-state
@@ -284,6 +301,15 @@ int bo_run_trials(const bo_trials_cfg *cfg, uint64_t trial_begin, uint64_t trial
 /* Per-node final states of one trial (trial id `trial`), nodes_out[N]. */
 int bo_run_trial_states(const bo_trials_cfg *cfg, uint64_t trial, bo_node_state *nodes_out,
                         uint32_t *rounds_out);
+
+/* Row K of the RANDOM_TALLY table for (m, q): *lo_out, and its hi-lo thresholds
+ * into thr_out[cap] (*n_out = their number; BO_ERR_INVALID_ARGUMENT if cap is short
+ * or K > m or q > m).  Exactly what bo_plan_create uploads.  Host only, no device
+ * needed.  lo = max(0, q - (m - K)), hi = min(K, q); threshold j is
+ * min(2^64 - 1, floor(CDF(lo + j) * 2^64)) of Hypergeometric(m, K, q), built in
+ * double; a draw u (uniform 64 bits) gives the count lo + #{ j : thr[j] <= u }. */
+int bo_tally_cdf(uint32_t m, uint32_t q, uint32_t K, uint32_t *lo_out,
+                 uint64_t *thr_out, uint32_t cap, uint32_t *n_out);
 
 /* ---- diagnostics ---- */
 

@@ -13,7 +13,14 @@ median and minimum ms per launch and the variant's median / first variant's.
         --shapes "4096,1365,400000;4096,0,100000" [--rounds 7] [--reps 3]
 
 A shape may carry a fourth field f < F (the first f nodes crashed, the rest of
-F the random-delivery slack: BO_MODE_RANDOM_DELIVERY).  Every line also reports
+F the random-delivery slack: BO_MODE_RANDOM_DELIVERY).  A variant may also name
+the delivery mode with the pseudo-variable `mode` (lockstep, random or tally),
+so the mask-level and the count-level random-delivery modes are timed
+alternately on one plan each:
+
+    python tools/ab_inproc.py --variants "mask=mode:random;tally=mode:tally" --shapes "1024,341,100000,0"
+
+Every line also reports
 the live node-rounds per second its launches represent (bench.py node_rounds),
 so variants that change the outcome (a diagnostic cap) compare per unit of work.
 """
@@ -52,12 +59,18 @@ def main():
     for sp in a.shapes.split(";"):
         v = [int(x) for x in sp.split(",")]
         shapes.append((v[0], v[1], v[2], v[3] if len(v) > 3 else v[1]))
+    modes = {name: env.pop("mode", None) for name, env in variants}   # `mode` is no environment variable
     knobs = sorted({k for _, env in variants for k in env})
 
     import benor
     unknown = [k for k in knobs if k not in benor.KNOBS]
     if unknown:
         ap.error(f"not a registered libbenor knob (benor.KNOBS): {unknown}")
+    mode_ids = {"lockstep": benor.BO_MODE_LOCKSTEP, "random": benor.BO_MODE_RANDOM_DELIVERY,
+                "tally": benor.BO_MODE_RANDOM_TALLY}
+    bad = sorted({v for v in modes.values() if v is not None and v not in mode_ids})
+    if bad:
+        ap.error(f"mode must be one of {sorted(mode_ids)}: {bad}")
 
     import numpy as np
     import torch
@@ -75,12 +88,17 @@ def main():
 
     times, work = {}, {}
     for N, F, T, f in shapes:
-        mode = benor.BO_MODE_RANDOM_DELIVERY if f < F else benor.BO_MODE_LOCKSTEP
-        plan = benor.TrialsPlan(N, F, [i < f for i in range(N)], seed=0x5EED + N, k_max=32, mode=mode)
-        h = torch.zeros(plan.hist_len, dtype=torch.int64, device="cuda")
-        for _, env in variants:                       # warm-up per variant (allocations, code load)
+        dflt = benor.BO_MODE_RANDOM_DELIVERY if f < F else benor.BO_MODE_LOCKSTEP
+        plans = {}                                    # one plan per delivery mode the variants name
+        for name, _ in variants:
+            mode = mode_ids[modes[name]] if modes[name] else dflt
+            if mode not in plans:
+                plans[mode] = benor.TrialsPlan(N, F, [i < f for i in range(N)], seed=0x5EED + N, k_max=32, mode=mode)
+            plans[name] = plans[mode]
+        h = torch.zeros(plans[variants[0][0]].hist_len, dtype=torch.int64, device="cuda")
+        for name, env in variants:                    # warm-up per variant (allocations, code load)
             set_env(env)
-            plan.launch(0, max(1, T // 10), h.data_ptr(), st.cuda_stream)
+            plans[name].launch(0, max(1, T // 10), h.data_ptr(), st.cuda_stream)
         torch.cuda.synchronize()
         nxt = T
         for rnd in range(a.rounds):
@@ -91,7 +109,7 @@ def main():
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(st)
                 for _ in range(a.reps):
-                    plan.launch(nxt, T, h.data_ptr(), st.cuda_stream)
+                    plans[name].launch(nxt, T, h.data_ptr(), st.cuda_stream)
                     nxt += T
                 e1.record(st)
                 torch.cuda.synchronize()
