@@ -3,9 +3,11 @@
     python -m benor.cli start [--N 10 --faulty 0,1,2,3 --init 1,1,...]   # src/start.ts
     python -m benor.cli trials --N 1024 --F 341 --trials 1000000          # one batch, JSON summary
     python -m benor.cli trials --N 1024 --F 341 --mode tally --crashed 0  # f = 0 crashed, count-level random delivery
+    python -m benor.cli trials --N 10 --F 4 --mode tally3 --crashed 0     # the same for any quorum (ties, coins)
     python -m benor.cli sweep --N 64,128,...,4096 --steps 32 --trials 2**30 --out sweep.csv
                                                                           # C5 phase diagram
     python -m benor.cli sweep --cells 4096:0,4096:1984 --per-cell 4793490  # two cells of it
+    python -m benor.cli sweep --mode tally3 --crashed 0 --N 64,128 --steps 8  # the diagram under random delivery
 
 `start` re-states src/start.ts:6-43: same default scenario (N = 10, nodes
 0-3 faulty, every initial value 1), same checks ("Lengths don't match",
@@ -17,7 +19,9 @@ with F = floor(phi * N), phi on a `--steps` grid in [0, 0.5); the total trial
 budget is split evenly over cells, each cell's trials split across ranks
 (torch.distributed, one process per GPU).  All cells are launched back to back
 into one [cells, H] histogram buffer, merged with a single all-reduce.  Rows: N, F, m, trials, decided fraction, E[R], P(R = 1..4), P(v = 1),
-undecided, agreement violations.
+undecided, agreement violations.  `--mode tally3 --crashed f` draws the same
+diagram under count-level random delivery (BO_MODE_RANDOM_TALLY3) with the first
+f nodes of every cell crashed (f at most each cell's F; the rows' m is N - f).
 """
 from __future__ import annotations
 
@@ -40,8 +44,8 @@ def _ints(s: str) -> list[int]:
     return [_int(part) for part in s.split(",") if part.strip()]
 
 
-def summarize(hist: np.ndarray, N: int, F: int, k_max: int) -> dict:
-    m = N - F
+def summarize(hist: np.ndarray, N: int, F: int, k_max: int, crashed: int | None = None) -> dict:
+    m = N - (F if crashed is None else crashed)
     trials = int(hist[:-1].sum())
     dec = np.array([int(hist[r * 3] + hist[r * 3 + 1] + hist[r * 3 + 2]) for r in range(1, k_max + 1)])
     decided = int(dec.sum())
@@ -77,7 +81,7 @@ def cmd_trials(a) -> int:
     import benor
 
     mode = {"lockstep": benor.BO_MODE_LOCKSTEP, "random": benor.BO_MODE_RANDOM_DELIVERY,
-            "tally": benor.BO_MODE_RANDOM_TALLY}[a.mode]
+            "tally": benor.BO_MODE_RANDOM_TALLY, "tally3": benor.BO_MODE_RANDOM_TALLY3}[a.mode]
     crashed = a.F if a.crashed is None else a.crashed            # the first f nodes (start.ts:7-18 placement)
     plan = benor.TrialsPlan(a.N, a.F, [i < crashed for i in range(a.N)], seed=a.seed, k_max=a.k_max, mode=mode)
     t0 = time.perf_counter()
@@ -117,7 +121,17 @@ def cmd_sweep(a) -> int:
     else:
         cells = grid_cells(_ints(a.N), a.steps)
     per_cell = _int(str(a.per_cell)) if a.per_cell else max(1, _int(str(a.trials)) // len(cells))
-    rows, elapsed = run_sweep(cells, per_cell, a.seed, a.k_max, a.streams, rank, world, a.progress)
+    if a.mode == "lockstep" and a.crashed is not None:
+        raise SystemExit("sweep --crashed needs --mode tally3 (lockstep crashes exactly F nodes per cell)")
+    if a.mode == "tally3":
+        crashed = 0 if a.crashed is None else a.crashed
+        bad = [f"{N}:{F}" for (N, F) in cells if crashed > F]
+        if bad:
+            raise SystemExit(f"sweep --crashed {crashed} exceeds F in cells {','.join(bad)}")
+        rows, elapsed = run_sweep(cells, per_cell, a.seed, a.k_max, a.streams, rank, world, a.progress,
+                                  mode="tally3", crashed=crashed)
+    else:
+        rows, elapsed = run_sweep(cells, per_cell, a.seed, a.k_max, a.streams, rank, world, a.progress)
     if rank == 0:
         out = open(a.out, "w") if a.out else sys.stdout
         out.write(rows_csv(rows))
@@ -139,10 +153,13 @@ def rows_csv(rows: list[dict]) -> str:
     return ",".join(keys) + "\n" + "".join(",".join(str(r[k]) for k in keys) + "\n" for r in rows)
 
 
-def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progress=False):
+def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progress=False, mode="lockstep",
+              crashed=None):
     """The sweep's GPU work on the current device: (rows, seconds).  Under
     torch.distributed (world > 1) each cell's trials are split over the ranks
-    and the histograms merged by one all-reduce."""
+    and the histograms merged by one all-reduce.  mode "lockstep": F crashed
+    per cell; "tally3": BO_MODE_RANDOM_TALLY3 with the first `crashed` nodes of
+    every cell crashed (a count, at most each cell's F; default 0)."""
     import torch
 
     import benor
@@ -159,7 +176,18 @@ def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progre
     # round-robin over --streams streams: each plan owns its buffers, so cells are
     # independent, and one cell's short passes (deferred-trial rounds, the last
     # groups of a launch) overlap the next cell's launches instead of idling CUs.
-    plans = [benor.TrialsPlan(N, F, seed=seed ^ (N << 20) ^ F, k_max=k_max) for (N, F) in cells]
+    if mode == "lockstep":
+        if crashed is not None:
+            raise ValueError("crashed needs mode 'tally3' (lockstep crashes exactly F nodes per cell)")
+        plans = [benor.TrialsPlan(N, F, seed=seed ^ (N << 20) ^ F, k_max=k_max) for (N, F) in cells]
+    elif mode == "tally3":
+        crashed = 0 if crashed is None else crashed
+        if any(crashed > F for (_, F) in cells):
+            raise ValueError(f"crashed = {crashed} exceeds a cell's F")
+        plans = [benor.TrialsPlan(N, F, [i < crashed for i in range(N)], seed=seed ^ (N << 20) ^ F, k_max=k_max,
+                                  mode=benor.BO_MODE_RANDOM_TALLY3) for (N, F) in cells]
+    else:
+        raise ValueError(f"mode must be 'lockstep' or 'tally3': {mode!r}")
     H = plans[0].hist_len
     hists = torch.zeros((len(cells), H), dtype=torch.int64, device="cuda")
     streams = [stream] + [torch.cuda.Stream() for _ in range(max(1, streams_n) - 1)]
@@ -174,7 +202,7 @@ def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progre
         stream.wait_stream(s)
     merge_histogram(hists)
     allh = hists.cpu().numpy().astype(np.uint64)
-    rows = [summarize(allh[ci], N, F, k_max) for ci, (N, F) in enumerate(cells)]
+    rows = [summarize(allh[ci], N, F, k_max, crashed) for ci, (N, F) in enumerate(cells)]
     elapsed = time.perf_counter() - t0
     for plan in plans:
         plan.check()                               # device-side capacity invariants of every cell
@@ -197,10 +225,11 @@ def main(argv=None) -> int:
     t.add_argument("--begin", type=int, default=0)
     t.add_argument("--seed", type=int, default=0x243F6A8885A308D3)
     t.add_argument("--k-max", type=int, default=16)
-    t.add_argument("--mode", choices=["lockstep", "random", "tally"], default="lockstep",
-                   help="delivery model: lockstep, random (mask-level) or tally (count-level random delivery)")
+    t.add_argument("--mode", choices=["lockstep", "random", "tally", "tally3"], default="lockstep",
+                   help="delivery model: lockstep, random (mask-level), tally (count-level random delivery: odd "
+                        "quorum, no '?') or tally3 (count-level, any quorum)")
     t.add_argument("--crashed", type=int, default=None,
-                   help="crash the first f nodes (default F; random and tally take f <= F)")
+                   help="crash the first f nodes (default F; random, tally and tally3 take f <= F)")
     w = sub.add_parser("sweep", help="C5 decision-round phase diagram")
     w.add_argument("--N", default="64,128,256,512,1024,2048,4096")
     w.add_argument("--steps", type=int, default=32)
@@ -210,6 +239,10 @@ def main(argv=None) -> int:
     w.add_argument("--cells", default=None, help="N:F,N:F,... instead of the N x phi grid")
     w.add_argument("--per-cell", default=None, help="trials per cell (default: --trials / cells)")
     w.add_argument("--streams", type=int, default=4, help="HIP streams the cells are spread over")
+    w.add_argument("--mode", choices=["lockstep", "tally3"], default="lockstep",
+                   help="delivery model of every cell: lockstep (F crashed) or tally3 (count-level random delivery)")
+    w.add_argument("--crashed", type=int, default=None,
+                   help="tally3: crash the first f nodes of every cell (default 0; at most each cell's F)")
     w.add_argument("--out", default=None)
     w.add_argument("--progress", action="store_true")
     a = ap.parse_args(argv)

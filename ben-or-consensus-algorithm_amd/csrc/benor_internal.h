@@ -17,6 +17,7 @@ constexpr uint32_t kStreamDelivery = 2u;
 constexpr uint32_t kStreamOrder = 3u;
 constexpr uint32_t kStreamCrash = 4u;
 constexpr uint32_t kStreamTally = 5u;
+constexpr uint32_t kStreamWalk = 6u;       // BO_MODE_RANDOM_TALLY3: the smallest class's selection-sampling draws
 
 constexpr int kWavesPerBlock = 4;          // 256-thread workgroups, one trial per wave
 
@@ -49,10 +50,13 @@ struct KParams {
                             //    serves its state launches),
                             // 6: lane lockstep (m <= 64), 1: W-specialised lockstep (W <= kMaxWSpecialised = 32),
                             // 0: blocked lockstep, 2: random delivery, 4: event level,
-                            // 9: count-level random delivery (benor_tally.hip)
+                            // 9: count-level random delivery (benor_tally.hip),
+                            // 10: three-valued count-level random delivery (benor_tally3.hip)
   uint32_t base_variant;    // variant 7: the popcount kernel (1 W, 0 blocked) that serves the state
   uint32_t base_G;          //   launches and the deferred trials, and its G
-  uint32_t mode;            // BO_MODE_LOCKSTEP / BO_MODE_RANDOM_DELIVERY / BO_MODE_EVENT / BO_MODE_RANDOM_TALLY
+  uint32_t mode;            // BO_MODE_LOCKSTEP / BO_MODE_RANDOM_DELIVERY / BO_MODE_EVENT / BO_MODE_RANDOM_TALLY /
+                            // BO_MODE_RANDOM_TALLY3 (a BO_MODE_RANDOM_TALLY3 plan inside mode 3's scope holds
+                            // BO_MODE_RANDOM_TALLY here: it is that mode's plan)
   uint32_t q;               // quorum N - F (messages each receiver tallies per phase)
   uint32_t k_max;
   uint32_t init_mode;       // BO_INIT_RANDOM / BO_INIT_FIXED
@@ -80,7 +84,7 @@ struct KParams {
   // rd_b-bit index fields; rd_a = 0 selects Floyd (oracle_delivery_bernoulli)
   uint32_t rd_a, rd_b;
   uint32_t rd_rows;                // Bernoulli sampler: bitset rows per lane, max(ceil(m/32), 2^rd_b / 32)
-  // count-level random delivery (variant 9): the plan's threshold table -- row K of
+  // count-level random delivery (variants 9 and 10): the plan's threshold table -- row K of
   // HG(m, K, q) is tally_thr[tally_off[K] .. tally_off[K + 1]), K = 0..m; no row is
   // longer than tally_cap = min(q, m - q), the size of a wave's LDS row region
   const uint32_t *tally_off;
@@ -173,6 +177,11 @@ hipError_t launch_random_bern(const KParams &p, int grid_blocks, hipStream_t str
 uint32_t tally_wave_bytes(uint32_t W, uint32_t cap);
 int tally_blocks_per_cu(const KParams &p);        // resident workgroups per CU (registers, LDS); 0 = unknown
 hipError_t launch_tally(const KParams &p, int grid_blocks, hipStream_t stream);
+
+// Three-valued count-level random delivery (benor_tally3.hip): the same per-wave
+// LDS (a phase hands on its class sizes only; "?" is held by no node after round 1).
+int tally3_blocks_per_cu(const KParams &p);       // resident workgroups per CU (registers, LDS); 0 = unknown
+hipError_t launch_tally3(const KParams &p, int grid_blocks, hipStream_t stream);
 
 // Event level for kMaxEventN < N <= BO_MAX_N (benor_event_big.hip): one wave per trial.
 // The wave-per-trial event kernel keeps its message pool in LDS when it is at

@@ -643,10 +643,11 @@ void plan_geometry(KParams &p) {
     p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
     return;
   }
-  if (p.mode == BO_MODE_RANDOM_TALLY) {             // count-level random delivery (benor_tally.hip)
+  if (p.mode == BO_MODE_RANDOM_TALLY || p.mode == BO_MODE_RANDOM_TALLY3) {
+    // count-level random delivery (benor_tally.hip); three-valued: benor_tally3.hip, the same LDS layout
     p.G = 1;
     p.nblocks = W;
-    p.variant = 9;
+    p.variant = p.mode == BO_MODE_RANDOM_TALLY ? 9u : 10u;
     const uint32_t e = p.m - p.q;
     p.tally_cap = p.q <= e ? p.q : e;               // the widest row of HG(m, ., q)
     p.wave_bytes = (tally_wave_bytes(W, p.tally_cap) + 15u) & ~15u;   // x ballots + one staged row
@@ -785,6 +786,7 @@ hipError_t launch_lockstep(const KParams &p, int grid, hipStream_t s) {
     return launch_lockstep(q, grid, s);
   }
   if (p.variant == 9) return launch_tally(p, grid, s);
+  if (p.variant == 10) return launch_tally3(p, grid, s);
   if (p.variant == 2 && p.rd_a) return launch_random_bern(p, grid, s);
   if (p.variant == 2) {                      // Floyd sampler
     if (p.lds_bytes > 64u * 1024u) {
@@ -893,6 +895,10 @@ int lockstep_grid(const KParams &p, int device) {
   }
   if (p.variant == 9) {                      // count-level random delivery: its unrolled forms are register-bound
     const uint64_t fit = (uint64_t)tally_blocks_per_cu(p);
+    if (fit >= 1u && fit < per_cu) per_cu = fit;
+  }
+  if (p.variant == 10) {                     // its three-valued form: one kernel for every W
+    const uint64_t fit = (uint64_t)tally3_blocks_per_cu(p);
     if (fit >= 1u && fit < per_cu) per_cu = fit;
   }
   // Lane kernel: a short launch spread over every wave slot (~2 trials per

@@ -507,9 +507,10 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   if (cfg->N < 1 || cfg->N > BO_MAX_N) return fail(BO_ERR_UNSUPPORTED, "N must be in [1, 4096]");
   if (cfg->k_max < 1 || cfg->k_max > BO_MAX_K) return fail(BO_ERR_INVALID_ARGUMENT, "k_max must be in [1, 1024]");
   if (cfg->mode != BO_MODE_LOCKSTEP && cfg->mode != BO_MODE_RANDOM_DELIVERY && cfg->mode != BO_MODE_EVENT &&
-      cfg->mode != BO_MODE_RANDOM_TALLY)
+      cfg->mode != BO_MODE_RANDOM_TALLY && cfg->mode != BO_MODE_RANDOM_TALLY3)
     return fail(BO_ERR_UNSUPPORTED, "unknown delivery mode");
-  const bool random_mode = cfg->mode == BO_MODE_RANDOM_DELIVERY || cfg->mode == BO_MODE_RANDOM_TALLY;
+  const bool random_mode = cfg->mode == BO_MODE_RANDOM_DELIVERY || cfg->mode == BO_MODE_RANDOM_TALLY ||
+                           cfg->mode == BO_MODE_RANDOM_TALLY3;
   if (cfg->init_mode != BO_INIT_RANDOM && cfg->init_mode != BO_INIT_FIXED)
     return fail(BO_ERR_INVALID_ARGUMENT, "unknown init_mode");
   if (!cfg->faulty) return fail(BO_ERR_INVALID_ARGUMENT, "faulty is NULL");
@@ -567,6 +568,9 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
     return fail(BO_ERR_UNSUPPORTED, "BO_MODE_RANDOM_TALLY needs an odd quorum N - F: use BO_MODE_RANDOM_DELIVERY");
   if (cfg->mode == BO_MODE_RANDOM_TALLY && kp.init_q)
     return fail(BO_ERR_UNSUPPORTED, "BO_MODE_RANDOM_TALLY takes no \"?\" initial value: use BO_MODE_RANDOM_DELIVERY");
+  // The three-valued mode is a superset: inside that scope it is that mode's plan
+  // (its kernel, its results bit for bit); outside, benor_tally3.hip.
+  if (cfg->mode == BO_MODE_RANDOM_TALLY3 && (kp.q & 1u) && !kp.init_q) kp.mode = BO_MODE_RANDOM_TALLY;
   benor::plan_geometry(kp);   // after init_q: the kernel choice depends on the round-1 vote parity
   return BO_OK;
 }
@@ -685,7 +689,7 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
       kp.init_x = pl->d_init_x;
       kp.crash_at = pl->d_crash;
       kp.scratch = pl->d_scratch;
-    } else if (cfg->mode == BO_MODE_RANDOM_TALLY) {
+    } else if (kp.variant == 9 || kp.variant == 10) {   // BO_MODE_RANDOM_TALLY, BO_MODE_RANDOM_TALLY3
       // the whole table HG(m, K, q), K = 0..m: at most ~3.7 * 10^6 thresholds (30 MB) at m = 4096
       std::vector<uint32_t> off(m + 2u, 0u);
       std::vector<uint64_t> thr;
@@ -737,12 +741,14 @@ int bo_plan_kernel(const bo_plan *pl) {
 // is odd: then no R-phase count can tie, no proposal is "?" (node.ts:63-69),
 // and c0 = m - c1.  So 2 counts of ceil(m/32) words for odd M (the bench's
 // m = 683), 3 for even M (round-1 parity: M = m - init_q).  Random delivery
-// counts both values in both phases: 4 (the count-level mode answers the same
-// unit: the work it stands in for).
+// counts both values in both phases: 4 (the count-level modes answer the same
+// unit: the work they stand in for).
 uint64_t bo_plan_popc_words_per_node_round(const bo_plan *pl) {
   if (!pl) return 0;
   uint64_t counts = 4ull;
-  if (pl->kp.mode != BO_MODE_RANDOM_DELIVERY && pl->kp.mode != BO_MODE_RANDOM_TALLY) counts = ((pl->kp.m - pl->kp.init_q) & 1u) ? 2ull : 3ull;
+  if (pl->kp.mode != BO_MODE_RANDOM_DELIVERY && pl->kp.mode != BO_MODE_RANDOM_TALLY &&
+      pl->kp.mode != BO_MODE_RANDOM_TALLY3)
+    counts = ((pl->kp.m - pl->kp.init_q) & 1u) ? 2ull : 3ull;
   return counts * ((pl->kp.m + 31ull) / 32ull);
 }
 

@@ -84,8 +84,10 @@ export interface TrialsConfig {
   trialBegin?: bigint | number;
   trialCount?: bigint | number;
   /** 0 lockstep (default), 1 random delivery (f <= F), 2 event level (N <= 4096),
-   *  3 random delivery at the level of counts (MODE_RANDOM_TALLY: f <= F, N - F odd, no "?" initial value) */
-  mode?: 0 | 1 | 2 | 3;
+   *  3 random delivery at the level of counts (MODE_RANDOM_TALLY: f <= F, N - F odd, no "?" initial value),
+   *  4 the same for any quorum and with "?" initial values (MODE_RANDOM_TALLY3: f <= F; three vote classes,
+   *    ties and coins; equal to mode 3 bit for bit wherever mode 3 is defined) */
+  mode?: 0 | 1 | 2 | 3 | 4;
   /** event mode: deliveries after which node i is stopped (null = never) */
   crashAt?: (number | null)[];
   /** event mode, random schedule: stop crashCount live nodes at uniform delivery counts in [0, crashWindow) */
@@ -98,6 +100,7 @@ export declare const MODE_LOCKSTEP: 0;
 export declare const MODE_RANDOM_DELIVERY: 1;
 export declare const MODE_EVENT: 2;
 export declare const MODE_RANDOM_TALLY: 3;
+export declare const MODE_RANDOM_TALLY3: 4;
 
 /** Outcome histogram, (kMax + 1) * 3 + 1 bins (include/benor.h). */
 export declare function runTrials(cfg: TrialsConfig): Promise<BigUint64Array>;

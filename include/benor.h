@@ -73,7 +73,25 @@ enum {
  * coin is drawn); other configurations return BO_ERR_UNSUPPORTED -- run them in
  * BO_MODE_RANDOM_DELIVERY.  Validation is RANDOM_DELIVERY's (at most F
  * faulty).  At f == F it equals LOCKSTEP bit for bit. */
-enum { BO_MODE_LOCKSTEP = 0, BO_MODE_RANDOM_DELIVERY = 1, BO_MODE_EVENT = 2, BO_MODE_RANDOM_TALLY = 3 };
+/* RANDOM_TALLY3 is RANDOM_TALLY without its scope: any quorum, "?" initial
+ * values allowed.  A phase's votes fall into three classes -- K0 zeros, K1 ones,
+ * Kq "?" (K0 + K1 + Kq = m) -- and a receiver's (c0, c1, c?) is multivariate
+ * hypergeometric over them with N-F draws.  One class count comes from the same
+ * table and the same stream-5 uniform as RANDOM_TALLY; the smallest class is then
+ * walked member by member (selection sampling, exact integer draws from Philox
+ * stream 6), and the third count is the remainder.  R-phase ties
+ * propose "?", P-phase ties and empty tallies take the node's coin (the coin
+ * stream of every batch mode).  A configuration inside RANDOM_TALLY's scope (odd
+ * quorum, no live "?") runs RANDOM_TALLY's kernel and gives its results bit for
+ * bit; at f == F the mode equals LOCKSTEP bit for bit, "?" and even m included.
+ * Validation is RANDOM_DELIVERY's (at most F faulty). */
+enum {
+  BO_MODE_LOCKSTEP = 0,
+  BO_MODE_RANDOM_DELIVERY = 1,
+  BO_MODE_EVENT = 2,
+  BO_MODE_RANDOM_TALLY = 3,
+  BO_MODE_RANDOM_TALLY3 = 4
+};
 
 enum { BO_INIT_RANDOM = 0, BO_INIT_FIXED = 1 };
 
@@ -207,7 +225,7 @@ typedef struct bo_trials_cfg {
     uint32_t mode;            /* BO_MODE_* */
     uint32_t reserved;
     uint64_t seed;            /* Philox4x32-10 key */
-    const uint8_t *faulty;    /* host [N]; exactly F set (LOCKSTEP, EVENT), at most F (RANDOM_DELIVERY, RANDOM_TALLY) */
+    const uint8_t *faulty;    /* host [N]; exactly F set (LOCKSTEP, EVENT), at most F (RANDOM_DELIVERY, RANDOM_TALLY, RANDOM_TALLY3) */
     const int8_t *init;       /* host [N]; used when init_mode == BO_INIT_FIXED */
     /* EVENT mode only: GET /stop schedule.  crash_at[i] = number of deliveries
      * after which node i is stopped (UINT32_MAX = never), or, when crash_at is
@@ -257,7 +275,7 @@ int bo_plan_check(bo_plan *plan);
  * (c0 = M - c1); the P-phase counts c1 when M is odd (no tie, so no "?"
  * proposal: c0 = m - c1) and c0, c1 otherwise -- 2 or 3 x ceil(m/32).
  * RANDOM_DELIVERY: both values in both phases, 4 x ceil(m/32).  RANDOM_TALLY
- * answers RANDOM_DELIVERY's unit, the work it stands in for. */
+ * and RANDOM_TALLY3 answer RANDOM_DELIVERY's unit, the work they stand in for. */
 uint64_t bo_plan_popc_words_per_node_round(const bo_plan *plan);
 uint32_t bo_plan_live_nodes(const bo_plan *plan);
 
@@ -277,9 +295,13 @@ enum {
                               64 * min(32/m, 8) trials per wave iteration, block-diagonal e2m1 products;
                               launches of fewer than 5 * 10^5 trials run the lane kernel
                               (BENOR_SMALL_MIN_TRIALS overrides) */
-  BO_KERNEL_TALLY = 9       /* BO_MODE_RANDOM_TALLY: one wave per trial, per-receiver hypergeometric counts
+  BO_KERNEL_TALLY = 9,      /* BO_MODE_RANDOM_TALLY: one wave per trial, per-receiver hypergeometric counts
                               by binary search in a table row staged in LDS; batch and per-node-state
-                              launches alike, no overflow or deferral state */
+                              launches alike, no overflow or deferral state; also what
+                              BO_MODE_RANDOM_TALLY3 runs inside that mode's scope */
+  BO_KERNEL_TALLY3 = 10     /* BO_MODE_RANDOM_TALLY3 outside RANDOM_TALLY's scope (even quorum or a live "?"
+                              initial value): one wave per trial, three vote classes -- one count from the
+                              table, the smallest class walked by selection sampling, coins on ties */
 };
 
 /* The kernel family bo_plan_launch runs for this plan.  (The per-node-state

@@ -14,7 +14,7 @@ median and minimum ms per launch and the variant's median / first variant's.
 
 A shape may carry a fourth field f < F (the first f nodes crashed, the rest of
 F the random-delivery slack: BO_MODE_RANDOM_DELIVERY).  A variant may also name
-the delivery mode with the pseudo-variable `mode` (lockstep, random or tally),
+the delivery mode with the pseudo-variable `mode` (lockstep, random, tally or tally3),
 so the mask-level and the count-level random-delivery modes are timed
 alternately on one plan each:
 
@@ -67,7 +67,7 @@ def main():
     if unknown:
         ap.error(f"not a registered libbenor knob (benor.KNOBS): {unknown}")
     mode_ids = {"lockstep": benor.BO_MODE_LOCKSTEP, "random": benor.BO_MODE_RANDOM_DELIVERY,
-                "tally": benor.BO_MODE_RANDOM_TALLY}
+                "tally": benor.BO_MODE_RANDOM_TALLY, "tally3": benor.BO_MODE_RANDOM_TALLY3}
     bad = sorted({v for v in modes.values() if v is not None and v not in mode_ids})
     if bad:
         ap.error(f"mode must be one of {sorted(mode_ids)}: {bad}")
