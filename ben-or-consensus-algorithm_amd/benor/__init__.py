@@ -39,7 +39,10 @@ BO_MODE_RANDOM_DELIVERY = 1
 BO_MODE_EVENT = 2
 BO_MODE_RANDOM_TALLY = 3       # random delivery at the level of counts (odd quorum, no "?" initial value)
 BO_MODE_RANDOM_TALLY3 = 4      # ... any quorum, "?" allowed: three vote classes, ties and coins (a superset of mode 3)
-NEVER = 0xFFFFFFFF             # crash_at entry: never stopped
+BO_MODE_CRASH_TALLY = 5        # mode 4 with crashes during the run: crash_at[i] = node i's step (2(r-1): R-phase of
+                               # round r, +1: its P-phase), or crash_count nodes at random steps below crash_window
+CRASH_TABLE_MAX_BYTES = 512 << 20   # mode 5: thresholds of the tables of all reachable live counts, at most
+NEVER = 0xFFFFFFFF             # crash_at entry: never stopped / never crashes
 BO_INIT_RANDOM = 0
 BO_INIT_FIXED = 1
 BO_KERNEL_NONE = -1
@@ -52,11 +55,13 @@ BO_KERNEL_MFMA = 7
 BO_KERNEL_MFMA_SMALL = 8
 BO_KERNEL_TALLY = 9
 BO_KERNEL_TALLY3 = 10
+BO_KERNEL_TALLY_CRASH = 11
 KERNEL_NAMES = {BO_KERNEL_NONE: "none", BO_KERNEL_BLOCKED: "blocked popcount", BO_KERNEL_W: "W popcount",
                 BO_KERNEL_RANDOM: "random delivery", BO_KERNEL_EVENT: "event level", BO_KERNEL_LANE: "lane",
                 BO_KERNEL_MFMA: "matrix core (e2m1 MFMA)", BO_KERNEL_MFMA_SMALL: "packed matrix core (e2m1 MFMA, m <= 32)",
                 BO_KERNEL_TALLY: "count-level random delivery (hypergeometric tallies)",
-                BO_KERNEL_TALLY3: "count-level random delivery, three vote classes (hypergeometric tally + walk)"}
+                BO_KERNEL_TALLY3: "count-level random delivery, three vote classes (hypergeometric tally + walk)",
+                BO_KERNEL_TALLY_CRASH: "count-level random delivery with crashes during the run (a table per live count)"}
 BO_MAX_N = 4096
 BO_MAX_K = 1024
 

@@ -4,6 +4,9 @@
     python -m benor.cli trials --N 1024 --F 341 --trials 1000000          # one batch, JSON summary
     python -m benor.cli trials --N 1024 --F 341 --mode tally --crashed 0  # f = 0 crashed, count-level random delivery
     python -m benor.cli trials --N 10 --F 4 --mode tally3 --crashed 0     # the same for any quorum (ties, coins)
+    python -m benor.cli trials --N 1024 --F 340 --mode crash --crashed 0 --crash-count 16 --crash-window 4
+                                                                          # ... with 16 crashes in rounds 1-2
+    python -m benor.cli trials --N 10 --F 4 --mode crash --crashed 1 --crash-at 3:0,7:1   # node 3 at step 0, node 7 at step 1
     python -m benor.cli sweep --N 64,128,...,4096 --steps 32 --trials 2**30 --out sweep.csv
                                                                           # C5 phase diagram
     python -m benor.cli sweep --cells 4096:0,4096:1984 --per-cell 4793490  # two cells of it
@@ -81,15 +84,36 @@ def cmd_trials(a) -> int:
     import benor
 
     mode = {"lockstep": benor.BO_MODE_LOCKSTEP, "random": benor.BO_MODE_RANDOM_DELIVERY,
-            "tally": benor.BO_MODE_RANDOM_TALLY, "tally3": benor.BO_MODE_RANDOM_TALLY3}[a.mode]
+            "tally": benor.BO_MODE_RANDOM_TALLY, "tally3": benor.BO_MODE_RANDOM_TALLY3,
+            "crash": benor.BO_MODE_CRASH_TALLY}[a.mode]
     crashed = a.F if a.crashed is None else a.crashed            # the first f nodes (start.ts:7-18 placement)
-    plan = benor.TrialsPlan(a.N, a.F, [i < crashed for i in range(a.N)], seed=a.seed, k_max=a.k_max, mode=mode)
+    sched = {}
+    if a.mode == "crash":                                         # crashes during the run, in steps
+        if a.crash_at and a.crash_count:
+            raise SystemExit("--crash-at and --crash-count are exclusive")
+        if a.crash_at:
+            crash_at = [None] * a.N
+            for part in a.crash_at.split(","):
+                node, _, step = part.partition(":")
+                if not 0 <= int(node) < a.N:
+                    raise SystemExit(f"--crash-at: node {node} is not in [0, {a.N})")
+                crash_at[int(node)] = int(step)
+            sched = {"crash_at": crash_at}
+        else:
+            sched = {"crash_count": a.crash_count, "crash_window": a.crash_window}
+    elif a.crash_at or a.crash_count:
+        raise SystemExit("--crash-at / --crash-count need --mode crash")
+    plan = benor.TrialsPlan(a.N, a.F, [i < crashed for i in range(a.N)], seed=a.seed, k_max=a.k_max, mode=mode,
+                            **sched)
     t0 = time.perf_counter()
     h = plan.run(a.begin, a.trials)
     dt = time.perf_counter() - t0
     row = summarize(h, a.N, a.F, a.k_max)
     if a.mode != "lockstep" or a.crashed is not None:
         row.update(m=a.N - crashed, mode=a.mode, crashed=crashed, hist=[int(v) for v in h])
+    if a.mode == "crash":                                         # m is the initially-live count
+        row.update(crash_count=a.crash_count, crash_window=a.crash_window, crash_at=a.crash_at,
+                   kernel=benor.KERNEL_NAMES[plan.kernel])
     row["seconds"] = dt
     print(json.dumps(row))
     return 0
@@ -225,11 +249,16 @@ def main(argv=None) -> int:
     t.add_argument("--begin", type=int, default=0)
     t.add_argument("--seed", type=int, default=0x243F6A8885A308D3)
     t.add_argument("--k-max", type=int, default=16)
-    t.add_argument("--mode", choices=["lockstep", "random", "tally", "tally3"], default="lockstep",
+    t.add_argument("--mode", choices=["lockstep", "random", "tally", "tally3", "crash"], default="lockstep",
                    help="delivery model: lockstep, random (mask-level), tally (count-level random delivery: odd "
-                        "quorum, no '?') or tally3 (count-level, any quorum)")
+                        "quorum, no '?'), tally3 (count-level, any quorum) or crash (tally3 with crashes during the run)")
     t.add_argument("--crashed", type=int, default=None,
-                   help="crash the first f nodes (default F; random, tally and tally3 take f <= F)")
+                   help="crash the first f nodes (default F; random, tally, tally3 and crash take f <= F)")
+    t.add_argument("--crash-count", type=int, default=0,
+                   help="crash: this many initially-live nodes crash, drawn per trial (f + count <= F)")
+    t.add_argument("--crash-window", type=int, default=0,
+                   help="crash: ... at uniform steps below this (step 2(r-1): R-phase of round r, +1: its P-phase)")
+    t.add_argument("--crash-at", default=None, help="crash: explicit schedule node:step,node:step,...")
     w = sub.add_parser("sweep", help="C5 decision-round phase diagram")
     w.add_argument("--N", default="64,128,256,512,1024,2048,4096")
     w.add_argument("--steps", type=int, default=32)

@@ -18,6 +18,7 @@ constexpr uint32_t kStreamOrder = 3u;
 constexpr uint32_t kStreamCrash = 4u;
 constexpr uint32_t kStreamTally = 5u;
 constexpr uint32_t kStreamWalk = 6u;       // BO_MODE_RANDOM_TALLY3: the smallest class's selection-sampling draws
+constexpr uint32_t kStreamSchedule = 7u;   // BO_MODE_CRASH_TALLY: a trial's random crash schedule (Floyd's algorithm)
 
 constexpr int kWavesPerBlock = 4;          // 256-thread workgroups, one trial per wave
 
@@ -38,6 +39,15 @@ constexpr uint32_t kMaxEventLdsN = 31;     // event level: inbox counters in LDS
 constexpr uint64_t kMaxTrialsPerLaunch = 1ull << 31;   // trial offsets within a launch fit 32 bits
 constexpr uint32_t kParamBytes = 32;       // LDS parameter block after the histogram (W kernel)
 
+// BO_MODE_CRASH_TALLY: the table of one live count (benor_tally_crash.hip), entry d
+// of the directory = the table of m - d live nodes: its row offsets
+// tally_off[off_base ..], m - d + 2 of them, relative to tally_thr[thr_base].
+struct CrashDir {
+  uint64_t thr_base;
+  uint32_t off_base;
+  uint32_t pad;
+};
+
 struct KParams {
   uint32_t N, F;            // network size, fault parameter
   uint32_t m;               // live (non-crashed) nodes = senders = receivers
@@ -51,12 +61,14 @@ struct KParams {
                             // 6: lane lockstep (m <= 64), 1: W-specialised lockstep (W <= kMaxWSpecialised = 32),
                             // 0: blocked lockstep, 2: random delivery, 4: event level,
                             // 9: count-level random delivery (benor_tally.hip),
-                            // 10: three-valued count-level random delivery (benor_tally3.hip)
+                            // 10: three-valued count-level random delivery (benor_tally3.hip),
+                            // 11: the same with crashes during the run (benor_tally_crash.hip)
   uint32_t base_variant;    // variant 7: the popcount kernel (1 W, 0 blocked) that serves the state
   uint32_t base_G;          //   launches and the deferred trials, and its G
   uint32_t mode;            // BO_MODE_LOCKSTEP / BO_MODE_RANDOM_DELIVERY / BO_MODE_EVENT / BO_MODE_RANDOM_TALLY /
-                            // BO_MODE_RANDOM_TALLY3 (a BO_MODE_RANDOM_TALLY3 plan inside mode 3's scope holds
-                            // BO_MODE_RANDOM_TALLY here: it is that mode's plan)
+                            // BO_MODE_RANDOM_TALLY3 / BO_MODE_CRASH_TALLY (a BO_MODE_RANDOM_TALLY3 plan inside
+                            // mode 3's scope holds BO_MODE_RANDOM_TALLY here: it is that mode's plan; a
+                            // BO_MODE_CRASH_TALLY plan with an empty schedule is BO_MODE_RANDOM_TALLY3's)
   uint32_t q;               // quorum N - F (messages each receiver tallies per phase)
   uint32_t k_max;
   uint32_t init_mode;       // BO_INIT_RANDOM / BO_INIT_FIXED
@@ -134,6 +146,15 @@ struct KParams {
   // diagnostics (BENOR_TIMELINE=<file>, packed matrix-core kernel): per wave,
   // kTimelineWords u64 -- wall-clock stamps of its phases and its batch counts
   unsigned long long *timeline;
+  // count-level random delivery with crashes during the run (variant 11; last, so that the
+  // fields above keep their offsets): m is the initially-live count m0 and
+  // tally_off / tally_thr hold one table per reachable live count, found through
+  // cr_dir[crashes so far]; tally_cap is the m0 table's.  The schedule: cr_n entries
+  // (step << 12 | compact index), the plan's cr_list (device; explicit, steps below 2 k_max
+  // only) or, with cr_random, drawn per trial (cr_n = crash_count nodes, steps below crash_window)
+  const CrashDir *cr_dir;
+  const uint32_t *cr_list;
+  uint32_t cr_n, cr_random;
 };
 
 constexpr uint32_t kTimelineWords = 12;
@@ -182,6 +203,14 @@ hipError_t launch_tally(const KParams &p, int grid_blocks, hipStream_t stream);
 // LDS (a phase hands on its class sizes only; "?" is held by no node after round 1).
 int tally3_blocks_per_cu(const KParams &p);       // resident workgroups per CU (registers, LDS); 0 = unknown
 hipError_t launch_tally3(const KParams &p, int grid_blocks, hipStream_t stream);
+
+// Count-level random delivery with crashes during the run (benor_tally_crash.hip):
+// per-wave LDS of a batch launch (four ballot planes, one staged row, the schedule
+// list and, for a random schedule whose row region is too small for them, a pass
+// of stream-7 words); a per-node-state launch adds two planes by itself.
+uint32_t crash_wave_bytes(uint32_t W, uint32_t cap, uint32_t ncr, bool random);
+int crash_blocks_per_cu(const KParams &p);        // resident workgroups per CU (registers, LDS); 0 = unknown
+hipError_t launch_tally_crash(const KParams &p, int grid_blocks, hipStream_t stream);
 
 // Event level for kMaxEventN < N <= BO_MAX_N (benor_event_big.hip): one wave per trial.
 // The wave-per-trial event kernel keeps its message pool in LDS when it is at

@@ -654,6 +654,17 @@ void plan_geometry(KParams &p) {
     p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
     return;
   }
+  if (p.mode == BO_MODE_CRASH_TALLY) {
+    // ... with crashes during the run (benor_tally_crash.hip): the row region is the m0 table's widest row
+    p.G = 1;
+    p.nblocks = W;
+    p.variant = 11u;
+    const uint32_t e = p.m - p.q;
+    p.tally_cap = p.q <= e ? p.q : e;
+    p.wave_bytes = (crash_wave_bytes(W, p.tally_cap, p.cr_n, p.cr_random != 0u) + 15u) & ~15u;
+    p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
+    return;
+  }
   if (p.m <= kMaxLaneM) {                           // lane kernel: one trial per lane
     const uint32_t M1 = p.m - p.init_q;
     const bool odd = (p.m & 1u) && (M1 & 1u);        // every vote count odd: no tie, no coin
@@ -787,6 +798,7 @@ hipError_t launch_lockstep(const KParams &p, int grid, hipStream_t s) {
   }
   if (p.variant == 9) return launch_tally(p, grid, s);
   if (p.variant == 10) return launch_tally3(p, grid, s);
+  if (p.variant == 11) return launch_tally_crash(p, grid, s);
   if (p.variant == 2 && p.rd_a) return launch_random_bern(p, grid, s);
   if (p.variant == 2) {                      // Floyd sampler
     if (p.lds_bytes > 64u * 1024u) {
@@ -899,6 +911,10 @@ int lockstep_grid(const KParams &p, int device) {
   }
   if (p.variant == 10) {                     // its three-valued form: one kernel for every W
     const uint64_t fit = (uint64_t)tally3_blocks_per_cu(p);
+    if (fit >= 1u && fit < per_cu) per_cu = fit;
+  }
+  if (p.variant == 11) {                     // ... and its form with crashes during the run
+    const uint64_t fit = (uint64_t)crash_blocks_per_cu(p);
     if (fit >= 1u && fit < per_cu) per_cu = fit;
   }
   // Lane kernel: a short launch spread over every wave slot (~2 trials per

@@ -587,7 +587,7 @@ static napi_value run_trials(napi_env env, napi_callback_info info) {
     j->trial_begin = prop_u64(env, o, "trialBegin", 0);
     j->trial_count = prop_u64(env, o, "trialCount", 1);
     uint32_t mode = BO_MODE_LOCKSTEP;
-    prop_u32(env, o, "mode", BO_MODE_LOCKSTEP, &mode);          /* 0 lockstep, 1 random delivery, 2 event, 3 random tally, 4 random tally3 */
+    prop_u32(env, o, "mode", BO_MODE_LOCKSTEP, &mode);          /* 0 lockstep, 1 random delivery, 2 event, 3 random tally, 4 random tally3, 5 crash tally */
     j->cfg.mode = mode;
     prop_u32(env, o, "crashCount", 0, &j->cfg.crash_count);
     prop_u32(env, o, "crashWindow", 0, &j->cfg.crash_window);

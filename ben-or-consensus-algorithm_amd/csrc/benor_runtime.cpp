@@ -142,7 +142,8 @@ struct bo_plan {
   uint64_t defer_words = 0;
   uint32_t *d_flag = nullptr;      // KParams::overflow (bo_plan_check)
   uint64_t *d_stops = nullptr;     // event level, N > 256: sorted /stop schedule
-  unsigned char *d_tally = nullptr;   // RANDOM_TALLY: u32 row offsets [m + 2] (padded to 8 bytes), u64 thresholds
+  unsigned char *d_tally = nullptr;   // RANDOM_TALLY: u32 row offsets [m + 2] (padded to 8 bytes), u64 thresholds;
+                                      // CRASH_TALLY: directory, row offsets, explicit schedule list, thresholds
   int device = 0;
 };
 
@@ -501,16 +502,32 @@ int bo_tally_cdf(uint32_t m, uint32_t q, uint32_t K, uint32_t *lo_out, uint64_t 
 // -------------------------------------------------------------- batch API
 // Validation and kernel planning of a trial configuration, host only: the
 // live-node map, the fixed-init plane and the KParams shape (no device fields).
+// BO_MODE_CRASH_TALLY, host side of a non-empty schedule: the explicit list
+// (step << 12 | compact index, ascending, steps below 2 k_max: no run reaches a
+// later one) and, per number of crashes so far d = 0 .. kp.cr_n, whether the
+// live count m0 - d is reachable and so needs a table.
+struct CrashPlan {
+  std::vector<uint32_t> list;
+  std::vector<uint8_t> reach;
+};
+
+// Thresholds of the table of (m, q): sum over K = 0..m of min(K, q) - max(0, q - (m - K)).
+static uint64_t tally_table_len(uint32_t m, uint32_t q) {
+  uint64_t n = 0;
+  for (uint32_t K = 0; K <= m; ++K) n += (K < q ? K : q) - (K + q > m ? K + q - m : 0u);
+  return n;
+}
+
 static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std::vector<uint4> &plane,
-                     benor::KParams &kp, bool live_run = false) {
+                     benor::KParams &kp, bool live_run = false, CrashPlan *crash = nullptr) {
   if (!cfg) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
   if (cfg->N < 1 || cfg->N > BO_MAX_N) return fail(BO_ERR_UNSUPPORTED, "N must be in [1, 4096]");
   if (cfg->k_max < 1 || cfg->k_max > BO_MAX_K) return fail(BO_ERR_INVALID_ARGUMENT, "k_max must be in [1, 1024]");
   if (cfg->mode != BO_MODE_LOCKSTEP && cfg->mode != BO_MODE_RANDOM_DELIVERY && cfg->mode != BO_MODE_EVENT &&
-      cfg->mode != BO_MODE_RANDOM_TALLY && cfg->mode != BO_MODE_RANDOM_TALLY3)
+      cfg->mode != BO_MODE_RANDOM_TALLY && cfg->mode != BO_MODE_RANDOM_TALLY3 && cfg->mode != BO_MODE_CRASH_TALLY)
     return fail(BO_ERR_UNSUPPORTED, "unknown delivery mode");
   const bool random_mode = cfg->mode == BO_MODE_RANDOM_DELIVERY || cfg->mode == BO_MODE_RANDOM_TALLY ||
-                           cfg->mode == BO_MODE_RANDOM_TALLY3;
+                           cfg->mode == BO_MODE_RANDOM_TALLY3 || cfg->mode == BO_MODE_CRASH_TALLY;
   if (cfg->init_mode != BO_INIT_RANDOM && cfg->init_mode != BO_INIT_FIXED)
     return fail(BO_ERR_INVALID_ARGUMENT, "unknown init_mode");
   if (!cfg->faulty) return fail(BO_ERR_INVALID_ARGUMENT, "faulty is NULL");
@@ -527,6 +544,21 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   for (uint32_t i = 0; i < cfg->N; ++i)
     if (!cfg->faulty[i]) live.push_back(i);
   const uint32_t m = (uint32_t)live.size();
+  // Crashes during the run (BO_MODE_CRASH_TALLY): with the initially faulty nodes at
+  // most F, so every step has a quorum of live senders.
+  uint64_t n_crash = 0;
+  bool crash_random = false;
+  if (cfg->mode == BO_MODE_CRASH_TALLY) {
+    if (cfg->crash_at) {
+      for (uint32_t c = 0; c < m; ++c) n_crash += cfg->crash_at[live[c]] != 0xFFFFFFFFu ? 1u : 0u;
+    } else if (cfg->crash_count > 0) {
+      if (cfg->crash_window < 1) return fail(BO_ERR_INVALID_ARGUMENT, "crash_count > 0 needs crash_window >= 1");
+      n_crash = cfg->crash_count;
+      crash_random = true;
+    }
+    if ((uint64_t)f + n_crash > cfg->F)
+      return fail(BO_ERR_FAULTY_COUNT, "BO_MODE_CRASH_TALLY needs at most F nodes faulty or scheduled to crash");
+  }
   kp = benor::KParams{};
   kp.N = cfg->N;
   kp.F = cfg->F;
@@ -570,7 +602,36 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
     return fail(BO_ERR_UNSUPPORTED, "BO_MODE_RANDOM_TALLY takes no \"?\" initial value: use BO_MODE_RANDOM_DELIVERY");
   // The three-valued mode is a superset: inside that scope it is that mode's plan
   // (its kernel, its results bit for bit); outside, benor_tally3.hip.
-  if (cfg->mode == BO_MODE_RANDOM_TALLY3 && (kp.q & 1u) && !kp.init_q) kp.mode = BO_MODE_RANDOM_TALLY;
+  // A BO_MODE_CRASH_TALLY plan with an empty schedule is the three-valued mode's plan.
+  if (cfg->mode == BO_MODE_CRASH_TALLY && n_crash == 0) kp.mode = BO_MODE_RANDOM_TALLY3;
+  if (kp.mode == BO_MODE_RANDOM_TALLY3 && (kp.q & 1u) && !kp.init_q) kp.mode = BO_MODE_RANDOM_TALLY;
+  if (kp.mode == BO_MODE_CRASH_TALLY) {
+    CrashPlan local;
+    CrashPlan &cp = crash ? *crash : local;
+    cp.list.clear();
+    kp.cr_random = crash_random ? 1u : 0u;
+    if (crash_random) {
+      kp.cr_n = (uint32_t)n_crash;
+      cp.reach.assign(kp.cr_n + 1u, 1);            // every m0 - j, j = 0 .. crash_count
+    } else {
+      for (uint32_t c = 0; c < m; ++c) {
+        const uint32_t s = cfg->crash_at[live[c]];
+        if (s != 0xFFFFFFFFu && (uint64_t)s < 2ull * cfg->k_max) cp.list.push_back(s << 12 | c);
+      }
+      std::sort(cp.list.begin(), cp.list.end());
+      kp.cr_n = (uint32_t)cp.list.size();
+      cp.reach.assign(kp.cr_n + 1u, 0);            // m0 minus the cumulative crashes at each distinct step
+      cp.reach[0] = 1;
+      for (uint32_t i = 0; i < kp.cr_n; ++i)
+        if (i + 1u == kp.cr_n || (cp.list[i + 1u] >> 12) != (cp.list[i] >> 12)) cp.reach[i + 1u] = 1;
+    }
+    uint64_t bytes = 0;
+    for (uint32_t d = 0; d <= kp.cr_n; ++d)
+      if (cp.reach[d]) bytes += 8ull * tally_table_len(m - d, kp.q);
+    if (bytes > BO_CRASH_TABLE_MAX_BYTES)
+      return fail(BO_ERR_UNSUPPORTED, "BO_MODE_CRASH_TALLY: the threshold tables of the reachable live counts exceed "
+                                      "the 512 MiB limit (BO_CRASH_TABLE_MAX_BYTES): schedule fewer crashes");
+  }
   benor::plan_geometry(kp);   // after init_q: the kernel choice depends on the round-1 vote parity
   return BO_OK;
 }
@@ -599,7 +660,8 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
   std::vector<uint32_t> live;
   std::vector<uint4> plane;
   benor::KParams kp0;
-  int rc = plan_host(cfg, live, plane, kp0, live_run);
+  CrashPlan crash;
+  int rc = plan_host(cfg, live, plane, kp0, live_run, &crash);
   if (rc) return rc;
   int dev = 0;
   rc = check_device(&dev);
@@ -707,6 +769,45 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
       if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "tally table upload"); }
       kp.tally_off = reinterpret_cast<const uint32_t *>(pl->d_tally);
       kp.tally_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + off_bytes);
+    } else if (kp.variant == 11) {   // BO_MODE_CRASH_TALLY: one table per reachable live count, and their directory
+      std::vector<benor::CrashDir> dir(kp.cr_n + 1u);
+      std::vector<uint32_t> off;
+      std::vector<uint64_t> thr;
+      std::vector<double> w;
+      for (uint32_t d = 0; d <= kp.cr_n; ++d) {
+        if (!crash.reach[d]) {       // never read: the entry of the next larger live count (d = 0 is reachable)
+          dir[d] = dir[d - 1u];
+          continue;
+        }
+        const uint32_t md = m - d;
+        dir[d].thr_base = thr.size();
+        dir[d].off_base = (uint32_t)off.size();
+        dir[d].pad = 0u;
+        const size_t base = thr.size();
+        for (uint32_t K = 0; K <= md; ++K) {
+          off.push_back((uint32_t)(thr.size() - base));
+          (void)tally_row(md, kp.q, K, thr, w);
+        }
+        off.push_back((uint32_t)(thr.size() - base));   // the md + 2nd offset: the last row's end
+      }
+      const size_t dir_bytes = sizeof(benor::CrashDir) * dir.size();
+      const size_t off_bytes = (sizeof(uint32_t) * off.size() + 7u) & ~size_t(7);
+      const size_t list_bytes = (sizeof(uint32_t) * crash.list.size() + 7u) & ~size_t(7);
+      e = hipMalloc(&pl->d_tally, dir_bytes + off_bytes + list_bytes + sizeof(uint64_t) * std::max<size_t>(thr.size(), 1u));
+      if (e == hipSuccess) e = hipMemcpy(pl->d_tally, dir.data(), dir_bytes, hipMemcpyHostToDevice);
+      if (e == hipSuccess)
+        e = hipMemcpy(pl->d_tally + dir_bytes, off.data(), sizeof(uint32_t) * off.size(), hipMemcpyHostToDevice);
+      if (e == hipSuccess && !crash.list.empty())
+        e = hipMemcpy(pl->d_tally + dir_bytes + off_bytes, crash.list.data(), sizeof(uint32_t) * crash.list.size(),
+                      hipMemcpyHostToDevice);
+      if (e == hipSuccess && !thr.empty())
+        e = hipMemcpy(pl->d_tally + dir_bytes + off_bytes + list_bytes, thr.data(), sizeof(uint64_t) * thr.size(),
+                      hipMemcpyHostToDevice);
+      if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "crash tally table upload"); }
+      kp.cr_dir = reinterpret_cast<const benor::CrashDir *>(pl->d_tally);
+      kp.tally_off = reinterpret_cast<const uint32_t *>(pl->d_tally + dir_bytes);
+      kp.cr_list = crash.list.empty() ? nullptr : reinterpret_cast<const uint32_t *>(pl->d_tally + dir_bytes + off_bytes);
+      kp.tally_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + dir_bytes + off_bytes + list_bytes);
     }
   }
   *out = pl;
@@ -747,7 +848,7 @@ uint64_t bo_plan_popc_words_per_node_round(const bo_plan *pl) {
   if (!pl) return 0;
   uint64_t counts = 4ull;
   if (pl->kp.mode != BO_MODE_RANDOM_DELIVERY && pl->kp.mode != BO_MODE_RANDOM_TALLY &&
-      pl->kp.mode != BO_MODE_RANDOM_TALLY3)
+      pl->kp.mode != BO_MODE_RANDOM_TALLY3 && pl->kp.mode != BO_MODE_CRASH_TALLY)
     counts = ((pl->kp.m - pl->kp.init_q) & 1u) ? 2ull : 3ull;
   return counts * ((pl->kp.m + 31ull) / 32ull);
 }

@@ -1,0 +1,417 @@
+// benor_tally_crash.hip -- count-level random delivery with crashes during the
+// run (BO_MODE_CRASH_TALLY with a non-empty schedule).
+//
+// The model is benor_tally3.hip's with the live set no longer constant: a node
+// may crash at a step boundary (step 2(r - 1) = the R-phase of round r, step
+// 2(r - 1) + 1 = its P-phase).  At step s the senders and the receivers are the
+// alive set A_s, m_s = |A_s| >= q, the class sizes are counted over A_s, and a
+// receiver's (c0, c1) is benor_tally3.hip's draw3 with m = m_s: one count from
+// row K_A of the HG(m_s, ., q) table, the smallest class walked from stream 6.
+// So the plan holds one table per reachable live count, found through a small
+// directory indexed by the number of crashes so far (CrashDir), and m_s, the
+// table choice and every class size are wave-uniform.
+//
+// One wave = one trial, lane l of receiver group j = compact index 64 j + l over
+// the initially-live nodes, fixed for the run: a crashed node is a hole in its
+// group, never compacted, and a group may become empty.  Per-wave LDS state:
+// ballot planes of W words -- AL (alive), X0 / X1 (x = 0, x = 1; neither: "?"),
+// P0 / P1 (the round's proposals) -- and the sticky decided bits, bit j of a
+// lane's register for group j.  A bit of a crashed node is never written again,
+// so it holds the node's state as of its crash.  That state is only reported by
+// a per-node-state launch; in a batch launch X0 is dead once round 1 has counted
+// its classes (after a P-phase every alive x is binary), so P0 takes its words
+// and a wave holds four planes, which at N = 4096 keeps three workgroups on a
+// CU as benor_tally3.hip has; a state launch adds X0 and a decided plane of its
+// own (crash_state_bytes).  The schedule is a list of (step << 12 | compact
+// index), step clamped to 2^20 - 1 (no run reaches step 2 BO_MAX_K): the plan's
+// for an explicit schedule, drawn per trial by Floyd's algorithm from Philox
+// stream 7 for a random one.  No floating point runs on the device.
+#include "benor_device.h"
+
+namespace benor {
+
+namespace {
+
+__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint64_t uni64(uint64_t v) { return (uint64_t)uni((uint32_t)(v >> 32)) << 32 | uni((uint32_t)v); }
+
+constexpr uint32_t kStepClamp = 0xFFFFFu;          // schedule entries: step in 20 bits, compact index in 12
+constexpr uint32_t kSchedWords = 256u;             // stream-7 words drawn per pass (64 lanes, one block each)
+
+// The table of the step's live count.
+struct Table {
+  uint32_t m;                                      // m_s
+  const uint32_t *off;                             // [m_s + 2] row offsets
+  const unsigned long long *thr;
+};
+
+// The wave-uniform part of a phase's draw (benor_tally3.hip Phase3).
+struct PhaseC {
+  uint32_t sel;      // 0: S = "?", A = 1, T = 0;  1: S = 0, A = 1, T = "?";  2: S = 1, A = 0, T = "?"
+  uint32_t KA, KS;   // class sizes
+  uint32_t lo;       // max(0, q - (m_s - KA)): row KA's least count
+  uint32_t n, steps; // row KA staged in LDS: its width, and ceil(log2(n + 1))
+};
+
+__device__ __forceinline__ PhaseC phase_setup(uint64_t *__restrict__ row, const KParams &p, const Table &tb, uint32_t K0,
+                                              uint32_t K1, uint32_t Kq, uint32_t lane) {
+  PhaseC ph;
+  if (Kq <= K0 && Kq <= K1) ph.sel = 0u, ph.KS = Kq, ph.KA = K1;
+  else if (K0 <= K1) ph.sel = 1u, ph.KS = K0, ph.KA = K1;
+  else ph.sel = 2u, ph.KS = K1, ph.KA = K0;
+  const uint32_t m = tb.m, q = p.q, K = ph.KA;
+  ph.lo = K + q > m ? K + q - m : 0u;
+  ph.n = 0u, ph.steps = 0u;
+  if (K != 0u && K != m && m != q) {               // else the row is a point
+    __builtin_amdgcn_wave_barrier();               // the previous phase's searches are done with the region
+    const uint32_t o = uni(tb.off[K]);
+    uint32_t n = uni(tb.off[K + 1u]) - o;
+    if (n > p.tally_cap) n = p.tally_cap;          // the region's size (no row of any table exceeds it)
+    const unsigned long long *src = tb.thr + o;
+    for (uint32_t i = lane; i < n; i += 64u) row[i] = src[i];
+    __builtin_amdgcn_wave_barrier();               // a wave's LDS operations retire in order
+    ph.n = n;
+    ph.steps = 32u - (uint32_t)__builtin_clz(n | 1u);
+  }
+  return ph;
+}
+
+// #{ j < n : T[j] <= u }: `steps` wave-uniform steps (benor_tally.hip row_count).
+__device__ __forceinline__ uint32_t row_count(const uint64_t *__restrict__ row, uint32_t n, uint32_t steps,
+                                              uint64_t u) {
+  uint32_t pos = 0;
+  for (uint32_t st = 1u << (steps - 1u); st != 0u; st >>= 1) {
+    const uint32_t i = pos + st - 1u;
+    const uint64_t t = row[i < n ? i : n - 1u];
+    if (i < n && t <= u) pos += st;
+  }
+  return pos;
+}
+
+// Receiver c's counts (c0, c1) of the phase among m senders: benor_tally3.hip's draw3.
+__device__ __forceinline__ void draw3(const uint64_t *__restrict__ row, const PhaseC &ph, uint32_t m, uint32_t q,
+                                      uint32_t k0, uint32_t k1, uint32_t tlo, uint32_t thi, uint32_t c, uint32_t r,
+                                      uint32_t phase, uint64_t u, uint32_t &c0, uint32_t &c1) {
+  uint32_t cA = ph.lo;
+  if (ph.n != 0u) cA += row_count(row, ph.n, ph.steps, u);
+  uint32_t cS = 0u;
+  if (ph.KS != 0u) {
+    if (m == q) {
+      cS = ph.KS;                                  // every alive sender is in the inbox
+    } else {
+      const uint32_t slots = q - cA;               // inbox slots left to the senders outside A
+      const uint32_t dtop = m - ph.KA;             // ... of which there are this many (>= slots, >= KS)
+      const uint32_t c3 = (r - 1u) | (phase << 16) | (kStreamWalk << 24);
+      uint32_t i = 0;
+      const auto word = [&](uint32_t w) {
+        if (i < ph.KS) {
+          const uint32_t d = dtop - i;             // member i's denominator, >= 1
+          const uint64_t mm = (uint64_t)w * d;     // multiply-shift: the draw is the high word ...
+          const uint32_t l = (uint32_t)mm;
+          bool ok = true;
+          if (l < d) ok = l >= (0u - d) % d;       // ... unless the low word falls in the biased remainder
+          if (ok) {
+            if ((uint32_t)(mm >> 32) < slots - cS) ++cS;
+            ++i;
+          }
+        }
+      };
+      for (uint32_t blk = 0; __any(i < ph.KS); ++blk) {
+        const uint4 b = philox4x32_10(k0, k1, make_uint4(tlo, thi, c | (blk << 12), c3));
+        word(b.x), word(b.y), word(b.z), word(b.w);
+      }
+    }
+  }
+  const uint32_t cT = q - cA - cS;
+  c1 = ph.sel == 2u ? cS : cA;
+  c0 = ph.sel == 0u ? cT : (ph.sel == 1u ? cS : cA);
+}
+
+// The trial's random schedule: Floyd's algorithm over the compact indices, from
+// the word stream of Philox stream 7, blocks {trial_lo, trial_hi, b, 7 << 24},
+// b = 0, 1, ..  For j = m0 - n .. m0 - 1: t uniform below j + 1, the node is t
+// unless already chosen, then j; its step uniform below the window.  The wave
+// draws 64 blocks at a time into WB, lane 0 consumes the words in order (a
+// rejected word draws the next one for the same denominator); `chosen` is a
+// zeroed plane of W words.
+__device__ __forceinline__ void draw_schedule(uint32_t *__restrict__ SC, uint32_t *__restrict__ WB,
+                                              uint64_t *__restrict__ chosen, const KParams &p, uint32_t k0, uint32_t k1,
+                                              uint32_t tlo, uint32_t thi, uint32_t lane) {
+  const uint32_t m0 = p.m, window = p.crash_window;
+  uint32_t j = m0 - p.cr_n, i = 0u, have = 0u, node = 0u;   // lane 0's walk
+  for (uint32_t base = 0u;; base += 64u) {
+    const uint4 b = philox4x32_10(k0, k1, make_uint4(tlo, thi, base + lane, kStreamSchedule << 24));
+    __builtin_amdgcn_wave_barrier();               // the previous pass's words are consumed
+    reinterpret_cast<uint4 *>(WB)[lane] = b;
+    __builtin_amdgcn_wave_barrier();
+    if (lane == 0u) {
+      for (uint32_t w = 0u; w < kSchedWords && j < m0; ++w) {
+        const uint32_t d = have ? window : j + 1u;
+        const uint64_t mm = (uint64_t)WB[w] * d;
+        const uint32_t l = (uint32_t)mm;
+        if (l < d && l < (0u - d) % d) continue;   // the biased remainder: the next word, same denominator
+        uint32_t v = (uint32_t)(mm >> 32);
+        if (!have) {
+          if ((chosen[v >> 6] >> (v & 63u)) & 1ull) v = j;
+          chosen[v >> 6] |= 1ull << (v & 63u);
+          node = v;
+          have = 1u;
+        } else {
+          SC[i++] = (v < kStepClamp ? v : kStepClamp) << 12 | node;
+          have = 0u;
+          ++j;
+        }
+      }
+    }
+    if (uni(j) >= m0) break;
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+__global__ void __launch_bounds__(256) benor_tally_crash_kernel(KParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wv = threadIdx.x >> 6;
+  const uint32_t m0 = p.m, F = p.F, W = p.W, q = p.q, ncr = p.cr_n;
+  const uint32_t WP = (W + 1u) & ~1u;
+
+  uint32_t *lhist = reinterpret_cast<uint32_t *>(smem);
+  const bool states = p.node_out != nullptr;       // a state launch: X0 and DEC planes of their own
+  const uint32_t capE = (p.tally_cap + 1u) & ~1u;
+  uint64_t *AL = reinterpret_cast<uint64_t *>(smem + p.hist_bytes + wv * p.wave_bytes);   // [W] alive
+  uint64_t *X1 = AL + WP;                                                                 // [W] x = 1
+  uint64_t *P1 = X1 + WP, *P0 = P1 + WP;                                                  // [W] proposals 1, 0
+  uint64_t *X0 = states ? P0 + WP : P0;                                                   // [W] x = 0 (round 1)
+  uint64_t *DEC = X0 + WP;                                                                // [W] decided (state launch)
+  uint64_t *row = AL + (states ? 6u : 4u) * WP;                                           // [tally_cap] thresholds
+  // [256] stream-7 words: in the row region when it is large enough (no row is staged while a schedule is drawn)
+  uint32_t *WB = reinterpret_cast<uint32_t *>(2u * capE >= kSchedWords ? row : row + capE);
+  uint32_t *SC = reinterpret_cast<uint32_t *>(row + capE) +
+                 (p.cr_random && 2u * capE < kSchedWords ? kSchedWords : 0u);             // [ncr] the schedule
+
+  for (uint32_t i = threadIdx.x; i < p.hist_len; i += blockDim.x) lhist[i] = 0u;
+  __syncthreads();
+
+  if (!p.cr_random)                                // an explicit schedule is the plan's, the same for every trial
+    for (uint32_t i = lane; i < ncr; i += 64u) SC[i] = p.cr_list[i];
+
+  const uint32_t k0 = (uint32_t)p.seed, k1 = (uint32_t)(p.seed >> 32);
+  const uint64_t waves_total = (uint64_t)gridDim.x * kWavesPerBlock;
+
+  for (uint64_t t = (uint64_t)blockIdx.x * kWavesPerBlock + wv; t < p.trial_count; t += waves_total) {
+    const uint64_t trial = p.trial_begin + t;
+    const uint32_t tlo = uni((uint32_t)trial), thi = uni((uint32_t)(trial >> 32));
+    __builtin_amdgcn_wave_barrier();               // the previous trial's state reads are done
+    if (lane < W) {
+      AL[lane] = group_mask(lane, m0);
+      P1[lane] = 0ull;                             // the schedule draw's chosen set
+    }
+    if (p.init_mode == BO_INIT_RANDOM) {           // /start (node.ts:167-188): stream 1, as every batch mode
+      const uint32_t nph = (W + 1u) >> 1;
+      if (lane < nph) {
+        uint4 r;
+        if (m0 <= 32u) r = make_uint4(init_word_small(k0, k1, trial), 0u, 0u, 0u);   // shared block (m <= 32)
+        else r = philox4x32_10(k0, k1, make_uint4(tlo, thi, lane, kStreamInit << 24));
+        const uint32_t w0 = 2u * lane, w1 = w0 + 1u;
+        const uint64_t g0 = group_mask(w0, m0), a0 = ((uint64_t)r.y << 32 | r.x) & g0;
+        X1[w0] = a0, X0[w0] = g0 & ~a0;
+        if (w1 < W) {
+          const uint64_t g1 = group_mask(w1, m0), a1 = ((uint64_t)r.w << 32 | r.z) & g1;
+          X1[w1] = a1, X0[w1] = g1 & ~a1;
+        }
+      }
+    } else {
+      for (uint32_t w = lane; w < W; w += 64u) {
+        const uint4 rc = p.init_plane[w];
+        X0[w] = (uint64_t)rc.y << 32 | rc.x;
+        X1[w] = (uint64_t)rc.w << 32 | rc.z;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (p.cr_random) draw_schedule(SC, WB, P1, p, k0, k1, tlo, thi, lane);
+
+    // The crashes of step s, then the step's live count and its table.
+    Table tb;
+    const auto step_begin = [&](uint32_t s) {
+      __builtin_amdgcn_wave_barrier();             // the previous step's plane writes are done
+      for (uint32_t i = lane; i < ncr; i += 64u) {
+        const uint32_t e = SC[i];
+        if ((e >> 12) == s) {
+          const uint32_t c = e & 0xFFFu;
+          atomicAnd(reinterpret_cast<unsigned long long *>(&AL[c >> 6]), ~(1ull << (c & 63u)));
+        }
+      }
+      __builtin_amdgcn_wave_barrier();
+      uint32_t ms = 0;
+      for (uint32_t j = 0; j < W; ++j) ms += (uint32_t)__builtin_popcountll(AL[j]);
+      ms = uni(ms);
+      const CrashDir de = p.cr_dir[m0 - ms];       // m0 - ms <= ncr crashes so far
+      tb.m = ms;
+      tb.off = p.tally_off + uni(de.off_base);
+      tb.thr = p.tally_thr + uni64(de.thr_base);
+      return ms;
+    };
+
+    uint64_t dec = 0ull;                           // bit j: node 64 j + lane has decided (sticky)
+    uint32_t R = 0;
+    bool all_dec = false, none = false;
+    for (uint32_t r = 1; r <= p.k_max; ++r) {
+      // ---- R-phase ("proposal phase", node.ts:46-82), step 2 (r - 1)
+      uint32_t ms = step_begin(2u * (r - 1u));
+      if (ms == 0u) { none = true; break; }
+      uint32_t K0 = 0, K1 = 0;
+      for (uint32_t j = 0; j < W; ++j) {
+        const uint64_t al = AL[j];
+        if (r == 1u) K0 += (uint32_t)__builtin_popcountll(X0[j] & al);
+        K1 += (uint32_t)__builtin_popcountll(X1[j] & al);
+      }
+      K1 = uni(K1);
+      K0 = r == 1u ? uni(K0) : ms - K1;            // after a P-phase every alive x is binary
+      PhaseC ph = phase_setup(row, p, tb, K0, K1, ms - K0 - K1, lane);
+      for (uint32_t j = 0; j < W; ++j) {
+        const uint64_t al = uni64(AL[j]);
+        uint64_t p0 = 0ull, p1 = 0ull;
+        if (al) {                                  // an emptied group draws nothing
+          const uint32_t c = j * 64u + lane;
+          // the round's block of receiver c: u_R = out[1] << 32 | out[0], u_P = out[3] << 32 | out[2]
+          const uint4 b = philox4x32_10(k0, k1, make_uint4(tlo, thi, c, (r - 1u) | (kStreamTally << 24)));
+          uint32_t c0, c1;
+          draw3(row, ph, ms, q, k0, k1, tlo, thi, c, r, 0u, (uint64_t)b.y << 32 | b.x, c0, c1);
+          p0 = ballot(c0 > c1) & al;
+          p1 = ballot(c1 > c0) & al;
+        }
+        if (lane == 0) P0[j] = p0, P1[j] = p1;
+      }
+      // ---- P-phase ("voting phase", node.ts:83-158), step 2 (r - 1) + 1: a node that
+      // proposed and crashes here does not vote
+      ms = step_begin(2u * (r - 1u) + 1u);
+      if (ms == 0u) { none = true; break; }
+      K0 = 0, K1 = 0;
+      for (uint32_t j = 0; j < W; ++j) {
+        const uint64_t al = AL[j];
+        K0 += (uint32_t)__builtin_popcountll(P0[j] & al);
+        K1 += (uint32_t)__builtin_popcountll(P1[j] & al);
+      }
+      K0 = uni(K0), K1 = uni(K1);
+      ph = phase_setup(row, p, tb, K0, K1, ms - K0 - K1, lane);
+      bool undecided = false;
+      for (uint32_t j = 0; j < W; ++j) {
+        const uint64_t al = uni64(AL[j]);
+        if (!al) continue;
+        const uint32_t c = j * 64u + lane;
+        const uint4 b = philox4x32_10(k0, k1, make_uint4(tlo, thi, c, (r - 1u) | (kStreamTally << 24)));
+        uint32_t c0, c1;
+        draw3(row, ph, ms, q, k0, k1, tlo, thi, c, r, 1u, (uint64_t)b.w << 32 | b.z, c0, c1);
+        const bool d0l = c0 > F, d1l = !d0l && c1 > F;
+        const uint64_t d0 = ballot(d0l) & al;
+        const uint64_t d1 = ballot(d1l) & al;
+        const uint64_t rest = al & ~(d0 | d1);
+        uint64_t x1 = d1;
+        if (rest) {
+          x1 |= ballot(c1 > c0) & rest;
+          const uint64_t tie = ballot(c1 == c0) & rest;              // an empty tally included
+          if (tie) x1 |= coin_ballot(k0, k1, tlo, thi, j, r, tie);
+        }
+        const bool mine = (al >> lane) & 1ull;     // this lane's node is alive
+        if (mine && (d0l || d1l)) dec |= 1ull << j;                  // sticky
+        if (lane == 0) {                           // the bits of crashed nodes stay as of their crash
+          X1[j] = (X1[j] & ~al) | x1;
+          if (states) X0[j] = (X0[j] & ~al) | (al & ~x1);
+        }
+        undecided = undecided || (mine && !((dec >> j) & 1ull));
+      }
+      R = r;
+      all_dec = !__any(undecided);                 // over the alive nodes
+      if (all_dec) break;
+    }
+    __builtin_amdgcn_wave_barrier();
+    uint32_t K = 0, ms = 0;                        // the nodes alive at the end, and those with x = 1
+    for (uint32_t j = 0; j < W; ++j) {
+      const uint64_t al = AL[j];
+      ms += (uint32_t)__builtin_popcountll(al);
+      K += (uint32_t)__builtin_popcountll(X1[j] & al);
+    }
+    K = uni(K), ms = uni(ms);
+    const uint32_t v = none ? 2u : ((K != 0u && K != ms) ? 2u : (K != 0u ? 1u : 0u));
+    if (none) all_dec = false;                     // nobody left: bin[2], rounds 0
+    if (lane == 0) {
+      atomicAdd(&lhist[all_dec ? (R * 3u + v) : v], 1u);
+      if (all_dec && v == 2u) atomicAdd(&lhist[p.hist_len - 1u], 1u);
+      if (p.rounds_out) *p.rounds_out = all_dec ? R : 0u;
+    }
+    if (states) {
+      for (uint32_t j = 0; j < W; ++j) {
+        const uint64_t d = ballot((dec >> j) & 1ull);
+        if (lane == 0) DEC[j] = d;
+      }
+      __builtin_amdgcn_wave_barrier();
+      for (uint32_t c = lane; c < m0; c += 64u) {
+        const uint32_t j = c >> 6;
+        if (!((AL[j] >> lane) & 1ull)) continue;
+        bo_node_state ns;
+        ns.killed = 0;
+        ns.x = (int8_t)((X1[j] >> lane) & 1ull);
+        ns.decided = (int8_t)((DEC[j] >> lane) & 1ull);
+        ns.pad = 0;
+        ns.k = (int32_t)R + 1;
+        p.node_out[p.live_ids[c]] = ns;
+      }
+      for (uint32_t i = lane; i < ncr; i += 64u) {   // crashed: x and decided as of the crash, k its round
+        const uint32_t e = SC[i], c = e & 0xFFFu, j = c >> 6, b = c & 63u;
+        if ((AL[j] >> b) & 1ull) continue;           // its step was never reached
+        bo_node_state ns;
+        ns.killed = 1;
+        ns.x = (int8_t)(((X1[j] >> b) & 1ull) ? 1 : (((X0[j] >> b) & 1ull) ? 0 : 2));
+        ns.decided = (int8_t)((DEC[j] >> b) & 1ull);
+        ns.pad = 0;
+        ns.k = (int32_t)(e >> 13) + 1;
+        p.node_out[p.live_ids[c]] = ns;
+      }
+    }
+  }
+
+  __syncthreads();
+  flush_hist(lhist, p);
+}
+
+}  // namespace
+
+// A batch launch's per-wave LDS: four planes, the row region, the schedule's
+// stream-7 words where the row region is too small for them, the schedule.
+uint32_t crash_wave_bytes(uint32_t W, uint32_t cap, uint32_t ncr, bool random) {
+  const uint32_t WP = (W + 1u) & ~1u, capE = (cap + 1u) & ~1u;
+  return (4u * WP + capE) * 8u + (random && 2u * capE < kSchedWords ? kSchedWords * 4u : 0u) + ((ncr + 3u) & ~3u) * 4u;
+}
+
+// ... and what a per-node-state launch adds to it: the X0 and DEC planes.
+uint32_t crash_state_bytes(uint32_t W) { return 2u * ((W + 1u) & ~1u) * 8u; }
+
+// Workgroups of the kernel that one CU holds at once (registers and LDS; 0 = unknown).
+int crash_blocks_per_cu(const KParams &p) {
+  int n = 0;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, benor_tally_crash_kernel, 64 * kWavesPerBlock,
+                                                                    p.lds_bytes);
+  return e == hipSuccess ? n : 0;
+}
+
+hipError_t launch_tally_crash(const KParams &plan, int grid, hipStream_t s) {
+  KParams p = plan;
+  if (p.node_out) {                                // a state launch (one trial): two more planes per wave
+    p.wave_bytes += crash_state_bytes(p.W);
+    p.lds_bytes += kWavesPerBlock * crash_state_bytes(p.W);
+  }
+  // (an explicit schedule whose steps all lie beyond 2 k_max leaves an empty list)
+  if (!p.tally_off || !p.tally_thr || !p.cr_dir || p.W > kMaxW || p.cr_n > p.m ||
+      (!p.cr_random && p.cr_n != 0u && !p.cr_list) || (p.cr_random && (p.cr_n == 0u || p.crash_window == 0u)) ||
+      plan.wave_bytes < crash_wave_bytes(p.W, p.tally_cap, p.cr_n, p.cr_random != 0u))
+    return hipErrorInvalidValue;
+  if (p.lds_bytes > 64u * 1024u) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&benor_tally_crash_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(benor_tally_crash_kernel, dim3(grid), dim3(64 * kWavesPerBlock), p.lds_bytes, s, p);
+  return hipGetLastError();
+}
+
+}  // namespace benor

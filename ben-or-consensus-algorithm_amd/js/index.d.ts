@@ -86,11 +86,16 @@ export interface TrialsConfig {
   /** 0 lockstep (default), 1 random delivery (f <= F), 2 event level (N <= 4096),
    *  3 random delivery at the level of counts (MODE_RANDOM_TALLY: f <= F, N - F odd, no "?" initial value),
    *  4 the same for any quorum and with "?" initial values (MODE_RANDOM_TALLY3: f <= F; three vote classes,
-   *    ties and coins; equal to mode 3 bit for bit wherever mode 3 is defined) */
-  mode?: 0 | 1 | 2 | 3 | 4;
-  /** event mode: deliveries after which node i is stopped (null = never) */
+   *    ties and coins; equal to mode 3 bit for bit wherever mode 3 is defined),
+   *  5 mode 4 with crashes during the run (MODE_CRASH_TALLY: clean crashes at step boundaries, step 2(r-1) =
+   *    the R-phase of round r, step 2(r-1)+1 = its P-phase; f + scheduled crashes <= F; an empty schedule is
+   *    mode 4 bit for bit) */
+  mode?: 0 | 1 | 2 | 3 | 4 | 5;
+  /** event mode: deliveries after which node i is stopped (null = never);
+   *  MODE_CRASH_TALLY: the step at which node i crashes (null = never) */
   crashAt?: (number | null)[];
-  /** event mode, random schedule: stop crashCount live nodes at uniform delivery counts in [0, crashWindow) */
+  /** event mode, random schedule: stop crashCount live nodes at uniform delivery counts in [0, crashWindow);
+   *  MODE_CRASH_TALLY: crashCount initially-live nodes crash at uniform steps in [0, crashWindow), per trial */
   crashCount?: number;
   crashWindow?: number;
 }
@@ -101,6 +106,7 @@ export declare const MODE_RANDOM_DELIVERY: 1;
 export declare const MODE_EVENT: 2;
 export declare const MODE_RANDOM_TALLY: 3;
 export declare const MODE_RANDOM_TALLY3: 4;
+export declare const MODE_CRASH_TALLY: 5;
 
 /** Outcome histogram, (kMax + 1) * 3 + 1 bins (include/benor.h). */
 export declare function runTrials(cfg: TrialsConfig): Promise<BigUint64Array>;

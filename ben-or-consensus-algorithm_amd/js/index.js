@@ -16,7 +16,8 @@ const BASE_NODE_PORT = 3000;          // src/config.ts:1
 const DEFAULT_K_MAX = 64;             // round cap: the reference runs until /stop
 // runTrials cfg.mode (include/benor.h BO_MODE_*)
 const MODE_LOCKSTEP = 0, MODE_RANDOM_DELIVERY = 1, MODE_EVENT = 2, MODE_RANDOM_TALLY = 3,
-  MODE_RANDOM_TALLY3 = 4;
+  MODE_RANDOM_TALLY3 = 4,
+  MODE_CRASH_TALLY = 5;
 
 let current = null;                   // { handle, N }
 
@@ -211,5 +212,5 @@ module.exports = {
   BASE_NODE_PORT, DEFAULT_K_MAX, launchNetwork, startConsensus, stopConsensus, stopNode,
   getNodeState, getNodesState, getNodeStatus, reachedFinality, runTrials, delay,
   waitConsensus, liveStopEvents, getNodesStateAt,
-  MODE_LOCKSTEP, MODE_RANDOM_DELIVERY, MODE_EVENT, MODE_RANDOM_TALLY, MODE_RANDOM_TALLY3,
+  MODE_LOCKSTEP, MODE_RANDOM_DELIVERY, MODE_EVENT, MODE_RANDOM_TALLY, MODE_RANDOM_TALLY3, MODE_CRASH_TALLY,
 };

@@ -85,13 +85,41 @@ enum {
  * quorum, no live "?") runs RANDOM_TALLY's kernel and gives its results bit for
  * bit; at f == F the mode equals LOCKSTEP bit for bit, "?" and even m included.
  * Validation is RANDOM_DELIVERY's (at most F faulty). */
+/* CRASH_TALLY is RANDOM_TALLY3 with crashes during the run: up
+ * to F - f of the m0 = N - f initially-live nodes crash cleanly at step
+ * boundaries, step 2(r-1) = the R-phase of round r, step 2(r-1)+1 = its P-phase.
+ * A node that crashes at step s completed step s-1; from step s on it neither
+ * sends nor receives (one that proposed and crashes at the P-step does not
+ * vote).  At every step the senders and receivers are the alive set, m_s >= N-F
+ * of them, the class sizes are counted over it, and a receiver's counts are
+ * RANDOM_TALLY3's draw with m replaced by m_s -- one threshold table per
+ * reachable live count.  The schedule is explicit (crash_at[i] = node i's step)
+ * or random (crash_count distinct initially-live nodes at uniform steps below
+ * crash_window, drawn per trial from Philox stream 7).  The run halts after the
+ * round in which every alive node has decided; the outcome is over the nodes
+ * alive at the end.  Validation is RANDOM_DELIVERY's, and f + (scheduled
+ * crashes) <= F (BO_ERR_FAULTY_COUNT), so a quorum of live senders always exists;
+ * crash_count > 0 needs crash_window >= 1.  The tables of all reachable live
+ * counts together may hold at most BO_CRASH_TABLE_MAX_BYTES of thresholds
+ * (BO_ERR_UNSUPPORTED beyond).  An empty schedule is RANDOM_TALLY3's plan: its
+ * kernel choice and its results bit for bit; a schedule no crash of which is
+ * reached gives RANDOM_TALLY3's results bit for bit on this mode's kernel.  Not
+ * modelled: partial broadcasts (a crasher's last message reaching only some
+ * receivers).  Batch API only (no network API, no `sweep`). */
 enum {
   BO_MODE_LOCKSTEP = 0,
   BO_MODE_RANDOM_DELIVERY = 1,
   BO_MODE_EVENT = 2,
   BO_MODE_RANDOM_TALLY = 3,
-  BO_MODE_RANDOM_TALLY3 = 4
+  BO_MODE_RANDOM_TALLY3 = 4,
+  BO_MODE_CRASH_TALLY = 5
 };
+
+/* BO_MODE_CRASH_TALLY: most bytes of 64-bit thresholds that the tables of a
+ * plan's reachable live counts may hold together (512 MiB).  The table of
+ * (m', q = N-F) holds the sum over K = 0..m' of min(K, q) - max(0, q - (m' - K))
+ * thresholds. */
+#define BO_CRASH_TABLE_MAX_BYTES (512ull << 20)
 
 enum { BO_INIT_RANDOM = 0, BO_INIT_FIXED = 1 };
 
@@ -225,12 +253,17 @@ typedef struct bo_trials_cfg {
     uint32_t mode;            /* BO_MODE_* */
     uint32_t reserved;
     uint64_t seed;            /* Philox4x32-10 key */
-    const uint8_t *faulty;    /* host [N]; exactly F set (LOCKSTEP, EVENT), at most F (RANDOM_DELIVERY, RANDOM_TALLY, RANDOM_TALLY3) */
+    const uint8_t *faulty;    /* host [N]; exactly F set (LOCKSTEP, EVENT), at most F (RANDOM_DELIVERY, RANDOM_TALLY, RANDOM_TALLY3, CRASH_TALLY) */
     const int8_t *init;       /* host [N]; used when init_mode == BO_INIT_FIXED */
-    /* EVENT mode only: GET /stop schedule.  crash_at[i] = number of deliveries
+    /* EVENT mode: GET /stop schedule.  crash_at[i] = number of deliveries
      * after which node i is stopped (UINT32_MAX = never), or, when crash_at is
      * NULL, crash_count distinct live nodes stopped at uniform delivery counts
-     * in [0, crash_window), drawn per trial from Philox. */
+     * in [0, crash_window), drawn per trial from Philox.
+     * CRASH_TALLY mode: the crash schedule in steps.  crash_at[i] = the step
+     * at which node i crashes (UINT32_MAX = never; entries of faulty nodes are
+     * ignored), or, when crash_at is NULL, crash_count distinct initially-live
+     * nodes at uniform steps in [0, crash_window), drawn per trial.
+     * The other modes ignore the three fields. */
     const uint32_t *crash_at; /* host [N] or NULL */
     uint32_t crash_count;
     uint32_t crash_window;
@@ -274,8 +307,10 @@ int bo_plan_check(bo_plan *plan);
  * initial values) binary votes.  LOCKSTEP / EVENT: the R-phase counts c1
  * (c0 = M - c1); the P-phase counts c1 when M is odd (no tie, so no "?"
  * proposal: c0 = m - c1) and c0, c1 otherwise -- 2 or 3 x ceil(m/32).
- * RANDOM_DELIVERY: both values in both phases, 4 x ceil(m/32).  RANDOM_TALLY
- * and RANDOM_TALLY3 answer RANDOM_DELIVERY's unit, the work they stand in for. */
+ * RANDOM_DELIVERY: both values in both phases, 4 x ceil(m/32).  RANDOM_TALLY,
+ * RANDOM_TALLY3 and CRASH_TALLY answer RANDOM_DELIVERY's unit, the work they
+ * stand in for (CRASH_TALLY with m = the initially-live count, as
+ * bo_plan_live_nodes reports it). */
 uint64_t bo_plan_popc_words_per_node_round(const bo_plan *plan);
 uint32_t bo_plan_live_nodes(const bo_plan *plan);
 
@@ -299,9 +334,13 @@ enum {
                               by binary search in a table row staged in LDS; batch and per-node-state
                               launches alike, no overflow or deferral state; also what
                               BO_MODE_RANDOM_TALLY3 runs inside that mode's scope */
-  BO_KERNEL_TALLY3 = 10     /* BO_MODE_RANDOM_TALLY3 outside RANDOM_TALLY's scope (even quorum or a live "?"
+  BO_KERNEL_TALLY3 = 10,    /* BO_MODE_RANDOM_TALLY3 outside RANDOM_TALLY's scope (even quorum or a live "?"
                               initial value): one wave per trial, three vote classes -- one count from the
                               table, the smallest class walked by selection sampling, coins on ties */
+  BO_KERNEL_TALLY_CRASH = 11 /* BO_MODE_CRASH_TALLY with a non-empty schedule: TALLY3's draw over the alive
+                              set of each step -- alive, x, proposal and decided ballot planes per trial,
+                              one table per reachable live count (an empty schedule runs RANDOM_TALLY3's
+                              kernel choice) */
 };
 
 /* The kernel family bo_plan_launch runs for this plan.  (The per-node-state

@@ -14,11 +14,19 @@ median and minimum ms per launch and the variant's median / first variant's.
 
 A shape may carry a fourth field f < F (the first f nodes crashed, the rest of
 F the random-delivery slack: BO_MODE_RANDOM_DELIVERY).  A variant may also name
-the delivery mode with the pseudo-variable `mode` (lockstep, random, tally or tally3),
+the delivery mode with the pseudo-variable `mode` (lockstep, random, tally, tally3 or crash),
 so the mask-level and the count-level random-delivery modes are timed
 alternately on one plan each:
 
     python tools/ab_inproc.py --variants "mask=mode:random;tally=mode:tally" --shapes "1024,341,100000,0"
+
+`mode:crash` (BO_MODE_CRASH_TALLY) takes its schedule from further pseudo-variables:
+`crash_count` and `crash_window` (a random schedule per trial) or `crash_at`
+(explicit, node@step+node@step; a step of 64 or more is never reached at this
+tool's k_max of 32, which times the mode's kernel on mode 4's results):
+
+    python tools/ab_inproc.py --variants "t3=mode:tally3;idle=mode:crash,crash_at:0@64;c16=mode:crash,crash_count:16,crash_window:4" \
+        --shapes "1024,340,100000,0"
 
 Every line also reports
 the live node-rounds per second its launches represent (bench.py node_rounds),
@@ -60,6 +68,8 @@ def main():
         v = [int(x) for x in sp.split(",")]
         shapes.append((v[0], v[1], v[2], v[3] if len(v) > 3 else v[1]))
     modes = {name: env.pop("mode", None) for name, env in variants}   # `mode` is no environment variable
+    scheds = {name: {k: env.pop(k) for k in ("crash_count", "crash_window", "crash_at") if k in env}
+              for name, env in variants}                              # ... nor is the crash schedule
     knobs = sorted({k for _, env in variants for k in env})
 
     import benor
@@ -67,10 +77,24 @@ def main():
     if unknown:
         ap.error(f"not a registered libbenor knob (benor.KNOBS): {unknown}")
     mode_ids = {"lockstep": benor.BO_MODE_LOCKSTEP, "random": benor.BO_MODE_RANDOM_DELIVERY,
-                "tally": benor.BO_MODE_RANDOM_TALLY, "tally3": benor.BO_MODE_RANDOM_TALLY3}
+                "tally": benor.BO_MODE_RANDOM_TALLY, "tally3": benor.BO_MODE_RANDOM_TALLY3,
+                "crash": benor.BO_MODE_CRASH_TALLY}
     bad = sorted({v for v in modes.values() if v is not None and v not in mode_ids})
     if bad:
         ap.error(f"mode must be one of {sorted(mode_ids)}: {bad}")
+    if any(sc and modes[name] != "crash" for name, sc in scheds.items()):
+        ap.error("crash_count / crash_window / crash_at need mode:crash")
+
+    def schedule(name, N):
+        sc, kw = scheds[name], {}
+        if "crash_at" in sc:
+            kw["crash_at"] = [None] * N
+            for part in sc["crash_at"].split("+"):
+                node, _, step = part.partition("@")
+                kw["crash_at"][int(node)] = int(step)
+        else:
+            kw = {k: int(v) for k, v in sc.items()}
+        return kw
 
     import numpy as np
     import torch
@@ -92,9 +116,11 @@ def main():
         plans = {}                                    # one plan per delivery mode the variants name
         for name, _ in variants:
             mode = mode_ids[modes[name]] if modes[name] else dflt
-            if mode not in plans:
-                plans[mode] = benor.TrialsPlan(N, F, [i < f for i in range(N)], seed=0x5EED + N, k_max=32, mode=mode)
-            plans[name] = plans[mode]
+            key = (mode, tuple(sorted(scheds[name].items())))
+            if key not in plans:
+                plans[key] = benor.TrialsPlan(N, F, [i < f for i in range(N)], seed=0x5EED + N, k_max=32, mode=mode,
+                                              **schedule(name, N))
+            plans[name] = plans[key]
         h = torch.zeros(plans[variants[0][0]].hist_len, dtype=torch.int64, device="cuda")
         for name, env in variants:                    # warm-up per variant (allocations, code load)
             set_env(env)
@@ -123,7 +149,10 @@ def main():
         for name, _ in variants:
             t = times[(N, F, T, f, name)]
             print(json.dumps({"N": N, "F": F, "f": f, "trials": T, "variant": name, "median_ms": statistics.median(t),
-                              "min_ms": min(t), "rounds": len(t), "median_vs_first": statistics.median(t) / base,
+                              "min_ms": min(t), "max_ms": max(t), "rounds": len(t),
+                              "median_vs_first": statistics.median(t) / base,
+                              "trials_per_s": T / (statistics.median(t) * 1e-3),
+                              "us_per_trial": statistics.median(t) * 1e3 / T, **scheds[name],
                               "node_rounds_per_s": statistics.median(work[(N, F, T, f, name)]),
                               "kernel_version": benor.kernel_version()}), flush=True)
 
