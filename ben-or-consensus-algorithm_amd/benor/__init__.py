@@ -41,7 +41,10 @@ BO_MODE_RANDOM_TALLY = 3       # random delivery at the level of counts (odd quo
 BO_MODE_RANDOM_TALLY3 = 4      # ... any quorum, "?" allowed: three vote classes, ties and coins (a superset of mode 3)
 BO_MODE_CRASH_TALLY = 5        # mode 4 with crashes during the run: crash_at[i] = node i's step (2(r-1): R-phase of
                                # round r, +1: its P-phase), or crash_count nodes at random steps below crash_window
-CRASH_TABLE_MAX_BYTES = 512 << 20   # mode 5: thresholds of the tables of all reachable live counts, at most
+BO_MODE_CRASH_PARTIAL = 6      # mode 5 with partial broadcasts: a crasher's last message reaches the receivers whose
+                               # compact index is below its cut (crash_cut = 0..m0 for every crasher, or CUT_RANDOM)
+CRASH_TABLE_MAX_BYTES = 512 << 20   # modes 5 and 6: thresholds of the tables of all reachable live counts, at most
+CUT_RANDOM = 0xFFFFFFFF        # crash_cut: a cut per trial and crasher, uniform on 0..m0 (Philox stream 8)
 NEVER = 0xFFFFFFFF             # crash_at entry: never stopped / never crashes
 BO_INIT_RANDOM = 0
 BO_INIT_FIXED = 1
@@ -56,12 +59,15 @@ BO_KERNEL_MFMA_SMALL = 8
 BO_KERNEL_TALLY = 9
 BO_KERNEL_TALLY3 = 10
 BO_KERNEL_TALLY_CRASH = 11
+BO_KERNEL_TALLY_PARTIAL = 12
 KERNEL_NAMES = {BO_KERNEL_NONE: "none", BO_KERNEL_BLOCKED: "blocked popcount", BO_KERNEL_W: "W popcount",
                 BO_KERNEL_RANDOM: "random delivery", BO_KERNEL_EVENT: "event level", BO_KERNEL_LANE: "lane",
                 BO_KERNEL_MFMA: "matrix core (e2m1 MFMA)", BO_KERNEL_MFMA_SMALL: "packed matrix core (e2m1 MFMA, m <= 32)",
                 BO_KERNEL_TALLY: "count-level random delivery (hypergeometric tallies)",
                 BO_KERNEL_TALLY3: "count-level random delivery, three vote classes (hypergeometric tally + walk)",
-                BO_KERNEL_TALLY_CRASH: "count-level random delivery with crashes during the run (a table per live count)"}
+                BO_KERNEL_TALLY_CRASH: "count-level random delivery with crashes during the run (a table per live count)",
+                BO_KERNEL_TALLY_PARTIAL: "count-level random delivery with crashes cutting a broadcast short "
+                                         "(a segment of receivers per cut)"}
 BO_MAX_N = 4096
 BO_MAX_K = 1024
 
@@ -106,7 +112,7 @@ class NodeStateC(ctypes.Structure):
 
 class TrialsCfgC(ctypes.Structure):
     _fields_ = [("N", ctypes.c_uint32), ("F", ctypes.c_uint32), ("k_max", ctypes.c_uint32),
-                ("init_mode", ctypes.c_uint32), ("mode", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("init_mode", ctypes.c_uint32), ("mode", ctypes.c_uint32), ("crash_cut", ctypes.c_uint32),
                 ("seed", ctypes.c_uint64), ("faulty", ctypes.POINTER(ctypes.c_uint8)),
                 ("init", ctypes.POINTER(ctypes.c_int8)), ("crash_at", ctypes.POINTER(ctypes.c_uint32)),
                 ("crash_count", ctypes.c_uint32), ("crash_window", ctypes.c_uint32)]
@@ -441,7 +447,7 @@ def hist_len(k_max: int) -> int:
 
 
 def _trials_cfg(N, F, faulty=None, *, seed=0, k_max=DEFAULT_K_MAX, initial_values=None, mode=BO_MODE_LOCKSTEP,
-                crash_at=None, crash_count=0, crash_window=0):
+                crash_at=None, crash_count=0, crash_window=0, crash_cut=0):
     """bo_trials_cfg for a shape, and the ctypes arrays it points into."""
     if faulty is None:                       # start.ts:7-18 placement: the first F nodes
         faulty = [i < F for i in range(N)]
@@ -453,7 +459,7 @@ def _trials_cfg(N, F, faulty=None, *, seed=0, k_max=DEFAULT_K_MAX, initial_value
         init = (ctypes.c_int8 * max(1, N))(*[_VAL[v] for v in initial_values])
         init_mode = BO_INIT_FIXED
     crash = _crash_array(N, crash_at)
-    cfg = TrialsCfgC(N, F, k_max, init_mode, mode, 0, seed,
+    cfg = TrialsCfgC(N, F, k_max, init_mode, mode, crash_cut, seed,
                      ctypes.cast(fl, ctypes.POINTER(ctypes.c_uint8)),
                      ctypes.cast(init, ctypes.POINTER(ctypes.c_int8)),
                      ctypes.cast(crash, ctypes.POINTER(ctypes.c_uint32)) if crash else None,
@@ -476,12 +482,12 @@ class TrialsPlan:
     def __init__(self, N: int, F: int, faulty: Sequence[bool] | None = None, *, seed: int = 0,
                  k_max: int = DEFAULT_K_MAX, initial_values: Sequence | None = None,
                  mode: int = BO_MODE_LOCKSTEP, crash_at: Sequence | None = None, crash_count: int = 0,
-                 crash_window: int = 0):
+                 crash_window: int = 0, crash_cut: int = 0):
         self.N, self.F, self.k_max, self.seed = N, F, k_max, seed
         self.mode = mode
         self._cfg, self._keep = _trials_cfg(N, F, faulty, seed=seed, k_max=k_max, initial_values=initial_values,
                                             mode=mode, crash_at=crash_at, crash_count=crash_count,
-                                            crash_window=crash_window)
+                                            crash_window=crash_window, crash_cut=crash_cut)
         h = ctypes.c_void_p()
         _check(lib().bo_plan_create(ctypes.byref(self._cfg), ctypes.byref(h)))
         self._h = h
@@ -531,7 +537,7 @@ class TrialsPlan:
 def run_trial_states(N: int, F: int, faulty: Sequence[bool], *, seed: int = 0, trial: int = 0,
                      k_max: int = DEFAULT_K_MAX, initial_values: Sequence | None = None,
                      mode: int = BO_MODE_LOCKSTEP, crash_at: Sequence | None = None, crash_count: int = 0,
-                     crash_window: int = 0):
+                     crash_window: int = 0, crash_cut: int = 0):
     """Per-node final states of one trial: (rounds, [NodeState dict] * N)."""
     fl = (ctypes.c_uint8 * max(1, N))(*[1 if v else 0 for v in faulty])
     if initial_values is None:
@@ -541,7 +547,7 @@ def run_trial_states(N: int, F: int, faulty: Sequence[bool], *, seed: int = 0, t
         init = (ctypes.c_int8 * max(1, N))(*[_VAL[v] for v in initial_values])
         init_mode = BO_INIT_FIXED
     ca = _crash_array(N, crash_at)
-    cfg = TrialsCfgC(N, F, k_max, init_mode, mode, 0, seed,
+    cfg = TrialsCfgC(N, F, k_max, init_mode, mode, crash_cut, seed,
                      ctypes.cast(fl, ctypes.POINTER(ctypes.c_uint8)),
                      ctypes.cast(init, ctypes.POINTER(ctypes.c_int8)),
                      ctypes.cast(ca, ctypes.POINTER(ctypes.c_uint32)) if ca else None, crash_count, crash_window)

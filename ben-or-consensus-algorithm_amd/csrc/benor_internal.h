@@ -19,6 +19,7 @@ constexpr uint32_t kStreamCrash = 4u;
 constexpr uint32_t kStreamTally = 5u;
 constexpr uint32_t kStreamWalk = 6u;       // BO_MODE_RANDOM_TALLY3: the smallest class's selection-sampling draws
 constexpr uint32_t kStreamSchedule = 7u;   // BO_MODE_CRASH_TALLY: a trial's random crash schedule (Floyd's algorithm)
+constexpr uint32_t kStreamCut = 8u;        // BO_MODE_CRASH_PARTIAL: a crasher's random cut, keyed by its compact index
 
 constexpr int kWavesPerBlock = 4;          // 256-thread workgroups, one trial per wave
 
@@ -62,13 +63,15 @@ struct KParams {
                             // 0: blocked lockstep, 2: random delivery, 4: event level,
                             // 9: count-level random delivery (benor_tally.hip),
                             // 10: three-valued count-level random delivery (benor_tally3.hip),
-                            // 11: the same with crashes during the run (benor_tally_crash.hip)
+                            // 11: the same with crashes during the run (benor_tally_crash.hip),
+                            // 12: ... whose last broadcast reaches a prefix of the receivers (benor_tally_partial.hip)
   uint32_t base_variant;    // variant 7: the popcount kernel (1 W, 0 blocked) that serves the state
   uint32_t base_G;          //   launches and the deferred trials, and its G
   uint32_t mode;            // BO_MODE_LOCKSTEP / BO_MODE_RANDOM_DELIVERY / BO_MODE_EVENT / BO_MODE_RANDOM_TALLY /
                             // BO_MODE_RANDOM_TALLY3 / BO_MODE_CRASH_TALLY (a BO_MODE_RANDOM_TALLY3 plan inside
                             // mode 3's scope holds BO_MODE_RANDOM_TALLY here: it is that mode's plan; a
-                            // BO_MODE_CRASH_TALLY plan with an empty schedule is BO_MODE_RANDOM_TALLY3's)
+                            // BO_MODE_CRASH_TALLY or BO_MODE_CRASH_PARTIAL plan with an empty schedule is
+                            // BO_MODE_RANDOM_TALLY3's)
   uint32_t q;               // quorum N - F (messages each receiver tallies per phase)
   uint32_t k_max;
   uint32_t init_mode;       // BO_INIT_RANDOM / BO_INIT_FIXED
@@ -155,6 +158,10 @@ struct KParams {
   const CrashDir *cr_dir;
   const uint32_t *cr_list;
   uint32_t cr_n, cr_random;
+  // ... with partial broadcasts (variant 12): every crasher's cut, the number of initially-live
+  // receivers (compact indices below it) its last message reaches; UINT32_MAX: drawn per trial and
+  // crasher from Philox stream 8.  The tables are those of every pool size m_s + |H_c|
+  uint32_t cr_cut;
 };
 
 constexpr uint32_t kTimelineWords = 12;
@@ -209,8 +216,15 @@ hipError_t launch_tally3(const KParams &p, int grid_blocks, hipStream_t stream);
 // list and, for a random schedule whose row region is too small for them, a pass
 // of stream-7 words); a per-node-state launch adds two planes by itself.
 uint32_t crash_wave_bytes(uint32_t W, uint32_t cap, uint32_t ncr, bool random);
+uint32_t crash_state_bytes(uint32_t W);
 int crash_blocks_per_cu(const KParams &p);        // resident workgroups per CU (registers, LDS); 0 = unknown
 hipError_t launch_tally_crash(const KParams &p, int grid_blocks, hipStream_t stream);
+
+// ... and with partial broadcasts (benor_tally_partial.hip): the same layout plus the
+// step's crasher list (cut and vote class per entry).
+uint32_t partial_wave_bytes(uint32_t W, uint32_t cap, uint32_t ncr, bool random);
+int partial_blocks_per_cu(const KParams &p);      // resident workgroups per CU (registers, LDS); 0 = unknown
+hipError_t launch_tally_partial(const KParams &p, int grid_blocks, hipStream_t stream);
 
 // Event level for kMaxEventN < N <= BO_MAX_N (benor_event_big.hip): one wave per trial.
 // The wave-per-trial event kernel keeps its message pool in LDS when it is at

@@ -524,10 +524,12 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   if (cfg->N < 1 || cfg->N > BO_MAX_N) return fail(BO_ERR_UNSUPPORTED, "N must be in [1, 4096]");
   if (cfg->k_max < 1 || cfg->k_max > BO_MAX_K) return fail(BO_ERR_INVALID_ARGUMENT, "k_max must be in [1, 1024]");
   if (cfg->mode != BO_MODE_LOCKSTEP && cfg->mode != BO_MODE_RANDOM_DELIVERY && cfg->mode != BO_MODE_EVENT &&
-      cfg->mode != BO_MODE_RANDOM_TALLY && cfg->mode != BO_MODE_RANDOM_TALLY3 && cfg->mode != BO_MODE_CRASH_TALLY)
+      cfg->mode != BO_MODE_RANDOM_TALLY && cfg->mode != BO_MODE_RANDOM_TALLY3 && cfg->mode != BO_MODE_CRASH_TALLY &&
+      cfg->mode != BO_MODE_CRASH_PARTIAL)
     return fail(BO_ERR_UNSUPPORTED, "unknown delivery mode");
+  const bool crash_mode = cfg->mode == BO_MODE_CRASH_TALLY || cfg->mode == BO_MODE_CRASH_PARTIAL;
   const bool random_mode = cfg->mode == BO_MODE_RANDOM_DELIVERY || cfg->mode == BO_MODE_RANDOM_TALLY ||
-                           cfg->mode == BO_MODE_RANDOM_TALLY3 || cfg->mode == BO_MODE_CRASH_TALLY;
+                           cfg->mode == BO_MODE_RANDOM_TALLY3 || crash_mode;
   if (cfg->init_mode != BO_INIT_RANDOM && cfg->init_mode != BO_INIT_FIXED)
     return fail(BO_ERR_INVALID_ARGUMENT, "unknown init_mode");
   if (!cfg->faulty) return fail(BO_ERR_INVALID_ARGUMENT, "faulty is NULL");
@@ -544,11 +546,11 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   for (uint32_t i = 0; i < cfg->N; ++i)
     if (!cfg->faulty[i]) live.push_back(i);
   const uint32_t m = (uint32_t)live.size();
-  // Crashes during the run (BO_MODE_CRASH_TALLY): with the initially faulty nodes at
-  // most F, so every step has a quorum of live senders.
+  // Crashes during the run (BO_MODE_CRASH_TALLY, BO_MODE_CRASH_PARTIAL): with the initially
+  // faulty nodes at most F, so every step has a quorum of live senders.
   uint64_t n_crash = 0;
   bool crash_random = false;
-  if (cfg->mode == BO_MODE_CRASH_TALLY) {
+  if (crash_mode) {
     if (cfg->crash_at) {
       for (uint32_t c = 0; c < m; ++c) n_crash += cfg->crash_at[live[c]] != 0xFFFFFFFFu ? 1u : 0u;
     } else if (cfg->crash_count > 0) {
@@ -557,7 +559,12 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
       crash_random = true;
     }
     if ((uint64_t)f + n_crash > cfg->F)
-      return fail(BO_ERR_FAULTY_COUNT, "BO_MODE_CRASH_TALLY needs at most F nodes faulty or scheduled to crash");
+      return fail(BO_ERR_FAULTY_COUNT, cfg->mode == BO_MODE_CRASH_TALLY
+                                           ? "BO_MODE_CRASH_TALLY needs at most F nodes faulty or scheduled to crash"
+                                           : "BO_MODE_CRASH_PARTIAL needs at most F nodes faulty or scheduled to crash");
+    // Partial broadcasts: a cut counts initially-live receivers
+    if (cfg->mode == BO_MODE_CRASH_PARTIAL && cfg->crash_cut != BO_CUT_RANDOM && cfg->crash_cut > m)
+      return fail(BO_ERR_INVALID_ARGUMENT, "crash_cut must be at most the initially-live count N - f, or BO_CUT_RANDOM");
   }
   kp = benor::KParams{};
   kp.N = cfg->N;
@@ -603,13 +610,14 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   // The three-valued mode is a superset: inside that scope it is that mode's plan
   // (its kernel, its results bit for bit); outside, benor_tally3.hip.
   // A BO_MODE_CRASH_TALLY plan with an empty schedule is the three-valued mode's plan.
-  if (cfg->mode == BO_MODE_CRASH_TALLY && n_crash == 0) kp.mode = BO_MODE_RANDOM_TALLY3;
+  if (crash_mode && n_crash == 0) kp.mode = BO_MODE_RANDOM_TALLY3;
   if (kp.mode == BO_MODE_RANDOM_TALLY3 && (kp.q & 1u) && !kp.init_q) kp.mode = BO_MODE_RANDOM_TALLY;
-  if (kp.mode == BO_MODE_CRASH_TALLY) {
+  if (kp.mode == BO_MODE_CRASH_TALLY || kp.mode == BO_MODE_CRASH_PARTIAL) {
     CrashPlan local;
     CrashPlan &cp = crash ? *crash : local;
     cp.list.clear();
     kp.cr_random = crash_random ? 1u : 0u;
+    kp.cr_cut = kp.mode == BO_MODE_CRASH_PARTIAL ? cfg->crash_cut : 0u;
     if (crash_random) {
       kp.cr_n = (uint32_t)n_crash;
       cp.reach.assign(kp.cr_n + 1u, 1);            // every m0 - j, j = 0 .. crash_count
@@ -624,13 +632,21 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
       cp.reach[0] = 1;
       for (uint32_t i = 0; i < kp.cr_n; ++i)
         if (i + 1u == kp.cr_n || (cp.list[i + 1u] >> 12) != (cp.list[i] >> 12)) cp.reach[i + 1u] = 1;
+      // Partial broadcasts: a receiver's pool is the alive set and the step's crashers that reach
+      // it.  A fixed cut gives all of them or none, live counts of the set above; random cuts
+      // any number of them, so every m0 - j
+      if (kp.cr_cut == BO_CUT_RANDOM) cp.reach.assign(kp.cr_n + 1u, 1);
     }
     uint64_t bytes = 0;
     for (uint32_t d = 0; d <= kp.cr_n; ++d)
       if (cp.reach[d]) bytes += 8ull * tally_table_len(m - d, kp.q);
     if (bytes > BO_CRASH_TABLE_MAX_BYTES)
-      return fail(BO_ERR_UNSUPPORTED, "BO_MODE_CRASH_TALLY: the threshold tables of the reachable live counts exceed "
-                                      "the 512 MiB limit (BO_CRASH_TABLE_MAX_BYTES): schedule fewer crashes");
+      return fail(BO_ERR_UNSUPPORTED,
+                  kp.mode == BO_MODE_CRASH_TALLY
+                      ? "BO_MODE_CRASH_TALLY: the threshold tables of the reachable live counts exceed "
+                        "the 512 MiB limit (BO_CRASH_TABLE_MAX_BYTES): schedule fewer crashes"
+                      : "BO_MODE_CRASH_PARTIAL: the threshold tables of the reachable pool sizes exceed "
+                        "the 512 MiB limit (BO_CRASH_TABLE_MAX_BYTES): schedule fewer crashes");
   }
   benor::plan_geometry(kp);   // after init_q: the kernel choice depends on the round-1 vote parity
   return BO_OK;
@@ -769,7 +785,8 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
       if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "tally table upload"); }
       kp.tally_off = reinterpret_cast<const uint32_t *>(pl->d_tally);
       kp.tally_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + off_bytes);
-    } else if (kp.variant == 11) {   // BO_MODE_CRASH_TALLY: one table per reachable live count, and their directory
+    } else if (kp.variant == 11 || kp.variant == 12) {
+      // BO_MODE_CRASH_TALLY, BO_MODE_CRASH_PARTIAL: one table per reachable live count (pool size), and their directory
       std::vector<benor::CrashDir> dir(kp.cr_n + 1u);
       std::vector<uint32_t> off;
       std::vector<uint64_t> thr;
@@ -848,7 +865,8 @@ uint64_t bo_plan_popc_words_per_node_round(const bo_plan *pl) {
   if (!pl) return 0;
   uint64_t counts = 4ull;
   if (pl->kp.mode != BO_MODE_RANDOM_DELIVERY && pl->kp.mode != BO_MODE_RANDOM_TALLY &&
-      pl->kp.mode != BO_MODE_RANDOM_TALLY3 && pl->kp.mode != BO_MODE_CRASH_TALLY)
+      pl->kp.mode != BO_MODE_RANDOM_TALLY3 && pl->kp.mode != BO_MODE_CRASH_TALLY &&
+      pl->kp.mode != BO_MODE_CRASH_PARTIAL)
     counts = ((pl->kp.m - pl->kp.init_q) & 1u) ? 2ull : 3ull;
   return counts * ((pl->kp.m + 31ull) / 32ull);
 }

@@ -89,15 +89,20 @@ export interface TrialsConfig {
    *    ties and coins; equal to mode 3 bit for bit wherever mode 3 is defined),
    *  5 mode 4 with crashes during the run (MODE_CRASH_TALLY: clean crashes at step boundaries, step 2(r-1) =
    *    the R-phase of round r, step 2(r-1)+1 = its P-phase; f + scheduled crashes <= F; an empty schedule is
-   *    mode 4 bit for bit) */
-  mode?: 0 | 1 | 2 | 3 | 4 | 5;
+   *    mode 4 bit for bit),
+   *  6 mode 5 with partial broadcasts (MODE_CRASH_PARTIAL: a crasher's last message reaches the initially-live
+   *    nodes whose index, in ascending node id, is below its cut; crashCut = 0 is mode 5 bit for bit) */
+  mode?: 0 | 1 | 2 | 3 | 4 | 5 | 6;
   /** event mode: deliveries after which node i is stopped (null = never);
-   *  MODE_CRASH_TALLY: the step at which node i crashes (null = never) */
+   *  MODE_CRASH_TALLY, MODE_CRASH_PARTIAL: the step at which node i crashes (null = never) */
   crashAt?: (number | null)[];
   /** event mode, random schedule: stop crashCount live nodes at uniform delivery counts in [0, crashWindow);
    *  MODE_CRASH_TALLY: crashCount initially-live nodes crash at uniform steps in [0, crashWindow), per trial */
   crashCount?: number;
   crashWindow?: number;
+  /** MODE_CRASH_PARTIAL: every crasher's cut, 0 .. the initially-live count, or CUT_RANDOM (uniform per trial
+   *  and crasher); default 0 */
+  crashCut?: number;
 }
 
 /** TrialsConfig.mode values (include/benor.h BO_MODE_*). */
@@ -107,6 +112,9 @@ export declare const MODE_EVENT: 2;
 export declare const MODE_RANDOM_TALLY: 3;
 export declare const MODE_RANDOM_TALLY3: 4;
 export declare const MODE_CRASH_TALLY: 5;
+export declare const MODE_CRASH_PARTIAL: 6;
+/** TrialsConfig.crashCut: a cut per trial and crasher (include/benor.h BO_CUT_RANDOM). */
+export declare const CUT_RANDOM: 4294967295;
 
 /** Outcome histogram, (kMax + 1) * 3 + 1 bins (include/benor.h). */
 export declare function runTrials(cfg: TrialsConfig): Promise<BigUint64Array>;

@@ -103,19 +103,47 @@ enum {
  * counts together may hold at most BO_CRASH_TABLE_MAX_BYTES of thresholds
  * (BO_ERR_UNSUPPORTED beyond).  An empty schedule is RANDOM_TALLY3's plan: its
  * kernel choice and its results bit for bit; a schedule no crash of which is
- * reached gives RANDOM_TALLY3's results bit for bit on this mode's kernel.  Not
- * modelled: partial broadcasts (a crasher's last message reaching only some
- * receivers).  Batch API only (no network API, no `sweep`). */
+ * reached gives RANDOM_TALLY3's results bit for bit on this mode's kernel.  A
+ * crash here is clean: a crasher's last message reaches everybody or nobody;
+ * CRASH_PARTIAL models the broadcast cut short.  Batch API only (no network API,
+ * no `sweep`). */
+/* CRASH_PARTIAL is CRASH_TALLY with partial broadcasts.  The
+ * reference broadcasts in ascending node id (node.ts:72-80, :149-157, :173-185),
+ * so a node that crashes during its step-s broadcast reaches a prefix of the
+ * receivers.  Every scheduled crasher p has a cut, cut_p in [0, m0], counted over
+ * the initially-live nodes in ascending node id (the compact index; faulty nodes
+ * never receive and are not counted): crash_cut <= m0 gives every crasher that
+ * cut, crash_cut == BO_CUT_RANDOM draws each crasher's cut per trial, uniform on
+ * 0..m0, from Philox stream 8 keyed by the crasher's compact index; any other
+ * value is BO_ERR_INVALID_ARGUMENT.  A node that crashes at step s does not
+ * receive at step s; its step-s message -- its x at an R-step, the proposal it
+ * formed at step s-1 at a P-step -- reaches exactly the receivers with compact
+ * index c < cut_p.  Receiver c of the alive set A_s draws its N-F messages from
+ * the pool A_s + H_c, H_c = { p crashing at s : c < cut_p }: CRASH_TALLY's draw
+ * with m = m_s + |H_c| and the class sizes counted over that pool.  Everything
+ * else -- schedule, validation, halting, outcome, per-node states, the table
+ * limit -- is CRASH_TALLY's.  An empty schedule is RANDOM_TALLY3's plan;
+ * crash_cut = 0 gives CRASH_TALLY's results bit for bit on this mode's kernel; an
+ * explicit schedule of even steps with crash_cut = m0 gives CRASH_TALLY's results
+ * for the schedule with every step one later.  The tables are those of every pool
+ * size: with a fixed cut CRASH_TALLY's set, with random cuts every m0 - j, j = 0
+ * .. the number of scheduled crashes below step 2 k_max.  Not modelled: subsets
+ * that are no prefix, a cut per node given explicitly.  Batch API only (no
+ * network API, no `sweep`). */
 enum {
   BO_MODE_LOCKSTEP = 0,
   BO_MODE_RANDOM_DELIVERY = 1,
   BO_MODE_EVENT = 2,
   BO_MODE_RANDOM_TALLY = 3,
   BO_MODE_RANDOM_TALLY3 = 4,
-  BO_MODE_CRASH_TALLY = 5
+  BO_MODE_CRASH_TALLY = 5,
+  BO_MODE_CRASH_PARTIAL = 6
 };
 
-/* BO_MODE_CRASH_TALLY: most bytes of 64-bit thresholds that the tables of a
+/* BO_MODE_CRASH_PARTIAL, crash_cut: a cut per trial and crasher, uniform on 0..m0. */
+#define BO_CUT_RANDOM 0xFFFFFFFFu
+
+/* BO_MODE_CRASH_TALLY, BO_MODE_CRASH_PARTIAL: most bytes of 64-bit thresholds that the tables of a
  * plan's reachable live counts may hold together (512 MiB).  The table of
  * (m', q = N-F) holds the sum over K = 0..m' of min(K, q) - max(0, q - (m' - K))
  * thresholds. */
@@ -251,15 +279,15 @@ typedef struct bo_trials_cfg {
     uint32_t k_max;           /* round cap, 1..BO_MAX_K */
     uint32_t init_mode;       /* BO_INIT_RANDOM: iid Bernoulli(1/2) per live node; BO_INIT_FIXED */
     uint32_t mode;            /* BO_MODE_* */
-    uint32_t reserved;
+    uint32_t crash_cut;       /* CRASH_PARTIAL: every crasher's cut, 0..m0, or BO_CUT_RANDOM; the other modes ignore it */
     uint64_t seed;            /* Philox4x32-10 key */
-    const uint8_t *faulty;    /* host [N]; exactly F set (LOCKSTEP, EVENT), at most F (RANDOM_DELIVERY, RANDOM_TALLY, RANDOM_TALLY3, CRASH_TALLY) */
+    const uint8_t *faulty;    /* host [N]; exactly F set (LOCKSTEP, EVENT), at most F (RANDOM_DELIVERY, RANDOM_TALLY, RANDOM_TALLY3, CRASH_TALLY, CRASH_PARTIAL) */
     const int8_t *init;       /* host [N]; used when init_mode == BO_INIT_FIXED */
     /* EVENT mode: GET /stop schedule.  crash_at[i] = number of deliveries
      * after which node i is stopped (UINT32_MAX = never), or, when crash_at is
      * NULL, crash_count distinct live nodes stopped at uniform delivery counts
      * in [0, crash_window), drawn per trial from Philox.
-     * CRASH_TALLY mode: the crash schedule in steps.  crash_at[i] = the step
+     * CRASH_TALLY and CRASH_PARTIAL modes: the crash schedule in steps.  crash_at[i] = the step
      * at which node i crashes (UINT32_MAX = never; entries of faulty nodes are
      * ignored), or, when crash_at is NULL, crash_count distinct initially-live
      * nodes at uniform steps in [0, crash_window), drawn per trial.
@@ -308,8 +336,8 @@ int bo_plan_check(bo_plan *plan);
  * (c0 = M - c1); the P-phase counts c1 when M is odd (no tie, so no "?"
  * proposal: c0 = m - c1) and c0, c1 otherwise -- 2 or 3 x ceil(m/32).
  * RANDOM_DELIVERY: both values in both phases, 4 x ceil(m/32).  RANDOM_TALLY,
- * RANDOM_TALLY3 and CRASH_TALLY answer RANDOM_DELIVERY's unit, the work they
- * stand in for (CRASH_TALLY with m = the initially-live count, as
+ * RANDOM_TALLY3, CRASH_TALLY and CRASH_PARTIAL answer RANDOM_DELIVERY's unit, the
+ * work they stand in for (the last two with m = the initially-live count, as
  * bo_plan_live_nodes reports it). */
 uint64_t bo_plan_popc_words_per_node_round(const bo_plan *plan);
 uint32_t bo_plan_live_nodes(const bo_plan *plan);
@@ -337,10 +365,13 @@ enum {
   BO_KERNEL_TALLY3 = 10,    /* BO_MODE_RANDOM_TALLY3 outside RANDOM_TALLY's scope (even quorum or a live "?"
                               initial value): one wave per trial, three vote classes -- one count from the
                               table, the smallest class walked by selection sampling, coins on ties */
-  BO_KERNEL_TALLY_CRASH = 11 /* BO_MODE_CRASH_TALLY with a non-empty schedule: TALLY3's draw over the alive
+  BO_KERNEL_TALLY_CRASH = 11, /* BO_MODE_CRASH_TALLY with a non-empty schedule: TALLY3's draw over the alive
                               set of each step -- alive, x, proposal and decided ballot planes per trial,
                               one table per reachable live count (an empty schedule runs RANDOM_TALLY3's
                               kernel choice) */
+  BO_KERNEL_TALLY_PARTIAL = 12 /* BO_MODE_CRASH_PARTIAL with a non-empty schedule: TALLY_CRASH's step run once
+                              per segment of receivers that hear the same crashers (the cuts of the step's
+                              crashers are the boundaries), one table per pool size */
 };
 
 /* The kernel family bo_plan_launch runs for this plan.  (The per-node-state

@@ -14,7 +14,7 @@ median and minimum ms per launch and the variant's median / first variant's.
 
 A shape may carry a fourth field f < F (the first f nodes crashed, the rest of
 F the random-delivery slack: BO_MODE_RANDOM_DELIVERY).  A variant may also name
-the delivery mode with the pseudo-variable `mode` (lockstep, random, tally, tally3 or crash),
+the delivery mode with the pseudo-variable `mode` (lockstep, random, tally, tally3, crash or partial),
 so the mask-level and the count-level random-delivery modes are timed
 alternately on one plan each:
 
@@ -27,6 +27,13 @@ tool's k_max of 32, which times the mode's kernel on mode 4's results):
 
     python tools/ab_inproc.py --variants "t3=mode:tally3;idle=mode:crash,crash_at:0@64;c16=mode:crash,crash_count:16,crash_window:4" \
         --shapes "1024,340,100000,0"
+
+`mode:partial` (BO_MODE_CRASH_PARTIAL) takes the same schedule and `crash_cut`, a
+count of initially-live receivers or `random`; at `crash_cut:0` it gives mode:crash's
+results on its own kernel, so that pair times the kernel's overhead alone:
+
+    python tools/ab_inproc.py --rounds 7 --reps 5 --shapes "1024,340,100000,0" --variants \
+        "m5=mode:crash,crash_count:16,crash_window:4;cut0=mode:partial,crash_count:16,crash_window:4,crash_cut:0;rand=mode:partial,crash_count:16,crash_window:4,crash_cut:random"
 
 Every line also reports
 the live node-rounds per second its launches represent (bench.py node_rounds),
@@ -68,7 +75,7 @@ def main():
         v = [int(x) for x in sp.split(",")]
         shapes.append((v[0], v[1], v[2], v[3] if len(v) > 3 else v[1]))
     modes = {name: env.pop("mode", None) for name, env in variants}   # `mode` is no environment variable
-    scheds = {name: {k: env.pop(k) for k in ("crash_count", "crash_window", "crash_at") if k in env}
+    scheds = {name: {k: env.pop(k) for k in ("crash_count", "crash_window", "crash_at", "crash_cut") if k in env}
               for name, env in variants}                              # ... nor is the crash schedule
     knobs = sorted({k for _, env in variants for k in env})
 
@@ -78,15 +85,18 @@ def main():
         ap.error(f"not a registered libbenor knob (benor.KNOBS): {unknown}")
     mode_ids = {"lockstep": benor.BO_MODE_LOCKSTEP, "random": benor.BO_MODE_RANDOM_DELIVERY,
                 "tally": benor.BO_MODE_RANDOM_TALLY, "tally3": benor.BO_MODE_RANDOM_TALLY3,
-                "crash": benor.BO_MODE_CRASH_TALLY}
+                "crash": benor.BO_MODE_CRASH_TALLY, "partial": benor.BO_MODE_CRASH_PARTIAL}
     bad = sorted({v for v in modes.values() if v is not None and v not in mode_ids})
     if bad:
         ap.error(f"mode must be one of {sorted(mode_ids)}: {bad}")
-    if any(sc and modes[name] != "crash" for name, sc in scheds.items()):
-        ap.error("crash_count / crash_window / crash_at need mode:crash")
+    if any(sc and modes[name] not in ("crash", "partial") for name, sc in scheds.items()):
+        ap.error("crash_count / crash_window / crash_at need mode:crash or mode:partial")
+    if any("crash_cut" in sc and modes[name] != "partial" for name, sc in scheds.items()):
+        ap.error("crash_cut needs mode:partial")
 
     def schedule(name, N):
-        sc, kw = scheds[name], {}
+        sc, kw = dict(scheds[name]), {}
+        cut = sc.pop("crash_cut", None)
         if "crash_at" in sc:
             kw["crash_at"] = [None] * N
             for part in sc["crash_at"].split("+"):
@@ -94,6 +104,8 @@ def main():
                 kw["crash_at"][int(node)] = int(step)
         else:
             kw = {k: int(v) for k, v in sc.items()}
+        if cut is not None:
+            kw["crash_cut"] = benor.CUT_RANDOM if cut == "random" else int(cut)
         return kw
 
     import numpy as np
