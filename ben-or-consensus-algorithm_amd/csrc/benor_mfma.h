@@ -54,9 +54,37 @@
 //  * Padding: senders >= m are zero bits in the x words; receiver rows >= m in
 //    the last tile are masked out of the P-phase operand and start their
 //    P-phase accumulator at NaN, which the min / max reductions skip.
+//  * KIND 0, paired form (the default; benor_mfma_pair.h has the constants
+//    and tests/pair_fields_check.cpp their exhaustive host check): receiver
+//    tiles 2a and 2a + 1 share one accumulator.  Tile 2a's W products enter at
+//    A scale 2^0, tile 2a + 1's at 2^12 (P-phase: 2^11), and C = 2^23 +
+//    (2^k - thr)(1 + 2^S), so the result is the integer 2^23 + (2^k + c_a -
+//    thr) + 2^S (2^k + c_b - thr) < 2^24, exact in f32, whose mantissa bits k
+//    and k + S are "count >= thr" of the two receivers.  R-phase: k = 9, thr =
+//    (M1 >> 1) + 1, bits 9 / 21 = p1; two v_perm_b32 and a mask-merge turn four
+//    results (eight receivers) into one dword of the p1 plane, a pair's 16
+//    results into P-phase chunk a.  P-phase: k = 10, thr = m - F, bits 10 / 21
+//    = x1; the OR / AND fold runs over 16 results per pair.  Every one of the
+//    MT (W + KP) products is still executed; the packing and the fold handle
+//    two receivers per VALU operation: static VALU 1082 -> 779 at W = 11, 436
+//    -> 355 at W = 3, MFMA unchanged (484, 36).  PMC (profiles/r11-b_summary.md
+//    against r11-b0_summary.md, the one-tile form BENOR_MFMA_PAIR=0): non-MFMA
+//    VALU per trial 27.9 -> 18.5 at the headline and 8.49 -> 5.99 at configs[2],
+//    MFMA per trial 15.125 and 1.125 as before, matrix core busy 0.935 -> 0.947
+//    and 0.669 -> 0.766.  Time against the one-tile form in one process, median
+//    of 7 rounds (profiles/r11-b_mfma_pair_ab.jsonl): configs[2] N=256/F=85
+//    0.223 -> 0.198 ms at 10^7 trials (0.888) and 4.24 -> 3.81 ms at 2*10^8
+//    (0.899); N=130/F=33 0.853; N=512/F=169 0.966; N=1000/F=333 0.988;
+//    N=1023/F=0 0.961 -- each beyond the rounds' spread.  The headline
+//    N=1024/F=341: 0.991 with the two forms' ranges over the rounds overlapping
+//    in that run, 0.985 with disjoint ranges on another box
+//    (profiles/r11-a_mfma_pair_forms_ab.jsonl), and bench.py 22.95 / 22.97 ->
+//    22.61 / 22.63 ms per step against the parent commit, alternated on one
+//    box (profiles/r11-c_bench_parent_pair.jsonl): a gain of 1-1.5 %.
 #pragma once
 
 #include "benor_device.h"
+#include "benor_mfma_pair.h"
 
 namespace benor {
 
@@ -138,13 +166,24 @@ __device__ __forceinline__ mf_v4i expand_votes(uint32_t w) {
                 (int)((w >> 2) & 0x22222222u)};
 }
 
-template <int W, bool HALF, int KIND>
+// Paired form: four results (two receivers each, benor_mfma_pair.h) -> one
+// B-operand dword of the P-phase, eight e2m1 nibbles.
+__device__ __forceinline__ uint32_t pack_pair4(const mf_v16f &acc, int base) {
+  const uint32_t x = __builtin_amdgcn_perm(__float_as_uint(acc[base + 1]), __float_as_uint(acc[base + 0]), pairf::kSelX);
+  const uint32_t y = __builtin_amdgcn_perm(__float_as_uint(acc[base + 3]), __float_as_uint(acc[base + 2]), pairf::kSelY);
+  return (x & pairf::kMaskX) | (y & pairf::kMaskY);
+}
+
+// PAIR (KIND 0 only): two receiver tiles per accumulator instead of one.
+template <int W, bool HALF, int KIND, bool PAIR = false>
 __global__ void __launch_bounds__(256) benor_mfma_kernel(KParams p) {
+  static_assert(!PAIR || KIND == 0, "the paired form is KIND 0's");
   constexpr int MT = 2 * W - (HALF ? 1 : 0);   // 32-receiver tiles (HALF: the last chunk holds <= 32 senders)
   constexpr int KP = (MT + 1) / 2;             // P-phase K chunks: two tiles' results each
   constexpr int NB = (W + 1) / 2;              // Philox init blocks per trial (128 senders each)
   constexpr int NJ = (NB + 1) / 2;             // blocks per lane: half h draws blocks h, h + 2, ...
   constexpr bool SURE = KIND == 0;
+  constexpr bool PAIRED = PAIR;
   // (r05 measured the SURE W <= 4 proposal packing and P-phase fold through
   // v_cvt_scalef32_pk_fp4_f32 instead of v_perm sign bytes and the f32 sign
   // fold: 10 % fewer VALU, 8-12 % slower at configs[2] -- the conversion is
@@ -194,8 +233,13 @@ __global__ void __launch_bounds__(256) benor_mfma_kernel(KParams p) {
   //     (decide 1, node.ts:102-105);
   //   KIND 2 (F < m <= 2F): acc = S = 6 (c1 - c0); the receiver decides iff
   //     |c1 - c0| > 2F - m (c0 > F or c1 > F), for the value of the sign.
-  const float bias_r = SURE ? -((float)(M1 >> 1) + 0.5f) : -8.0f * (float)M1;
-  const float bias_p = SURE ? -((float)p.F + 0.5f) : (KIND == 2 ? 0.0f : 3.0f - 6.0f * (float)(m - 2u * p.F));
+  // KIND 0 paired: tiles 2a and 2a + 1 in the two bit fields of one
+  //   accumulator (benor_mfma_pair.h): bits 9 / 21 of the R-phase result are
+  //   p1 = (c1 > M1 >> 1), the packed plane is the p1 plane, and bits 10 / 21
+  //   of the P-phase result are "c1 >= m - F" = "not d0" = x1.
+  const float bias_r = PAIRED ? pairf::bias_r2(M1) : SURE ? -((float)(M1 >> 1) + 0.5f) : -8.0f * (float)M1;
+  const float bias_p = PAIRED ? pairf::bias_p2(m, p.F)
+                       : SURE ? -((float)p.F + 0.5f) : (KIND == 2 ? 0.0f : 3.0f - 6.0f * (float)(m - 2u * p.F));
   const float dec_thr = 6.0f * (float)(2u * p.F - m) + 3.0f;   // KIND 2: |acc| > dec_thr <=> decided
   mf_v16f cr, cp, cp_tail;
   // Receiver rows of the last tile that exist: nibble masks for its packed
@@ -214,6 +258,19 @@ __global__ void __launch_bounds__(256) benor_mfma_kernel(KParams p) {
     const uint32_t nib = !live ? 0u : SURE ? ((j & 4) ? 0x20u : 0x02u) << (8 * (j & 3)) : 0xFu << (4 * (j & 7));
     if (j < 8) tail0 |= nib;
     else tail1 |= nib;
+  }
+  // Paired form: the last pair's packed dword k holds results 4k .. 4k + 3 of
+  // its low tile (MT odd: the last tile; MT even: a full one) and of its high
+  // tile (MT even: the last tile; MT odd: none, its field carries no count).
+  uint32_t tailq[4] = {0u, 0u, 0u, 0u};
+  if constexpr (PAIRED) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const uint32_t row = (uint32_t)((j & 3) + 8 * (j >> 2)) + 4u * h;
+      const bool live = row < mrem;
+      const bool live_lo = (MT & 1) ? live : true, live_hi = (MT & 1) ? false : live;
+      tailq[j >> 2] |= (live_lo ? pairf::nib_lo(j & 3) : 0u) | (live_hi ? pairf::nib_hi(j & 3) : 0u);
+    }
   }
   // Fixed initial values: the same x1 words for every trial.
   uint32_t fixed_w[W];
@@ -281,8 +338,58 @@ __global__ void __launch_bounds__(256) benor_mfma_kernel(KParams p) {
     // ---- R-phase ("proposal phase", node.ts:46-82): every receiver tile
     // counts the x plane; the packed result is its proposal.
     uint32_t bp[MT][2];
+    mf_v4i pb[KP];
     uint32_t qz = 0u;                          // KIND > 0: a live receiver proposed "?"
-    if constexpr (SURE && W <= 4) {
+    if constexpr (PAIRED && W <= 4) {
+      // as the one-tile W <= 4 form below, with the pair as the unit (against
+      // the plain loop at W <= 4: -1.5 .. -3 %, profiles/r11-a_mfma_pair_forms_ab.jsonl)
+      __builtin_amdgcn_s_setprio(1);
+      mf_v16f racc[2];
+#pragma unroll
+      for (int a = 0; a <= KP; ++a) {
+        constexpr int VPM = (16 + 2 * W - 1) / (2 * W);
+        if (a < KP) {
+          asm volatile("" : "+v"(ones));
+          mf_v16f acc = mfma_count(ones, bx[0], cr);
+#pragma unroll
+          for (int c = 1; c < W; ++c) acc = mfma_count(ones, bx[c], acc);
+          if (2 * a + 1 < MT) {
+            asm volatile("" : "+v"(ones));
+#pragma unroll
+            for (int c = 0; c < W; ++c) acc = mfma_count<pairf::kShiftR>(ones, bx[c], acc);
+          }
+          racc[a & 1] = acc;
+        }
+        if (a > 0) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) pb[a - 1][k] = (int)pack_pair4(racc[(a - 1) & 1], 4 * k);
+        }
+        if (a < KP && a > 0) {
+#pragma unroll
+          for (int c = 0; c < (2 * a + 1 < MT ? 2 * W : W); ++c) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, VPM, 0);
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    } else if constexpr (PAIRED) {
+#pragma unroll
+      for (int a = 0; a < KP; ++a) {
+        asm volatile("" : "+v"(ones));
+        mf_v16f acc = mfma_count(ones, bx[0], cr);
+#pragma unroll
+        for (int c = 1; c < W; ++c) acc = mfma_count(ones, bx[c], acc);
+        if (2 * a + 1 < MT) {
+          asm volatile("" : "+v"(ones));
+#pragma unroll
+          for (int c = 0; c < W; ++c) acc = mfma_count<pairf::kShiftR>(ones, bx[c], acc);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) pb[a][k] = (int)pack_pair4(acc, 4 * k);
+        __builtin_amdgcn_sched_barrier(0);     // one pair's accumulator live at a time
+      }
+    } else if constexpr (SURE && W <= 4) {
       // Few products per tile (W): the sign packing of tile i - 1 is issued
       // among tile i's products, a few VALU per MFMA, so it runs in their
       // shadow (two accumulators live).  The wave raises its issue priority for
@@ -336,13 +443,18 @@ __global__ void __launch_bounds__(256) benor_mfma_kernel(KParams p) {
       }
       __builtin_amdgcn_sched_barrier(0);   // one tile's accumulator live at a time
     }
-    bp[MT - 1][0] &= tail0;
-    bp[MT - 1][1] &= tail1;
-    mf_v4i pb[KP];
+    if constexpr (PAIRED) {
+      // padded receiver rows, and the high field of a last tile that runs alone
 #pragma unroll
-    for (int c = 0; c < KP; ++c)
-      pb[c] = mf_v4i{(int)bp[2 * c][0], (int)bp[2 * c][1], 2 * c + 1 < MT ? (int)bp[2 * c + 1][0] : 0,
-                     2 * c + 1 < MT ? (int)bp[2 * c + 1][1] : 0};
+      for (int k = 0; k < 4; ++k) pb[KP - 1][k] &= (int)tailq[k];
+    } else {
+      bp[MT - 1][0] &= tail0;
+      bp[MT - 1][1] &= tail1;
+#pragma unroll
+      for (int c = 0; c < KP; ++c)
+        pb[c] = mf_v4i{(int)bp[2 * c][0], (int)bp[2 * c][1], 2 * c + 1 < MT ? (int)bp[2 * c + 1][0] : 0,
+                       2 * c + 1 < MT ? (int)bp[2 * c + 1][1] : 0};
+    }
 
     // ---- P-phase ("voting phase", node.ts:83-158): every receiver tile
     // counts the proposals; the sign of its result is its decision.  The
@@ -350,8 +462,66 @@ __global__ void __launch_bounds__(256) benor_mfma_kernel(KParams p) {
     // some decided 1 (and for KIND 2 whether every receiver decided).
     uint32_t any1, any0, halt = (uint32_t)ballot(valid);
     if constexpr (SURE) {
-      uint32_t s_or = 0u, s_and = ~0u;        // sign bit = "not d0" = x1
-      if constexpr (W <= 4) {
+      uint32_t s_or = 0u, s_and = ~0u;        // sign bit (paired: bits 10 / 21) = "not d0" = x1
+      // Paired: a last tile that runs alone leaves its high field at the bias,
+      // decide-1 bit clear: neutral in the OR; the AND takes it as set.
+      [[maybe_unused]] auto fold_pair = [&](const mf_v16f &acc, bool lone) {
+        uint32_t a_and = ~0u;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          const uint32_t u = __float_as_uint(acc[j]);
+          s_or |= u;
+          if (lone) a_and &= u;
+          else s_and &= u;
+        }
+        if (lone) s_and &= a_and | pairf::kIndPHigh;
+      };
+      if constexpr (PAIRED && W <= 4) {
+        mf_v16f pacc[2];
+#pragma unroll
+        for (int a = 0; a <= KP; ++a) {
+          constexpr int VPM = (32 + 2 * KP - 1) / (2 * KP);
+          if (a < KP) {
+            asm volatile("" : "+v"(ones));
+            mf_v16f acc = mfma_count(ones, pb[0], cp);
+#pragma unroll
+            for (int c = 1; c < KP; ++c) acc = mfma_count(ones, pb[c], acc);
+            if (2 * a + 1 < MT) {
+              asm volatile("" : "+v"(ones));
+#pragma unroll
+              for (int c = 0; c < KP; ++c) acc = mfma_count<pairf::kShiftP>(ones, pb[c], acc);
+            }
+            pacc[a & 1] = acc;
+          }
+          if (a > 0) fold_pair(pacc[(a - 1) & 1], 2 * (a - 1) + 1 >= MT);
+          if (a < KP && a > 0) {
+#pragma unroll
+            for (int c = 0; c < (2 * a + 1 < MT ? 2 * KP : KP); ++c) {
+              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+              __builtin_amdgcn_sched_group_barrier(0x002, VPM, 0);
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        __builtin_amdgcn_s_setprio(0);
+      } else if constexpr (PAIRED) {
+#pragma unroll
+        for (int a = 0; a < KP; ++a) {
+          asm volatile("" : "+v"(ones));
+          mf_v16f acc = mfma_count(ones, pb[0], cp);
+#pragma unroll
+          for (int c = 1; c < KP; ++c) acc = mfma_count(ones, pb[c], acc);
+          if (2 * a + 1 < MT) {
+            asm volatile("" : "+v"(ones));
+#pragma unroll
+            for (int c = 0; c < KP; ++c) acc = mfma_count<pairf::kShiftP>(ones, pb[c], acc);
+          }
+          // padded receiver rows need no mask, as in the one-tile form below
+          fold_pair(acc, 2 * a + 1 >= MT);
+          asm volatile("" : "+v"(s_or), "+v"(s_and));   // fold pair by pair: one accumulator live
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      } else if constexpr (W <= 4) {
         // tile i - 1's sign fold among tile i's products, as the R-phase
         mf_v16f pacc[2];
 #pragma unroll
@@ -402,8 +572,8 @@ __global__ void __launch_bounds__(256) benor_mfma_kernel(KParams p) {
         asm volatile("" : "+v"(s_or), "+v"(s_and));   // fold tile by tile: one accumulator live
         __builtin_amdgcn_sched_barrier(0);
       }
-      const uint64_t b1 = ballot(s_or >> 31);          // some receiver decided 1
-      const uint64_t b0 = ballot(!(s_and >> 31));      // some receiver decided 0
+      const uint64_t b1 = ballot(PAIRED ? (s_or & pairf::kIndP) != 0u : (s_or >> 31) != 0u);     // some receiver decided 1
+      const uint64_t b0 = ballot(PAIRED ? (~s_and & pairf::kIndP) != 0u : !(s_and >> 31));      // some receiver decided 0
       any1 = (uint32_t)b1 | (uint32_t)(b1 >> 32);
       any0 = (uint32_t)b0 | (uint32_t)(b0 >> 32);
     } else {
@@ -488,17 +658,25 @@ __global__ void __launch_bounds__(256) benor_mfma_kernel(KParams p) {
   flush_hist(lhist, p);
 }
 
-template <int W, int KIND>
+template <int W, int KIND, bool PAIR = false>
 static inline void launch_mfma_kind(const KParams &p, int grid, hipStream_t s) {
   if (p.m <= 64u * (uint32_t)(W - 1) + 32u)
-    hipLaunchKernelGGL((benor_mfma_kernel<W, true, KIND>), dim3(grid), dim3(64 * kWavesPerBlock), p.hist_bytes, s, p);
+    hipLaunchKernelGGL((benor_mfma_kernel<W, true, KIND, PAIR>), dim3(grid), dim3(64 * kWavesPerBlock), p.hist_bytes, s, p);
   else
-    hipLaunchKernelGGL((benor_mfma_kernel<W, false, KIND>), dim3(grid), dim3(64 * kWavesPerBlock), p.hist_bytes, s, p);
+    hipLaunchKernelGGL((benor_mfma_kernel<W, false, KIND, PAIR>), dim3(grid), dim3(64 * kWavesPerBlock), p.hist_bytes, s, p);
+}
+
+// KIND 0's form: two receiver tiles per accumulator; BENOR_MFMA_PAIR=0
+// (validation) runs the one-tile form on the same trials.
+template <int W>
+static inline void launch_mfma_sure(const KParams &p, int grid, hipStream_t s) {
+  if (knob_is("BENOR_MFMA_PAIR", "0")) launch_mfma_kind<W, 0, false>(p, grid, s);
+  else launch_mfma_kind<W, 0, true>(p, grid, s);
 }
 
 template <int W>
 hipError_t launch_mfma(const KParams &p, int grid, hipStream_t s) {
-  if (p.G == 0u) launch_mfma_kind<W, 0>(p, grid, s);
+  if (p.G == 0u) launch_mfma_sure<W>(p, grid, s);
   else if (p.G == 1u) launch_mfma_kind<W, 1>(p, grid, s);
   else launch_mfma_kind<W, 2>(p, grid, s);
   return hipGetLastError();

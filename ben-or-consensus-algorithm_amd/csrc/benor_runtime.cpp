@@ -80,6 +80,7 @@ struct KnobSpec {
 constexpr KnobSpec kKnobs[] = {
     {"BENOR_NO_MFMA", "validation"},            // "1": popcount kernels instead of the matrix-core ones
     {"BENOR_NO_MFMA_BIG", "validation"},        // "1": popcount kernels for m > 1024
+    {"BENOR_MFMA_PAIR", "validation"},          // "0": KIND 0 matrix-core kernel, one receiver tile per accumulator
     {"BENOR_BIG_FORM", "validation"},           // "wave" / "coop": big-network matrix-core form
     {"BENOR_COOP_BW", "validation"},            // 4 / 8: waves per cooperative workgroup
     {"BENOR_SMALL_MIN_TRIALS", "validation"},   // packed matrix-core kernel from this launch size
