@@ -43,8 +43,11 @@ BO_MODE_CRASH_TALLY = 5        # mode 4 with crashes during the run: crash_at[i]
                                # round r, +1: its P-phase), or crash_count nodes at random steps below crash_window
 BO_MODE_CRASH_PARTIAL = 6      # mode 5 with partial broadcasts: a crasher's last message reaches the receivers whose
                                # compact index is below its cut (crash_cut = 0..m0 for every crasher, or CUT_RANDOM)
-CRASH_TABLE_MAX_BYTES = 512 << 20   # modes 5 and 6: thresholds of the tables of all reachable live counts, at most
+BO_MODE_CRASH_SUBSET = 7       # mode 6 with an arbitrary subset for the prefix: a crasher's last message reaches each
+                               # receiver independently with probability crash_reach / 2^32 (REACH_ALL: certainly)
+CRASH_TABLE_MAX_BYTES = 512 << 20   # modes 5, 6 and 7: thresholds of the tables of all reachable live counts, at most
 CUT_RANDOM = 0xFFFFFFFF        # crash_cut: a cut per trial and crasher, uniform on 0..m0 (Philox stream 8)
+REACH_ALL = 0xFFFFFFFF         # crash_reach: every crasher reaches every receiver (no Philox stream 9 word is drawn)
 NEVER = 0xFFFFFFFF             # crash_at entry: never stopped / never crashes
 BO_INIT_RANDOM = 0
 BO_INIT_FIXED = 1
@@ -60,6 +63,7 @@ BO_KERNEL_TALLY = 9
 BO_KERNEL_TALLY3 = 10
 BO_KERNEL_TALLY_CRASH = 11
 BO_KERNEL_TALLY_PARTIAL = 12
+BO_KERNEL_TALLY_SUBSET = 13
 KERNEL_NAMES = {BO_KERNEL_NONE: "none", BO_KERNEL_BLOCKED: "blocked popcount", BO_KERNEL_W: "W popcount",
                 BO_KERNEL_RANDOM: "random delivery", BO_KERNEL_EVENT: "event level", BO_KERNEL_LANE: "lane",
                 BO_KERNEL_MFMA: "matrix core (e2m1 MFMA)", BO_KERNEL_MFMA_SMALL: "packed matrix core (e2m1 MFMA, m <= 32)",
@@ -67,7 +71,9 @@ KERNEL_NAMES = {BO_KERNEL_NONE: "none", BO_KERNEL_BLOCKED: "blocked popcount", B
                 BO_KERNEL_TALLY3: "count-level random delivery, three vote classes (hypergeometric tally + walk)",
                 BO_KERNEL_TALLY_CRASH: "count-level random delivery with crashes during the run (a table per live count)",
                 BO_KERNEL_TALLY_PARTIAL: "count-level random delivery with crashes cutting a broadcast short "
-                                         "(a segment of receivers per cut)"}
+                                         "(a segment of receivers per cut)",
+                BO_KERNEL_TALLY_SUBSET: "count-level random delivery with crashes whose last broadcast reaches a random "
+                                        "subset (a reach pass per group, per-lane draws for the receivers it reaches)"}
 BO_MAX_N = 4096
 BO_MAX_K = 1024
 
@@ -447,9 +453,28 @@ def hist_len(k_max: int) -> int:
     return (k_max + 1) * 3 + 1
 
 
+def _cut_word(crash_cut, crash_reach):
+    """The configuration word that mode 6 reads as crash_cut and mode 7 as crash_reach."""
+    if crash_reach is None:
+        return crash_cut
+    if crash_cut:
+        raise ValueError("crash_cut and crash_reach name the same configuration word: give one")
+    if not 0 <= crash_reach <= REACH_ALL:
+        raise ValueError("crash_reach is a probability in units of 2**-32: 0 .. 2**32 - 1")
+    return crash_reach
+
+
+def reach_word(p: float) -> int:
+    """crash_reach of a probability in [0, 1]: 1.0 is REACH_ALL, otherwise floor(p * 2**32)."""
+    if not 0.0 <= p <= 1.0:
+        raise ValueError("a reach probability lies in [0, 1]")
+    return REACH_ALL if p >= 1.0 else int(p * 2.0 ** 32)
+
+
 def _trials_cfg(N, F, faulty=None, *, seed=0, k_max=DEFAULT_K_MAX, initial_values=None, mode=BO_MODE_LOCKSTEP,
-                crash_at=None, crash_count=0, crash_window=0, crash_cut=0):
+                crash_at=None, crash_count=0, crash_window=0, crash_cut=0, crash_reach=None):
     """bo_trials_cfg for a shape, and the ctypes arrays it points into."""
+    crash_cut = _cut_word(crash_cut, crash_reach)
     if faulty is None:                       # start.ts:7-18 placement: the first F nodes
         faulty = [i < F for i in range(N)]
     fl = (ctypes.c_uint8 * max(1, N))(*[1 if v else 0 for v in faulty])
@@ -483,12 +508,12 @@ class TrialsPlan:
     def __init__(self, N: int, F: int, faulty: Sequence[bool] | None = None, *, seed: int = 0,
                  k_max: int = DEFAULT_K_MAX, initial_values: Sequence | None = None,
                  mode: int = BO_MODE_LOCKSTEP, crash_at: Sequence | None = None, crash_count: int = 0,
-                 crash_window: int = 0, crash_cut: int = 0):
+                 crash_window: int = 0, crash_cut: int = 0, crash_reach: int | None = None):
         self.N, self.F, self.k_max, self.seed = N, F, k_max, seed
         self.mode = mode
         self._cfg, self._keep = _trials_cfg(N, F, faulty, seed=seed, k_max=k_max, initial_values=initial_values,
                                             mode=mode, crash_at=crash_at, crash_count=crash_count,
-                                            crash_window=crash_window, crash_cut=crash_cut)
+                                            crash_window=crash_window, crash_cut=crash_cut, crash_reach=crash_reach)
         h = ctypes.c_void_p()
         _check(lib().bo_plan_create(ctypes.byref(self._cfg), ctypes.byref(h)))
         self._h = h
@@ -538,8 +563,9 @@ class TrialsPlan:
 def run_trial_states(N: int, F: int, faulty: Sequence[bool], *, seed: int = 0, trial: int = 0,
                      k_max: int = DEFAULT_K_MAX, initial_values: Sequence | None = None,
                      mode: int = BO_MODE_LOCKSTEP, crash_at: Sequence | None = None, crash_count: int = 0,
-                     crash_window: int = 0, crash_cut: int = 0):
+                     crash_window: int = 0, crash_cut: int = 0, crash_reach: int | None = None):
     """Per-node final states of one trial: (rounds, [NodeState dict] * N)."""
+    crash_cut = _cut_word(crash_cut, crash_reach)
     fl = (ctypes.c_uint8 * max(1, N))(*[1 if v else 0 for v in faulty])
     if initial_values is None:
         init = (ctypes.c_int8 * max(1, N))()

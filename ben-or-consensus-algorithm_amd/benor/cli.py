@@ -9,6 +9,8 @@
     python -m benor.cli trials --N 10 --F 4 --mode crash --crashed 1 --crash-at 3:0,7:1   # node 3 at step 0, node 7 at step 1
     python -m benor.cli trials --N 1024 --F 340 --mode partial --crashed 0 --crash-count 16 --crash-window 4 --crash-cut random
                                                                           # ... each crash cutting its last broadcast short
+    python -m benor.cli trials --N 1024 --F 340 --mode subset --crashed 0 --crash-count 16 --crash-window 4 --crash-reach 0.5
+                                                                          # ... or reaching each receiver with probability 1/2
     python -m benor.cli sweep --N 64,128,...,4096 --steps 32 --trials 2**30 --out sweep.csv
                                                                           # C5 phase diagram
     python -m benor.cli sweep --cells 4096:0,4096:1984 --per-cell 4793490  # two cells of it
@@ -87,10 +89,11 @@ def cmd_trials(a) -> int:
 
     mode = {"lockstep": benor.BO_MODE_LOCKSTEP, "random": benor.BO_MODE_RANDOM_DELIVERY,
             "tally": benor.BO_MODE_RANDOM_TALLY, "tally3": benor.BO_MODE_RANDOM_TALLY3,
-            "crash": benor.BO_MODE_CRASH_TALLY, "partial": benor.BO_MODE_CRASH_PARTIAL}[a.mode]
+            "crash": benor.BO_MODE_CRASH_TALLY, "partial": benor.BO_MODE_CRASH_PARTIAL,
+            "subset": benor.BO_MODE_CRASH_SUBSET}[a.mode]
     crashed = a.F if a.crashed is None else a.crashed            # the first f nodes (start.ts:7-18 placement)
     sched = {}
-    if a.mode in ("crash", "partial"):                            # crashes during the run, in steps
+    if a.mode in ("crash", "partial", "subset"):                  # crashes during the run, in steps
         if a.crash_at and a.crash_count:
             raise SystemExit("--crash-at and --crash-count are exclusive")
         if a.crash_at:
@@ -104,13 +107,19 @@ def cmd_trials(a) -> int:
         else:
             sched = {"crash_count": a.crash_count, "crash_window": a.crash_window}
     elif a.crash_at or a.crash_count:
-        raise SystemExit("--crash-at / --crash-count need --mode crash or --mode partial")
+        raise SystemExit("--crash-at / --crash-count need --mode crash, --mode partial or --mode subset")
     if a.mode == "partial":                                       # ... the last broadcast cut short
         if a.crash_cut is None or (a.crash_cut != "random" and not a.crash_cut.isdigit()):
             raise SystemExit("--mode partial needs --crash-cut: a count of initially-live receivers or 'random'")
         sched["crash_cut"] = benor.CUT_RANDOM if a.crash_cut == "random" else int(a.crash_cut)
     elif a.crash_cut is not None:
         raise SystemExit("--crash-cut needs --mode partial")
+    if a.mode == "subset":                                        # ... reaching a random subset
+        if a.crash_reach is None or not 0.0 <= a.crash_reach <= 1.0:
+            raise SystemExit("--mode subset needs --crash-reach: a probability in [0, 1]")
+        sched["crash_reach"] = benor.reach_word(a.crash_reach)
+    elif a.crash_reach is not None:
+        raise SystemExit("--crash-reach needs --mode subset")
     plan = benor.TrialsPlan(a.N, a.F, [i < crashed for i in range(a.N)], seed=a.seed, k_max=a.k_max, mode=mode,
                             **sched)
     t0 = time.perf_counter()
@@ -119,11 +128,13 @@ def cmd_trials(a) -> int:
     row = summarize(h, a.N, a.F, a.k_max)
     if a.mode != "lockstep" or a.crashed is not None:
         row.update(m=a.N - crashed, mode=a.mode, crashed=crashed, hist=[int(v) for v in h])
-    if a.mode in ("crash", "partial"):                            # m is the initially-live count
+    if a.mode in ("crash", "partial", "subset"):                  # m is the initially-live count
         row.update(crash_count=a.crash_count, crash_window=a.crash_window, crash_at=a.crash_at,
                    kernel=benor.KERNEL_NAMES[plan.kernel])
     if a.mode == "partial":
         row.update(crash_cut=a.crash_cut)
+    if a.mode == "subset":
+        row.update(crash_reach=a.crash_reach, crash_reach_word=sched["crash_reach"])
     row["seconds"] = dt
     print(json.dumps(row))
     return 0
@@ -259,10 +270,12 @@ def main(argv=None) -> int:
     t.add_argument("--begin", type=int, default=0)
     t.add_argument("--seed", type=int, default=0x243F6A8885A308D3)
     t.add_argument("--k-max", type=int, default=16)
-    t.add_argument("--mode", choices=["lockstep", "random", "tally", "tally3", "crash", "partial"], default="lockstep",
+    t.add_argument("--mode", choices=["lockstep", "random", "tally", "tally3", "crash", "partial", "subset"],
+                   default="lockstep",
                    help="delivery model: lockstep, random (mask-level), tally (count-level random delivery: odd "
-                        "quorum, no '?'), tally3 (count-level, any quorum), crash (tally3 with crashes during the run) or "
-                        "partial (crash with the crasher's last broadcast reaching a prefix of the receivers)")
+                        "quorum, no '?'), tally3 (count-level, any quorum), crash (tally3 with crashes during the run), "
+                        "partial (crash with the crasher's last broadcast reaching a prefix of the receivers) or "
+                        "subset (... reaching each receiver independently with probability --crash-reach)")
     t.add_argument("--crashed", type=int, default=None,
                    help="crash the first f nodes (default F; random, tally, tally3 and crash take f <= F)")
     t.add_argument("--crash-count", type=int, default=0,
@@ -273,6 +286,9 @@ def main(argv=None) -> int:
     t.add_argument("--crash-cut", default=None,
                    help="partial: every crasher's last message reaches this many initially-live nodes, in ascending "
                         "node id (0: nobody, as crash; N - f: everybody), or 'random': uniform per trial and crasher")
+    t.add_argument("--crash-reach", type=float, default=None,
+                   help="subset: the probability in [0, 1] that a crasher's last message reaches a receiver (0: nobody, "
+                        "as crash; 1: everybody), independently per trial, crasher and receiver")
     w = sub.add_parser("sweep", help="C5 decision-round phase diagram")
     w.add_argument("--N", default="64,128,256,512,1024,2048,4096")
     w.add_argument("--steps", type=int, default=32)

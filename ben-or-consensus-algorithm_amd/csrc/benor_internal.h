@@ -20,6 +20,7 @@ constexpr uint32_t kStreamTally = 5u;
 constexpr uint32_t kStreamWalk = 6u;       // BO_MODE_RANDOM_TALLY3: the smallest class's selection-sampling draws
 constexpr uint32_t kStreamSchedule = 7u;   // BO_MODE_CRASH_TALLY: a trial's random crash schedule (Floyd's algorithm)
 constexpr uint32_t kStreamCut = 8u;        // BO_MODE_CRASH_PARTIAL: a crasher's random cut, keyed by its compact index
+constexpr uint32_t kStreamReach = 9u;      // BO_MODE_CRASH_SUBSET: whether crasher p's last message reaches receiver c
 
 constexpr int kWavesPerBlock = 4;          // 256-thread workgroups, one trial per wave
 
@@ -64,14 +65,15 @@ struct KParams {
                             // 9: count-level random delivery (benor_tally.hip),
                             // 10: three-valued count-level random delivery (benor_tally3.hip),
                             // 11: the same with crashes during the run (benor_tally_crash.hip),
-                            // 12: ... whose last broadcast reaches a prefix of the receivers (benor_tally_partial.hip)
+                            // 12: ... whose last broadcast reaches a prefix of the receivers (benor_tally_partial.hip),
+                            // 13: ... or a random subset of them, receiver by receiver (benor_tally_subset.hip)
   uint32_t base_variant;    // variant 7: the popcount kernel (1 W, 0 blocked) that serves the state
   uint32_t base_G;          //   launches and the deferred trials, and its G
   uint32_t mode;            // BO_MODE_LOCKSTEP / BO_MODE_RANDOM_DELIVERY / BO_MODE_EVENT / BO_MODE_RANDOM_TALLY /
                             // BO_MODE_RANDOM_TALLY3 / BO_MODE_CRASH_TALLY (a BO_MODE_RANDOM_TALLY3 plan inside
                             // mode 3's scope holds BO_MODE_RANDOM_TALLY here: it is that mode's plan; a
-                            // BO_MODE_CRASH_TALLY or BO_MODE_CRASH_PARTIAL plan with an empty schedule is
-                            // BO_MODE_RANDOM_TALLY3's)
+                            // BO_MODE_CRASH_TALLY, BO_MODE_CRASH_PARTIAL or BO_MODE_CRASH_SUBSET plan with an empty
+                            // schedule is BO_MODE_RANDOM_TALLY3's)
   uint32_t q;               // quorum N - F (messages each receiver tallies per phase)
   uint32_t k_max;
   uint32_t init_mode;       // BO_INIT_RANDOM / BO_INIT_FIXED
@@ -161,7 +163,13 @@ struct KParams {
   // ... with partial broadcasts (variant 12): every crasher's cut, the number of initially-live
   // receivers (compact indices below it) its last message reaches; UINT32_MAX: drawn per trial and
   // crasher from Philox stream 8.  The tables are those of every pool size m_s + |H_c|
-  uint32_t cr_cut;
+  // ... reaching a random subset (variant 13): the same word is the probability, in units of 2^-32,
+  // that a crasher's last message reaches a receiver (UINT32_MAX: certainly), decided per trial,
+  // crasher and receiver by a word of Philox stream 9
+  union {
+    uint32_t cr_cut;
+    uint32_t cr_reach;
+  };
 };
 
 constexpr uint32_t kTimelineWords = 12;
@@ -225,6 +233,12 @@ hipError_t launch_tally_crash(const KParams &p, int grid_blocks, hipStream_t str
 uint32_t partial_wave_bytes(uint32_t W, uint32_t cap, uint32_t ncr, bool random);
 int partial_blocks_per_cu(const KParams &p);      // resident workgroups per CU (registers, LDS); 0 = unknown
 hipError_t launch_tally_partial(const KParams &p, int grid_blocks, hipStream_t stream);
+
+// ... and with broadcasts that reach a random subset (benor_tally_subset.hip): the same
+// layout, the list holding compact index and vote class per entry.
+uint32_t subset_wave_bytes(uint32_t W, uint32_t cap, uint32_t ncr, bool random);
+int subset_blocks_per_cu(const KParams &p);       // resident workgroups per CU (registers, LDS); 0 = unknown
+hipError_t launch_tally_subset(const KParams &p, int grid_blocks, hipStream_t stream);
 
 // Event level for kMaxEventN < N <= BO_MAX_N (benor_event_big.hip): one wave per trial.
 // The wave-per-trial event kernel keeps its message pool in LDS when it is at

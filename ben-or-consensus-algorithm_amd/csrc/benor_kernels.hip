@@ -676,6 +676,17 @@ void plan_geometry(KParams &p) {
     p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
     return;
   }
+  if (p.mode == BO_MODE_CRASH_SUBSET) {
+    // ... or broadcasts that reach a random subset (benor_tally_subset.hip): the same pools, the same row region
+    p.G = 1;
+    p.nblocks = W;
+    p.variant = 13u;
+    const uint32_t e = p.m - p.q;
+    p.tally_cap = p.q <= e ? p.q : e;
+    p.wave_bytes = (subset_wave_bytes(W, p.tally_cap, p.cr_n, p.cr_random != 0u) + 15u) & ~15u;
+    p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
+    return;
+  }
   if (p.m <= kMaxLaneM) {                           // lane kernel: one trial per lane
     const uint32_t M1 = p.m - p.init_q;
     const bool odd = (p.m & 1u) && (M1 & 1u);        // every vote count odd: no tie, no coin
@@ -811,6 +822,7 @@ hipError_t launch_lockstep(const KParams &p, int grid, hipStream_t s) {
   if (p.variant == 10) return launch_tally3(p, grid, s);
   if (p.variant == 11) return launch_tally_crash(p, grid, s);
   if (p.variant == 12) return launch_tally_partial(p, grid, s);
+  if (p.variant == 13) return launch_tally_subset(p, grid, s);
   if (p.variant == 2 && p.rd_a) return launch_random_bern(p, grid, s);
   if (p.variant == 2) {                      // Floyd sampler
     if (p.lds_bytes > 64u * 1024u) {
@@ -931,6 +943,10 @@ int lockstep_grid(const KParams &p, int device) {
   }
   if (p.variant == 12) {                     // ... and with partial broadcasts
     const uint64_t fit = (uint64_t)partial_blocks_per_cu(p);
+    if (fit >= 1u && fit < per_cu) per_cu = fit;
+  }
+  if (p.variant == 13) {                     // ... that reach a random subset
+    const uint64_t fit = (uint64_t)subset_blocks_per_cu(p);
     if (fit >= 1u && fit < per_cu) per_cu = fit;
   }
   // Lane kernel: a short launch spread over every wave slot (~2 trials per

@@ -587,11 +587,12 @@ static napi_value run_trials(napi_env env, napi_callback_info info) {
     j->trial_begin = prop_u64(env, o, "trialBegin", 0);
     j->trial_count = prop_u64(env, o, "trialCount", 1);
     uint32_t mode = BO_MODE_LOCKSTEP;
-    prop_u32(env, o, "mode", BO_MODE_LOCKSTEP, &mode);          /* 0 lockstep, 1 random delivery, 2 event, 3 random tally, 4 random tally3, 5 crash tally, 6 crash partial */
+    prop_u32(env, o, "mode", BO_MODE_LOCKSTEP, &mode);          /* 0 lockstep, 1 random delivery, 2 event, 3 random tally, 4 random tally3, 5 crash tally, 6 crash partial, 7 crash subset */
     j->cfg.mode = mode;
     prop_u32(env, o, "crashCount", 0, &j->cfg.crash_count);
     prop_u32(env, o, "crashWindow", 0, &j->cfg.crash_window);
     prop_u32(env, o, "crashCut", 0, &j->cfg.crash_cut);          /* mode 6: 0 .. N - f, or BO_CUT_RANDOM */
+    prop_u32(env, o, "crashReach", j->cfg.crash_cut, &j->cfg.crash_reach);   /* mode 7: the same word, a probability in units of 2^-32 */
     const uint32_t N = j->cfg.N;
     j->faulty = (uint8_t *)calloc(N + 1, 1);
     j->init = (int8_t *)calloc(N + 1, 1);

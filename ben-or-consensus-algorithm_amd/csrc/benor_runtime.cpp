@@ -526,9 +526,10 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   if (cfg->k_max < 1 || cfg->k_max > BO_MAX_K) return fail(BO_ERR_INVALID_ARGUMENT, "k_max must be in [1, 1024]");
   if (cfg->mode != BO_MODE_LOCKSTEP && cfg->mode != BO_MODE_RANDOM_DELIVERY && cfg->mode != BO_MODE_EVENT &&
       cfg->mode != BO_MODE_RANDOM_TALLY && cfg->mode != BO_MODE_RANDOM_TALLY3 && cfg->mode != BO_MODE_CRASH_TALLY &&
-      cfg->mode != BO_MODE_CRASH_PARTIAL)
+      cfg->mode != BO_MODE_CRASH_PARTIAL && cfg->mode != BO_MODE_CRASH_SUBSET)
     return fail(BO_ERR_UNSUPPORTED, "unknown delivery mode");
-  const bool crash_mode = cfg->mode == BO_MODE_CRASH_TALLY || cfg->mode == BO_MODE_CRASH_PARTIAL;
+  const bool crash_mode = cfg->mode == BO_MODE_CRASH_TALLY || cfg->mode == BO_MODE_CRASH_PARTIAL ||
+                          cfg->mode == BO_MODE_CRASH_SUBSET;
   const bool random_mode = cfg->mode == BO_MODE_RANDOM_DELIVERY || cfg->mode == BO_MODE_RANDOM_TALLY ||
                            cfg->mode == BO_MODE_RANDOM_TALLY3 || crash_mode;
   if (cfg->init_mode != BO_INIT_RANDOM && cfg->init_mode != BO_INIT_FIXED)
@@ -547,8 +548,8 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   for (uint32_t i = 0; i < cfg->N; ++i)
     if (!cfg->faulty[i]) live.push_back(i);
   const uint32_t m = (uint32_t)live.size();
-  // Crashes during the run (BO_MODE_CRASH_TALLY, BO_MODE_CRASH_PARTIAL): with the initially
-  // faulty nodes at most F, so every step has a quorum of live senders.
+  // Crashes during the run (BO_MODE_CRASH_TALLY, BO_MODE_CRASH_PARTIAL, BO_MODE_CRASH_SUBSET): with
+  // the initially faulty nodes at most F, so every step has a quorum of live senders.
   uint64_t n_crash = 0;
   bool crash_random = false;
   if (crash_mode) {
@@ -560,12 +561,14 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
       crash_random = true;
     }
     if ((uint64_t)f + n_crash > cfg->F)
-      return fail(BO_ERR_FAULTY_COUNT, cfg->mode == BO_MODE_CRASH_TALLY
-                                           ? "BO_MODE_CRASH_TALLY needs at most F nodes faulty or scheduled to crash"
-                                           : "BO_MODE_CRASH_PARTIAL needs at most F nodes faulty or scheduled to crash");
+      return fail(BO_ERR_FAULTY_COUNT,
+                  cfg->mode == BO_MODE_CRASH_TALLY     ? "BO_MODE_CRASH_TALLY needs at most F nodes faulty or scheduled to crash"
+                  : cfg->mode == BO_MODE_CRASH_PARTIAL ? "BO_MODE_CRASH_PARTIAL needs at most F nodes faulty or scheduled to crash"
+                                                       : "BO_MODE_CRASH_SUBSET needs at most F nodes faulty or scheduled to crash");
     // Partial broadcasts: a cut counts initially-live receivers
     if (cfg->mode == BO_MODE_CRASH_PARTIAL && cfg->crash_cut != BO_CUT_RANDOM && cfg->crash_cut > m)
       return fail(BO_ERR_INVALID_ARGUMENT, "crash_cut must be at most the initially-live count N - f, or BO_CUT_RANDOM");
+    // (BO_MODE_CRASH_SUBSET reads the word as crash_reach, a probability in units of 2^-32: every value is one)
   }
   kp = benor::KParams{};
   kp.N = cfg->N;
@@ -613,12 +616,13 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   // A BO_MODE_CRASH_TALLY plan with an empty schedule is the three-valued mode's plan.
   if (crash_mode && n_crash == 0) kp.mode = BO_MODE_RANDOM_TALLY3;
   if (kp.mode == BO_MODE_RANDOM_TALLY3 && (kp.q & 1u) && !kp.init_q) kp.mode = BO_MODE_RANDOM_TALLY;
-  if (kp.mode == BO_MODE_CRASH_TALLY || kp.mode == BO_MODE_CRASH_PARTIAL) {
+  if (kp.mode == BO_MODE_CRASH_TALLY || kp.mode == BO_MODE_CRASH_PARTIAL || kp.mode == BO_MODE_CRASH_SUBSET) {
     CrashPlan local;
     CrashPlan &cp = crash ? *crash : local;
     cp.list.clear();
     kp.cr_random = crash_random ? 1u : 0u;
     kp.cr_cut = kp.mode == BO_MODE_CRASH_PARTIAL ? cfg->crash_cut : 0u;
+    if (kp.mode == BO_MODE_CRASH_SUBSET) kp.cr_reach = cfg->crash_reach;
     if (crash_random) {
       kp.cr_n = (uint32_t)n_crash;
       cp.reach.assign(kp.cr_n + 1u, 1);            // every m0 - j, j = 0 .. crash_count
@@ -636,7 +640,10 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
       // Partial broadcasts: a receiver's pool is the alive set and the step's crashers that reach
       // it.  A fixed cut gives all of them or none, live counts of the set above; random cuts
       // any number of them, so every m0 - j
-      if (kp.cr_cut == BO_CUT_RANDOM) cp.reach.assign(kp.cr_n + 1u, 1);
+      if (kp.mode == BO_MODE_CRASH_PARTIAL && kp.cr_cut == BO_CUT_RANDOM) cp.reach.assign(kp.cr_n + 1u, 1);
+      // A random subset: any number of a step's crashers may reach a receiver, every m0 - j (at reach
+      // 0 and UINT32_MAX too: one rule for the mode)
+      if (kp.mode == BO_MODE_CRASH_SUBSET) cp.reach.assign(kp.cr_n + 1u, 1);
     }
     uint64_t bytes = 0;
     for (uint32_t d = 0; d <= kp.cr_n; ++d)
@@ -646,7 +653,10 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
                   kp.mode == BO_MODE_CRASH_TALLY
                       ? "BO_MODE_CRASH_TALLY: the threshold tables of the reachable live counts exceed "
                         "the 512 MiB limit (BO_CRASH_TABLE_MAX_BYTES): schedule fewer crashes"
-                      : "BO_MODE_CRASH_PARTIAL: the threshold tables of the reachable pool sizes exceed "
+                  : kp.mode == BO_MODE_CRASH_PARTIAL
+                      ? "BO_MODE_CRASH_PARTIAL: the threshold tables of the reachable pool sizes exceed "
+                        "the 512 MiB limit (BO_CRASH_TABLE_MAX_BYTES): schedule fewer crashes"
+                      : "BO_MODE_CRASH_SUBSET: the threshold tables of the reachable pool sizes exceed "
                         "the 512 MiB limit (BO_CRASH_TABLE_MAX_BYTES): schedule fewer crashes");
   }
   benor::plan_geometry(kp);   // after init_q: the kernel choice depends on the round-1 vote parity
@@ -786,8 +796,9 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
       if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "tally table upload"); }
       kp.tally_off = reinterpret_cast<const uint32_t *>(pl->d_tally);
       kp.tally_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + off_bytes);
-    } else if (kp.variant == 11 || kp.variant == 12) {
-      // BO_MODE_CRASH_TALLY, BO_MODE_CRASH_PARTIAL: one table per reachable live count (pool size), and their directory
+    } else if (kp.variant == 11 || kp.variant == 12 || kp.variant == 13) {
+      // BO_MODE_CRASH_TALLY, BO_MODE_CRASH_PARTIAL, BO_MODE_CRASH_SUBSET: one table per reachable live count (pool
+      // size), and their directory
       std::vector<benor::CrashDir> dir(kp.cr_n + 1u);
       std::vector<uint32_t> off;
       std::vector<uint64_t> thr;
@@ -867,7 +878,7 @@ uint64_t bo_plan_popc_words_per_node_round(const bo_plan *pl) {
   uint64_t counts = 4ull;
   if (pl->kp.mode != BO_MODE_RANDOM_DELIVERY && pl->kp.mode != BO_MODE_RANDOM_TALLY &&
       pl->kp.mode != BO_MODE_RANDOM_TALLY3 && pl->kp.mode != BO_MODE_CRASH_TALLY &&
-      pl->kp.mode != BO_MODE_CRASH_PARTIAL)
+      pl->kp.mode != BO_MODE_CRASH_PARTIAL && pl->kp.mode != BO_MODE_CRASH_SUBSET)
     counts = ((pl->kp.m - pl->kp.init_q) & 1u) ? 2ull : 3ull;
   return counts * ((pl->kp.m + 31ull) / 32ull);
 }

@@ -91,10 +91,13 @@ export interface TrialsConfig {
    *    the R-phase of round r, step 2(r-1)+1 = its P-phase; f + scheduled crashes <= F; an empty schedule is
    *    mode 4 bit for bit),
    *  6 mode 5 with partial broadcasts (MODE_CRASH_PARTIAL: a crasher's last message reaches the initially-live
-   *    nodes whose index, in ascending node id, is below its cut; crashCut = 0 is mode 5 bit for bit) */
-  mode?: 0 | 1 | 2 | 3 | 4 | 5 | 6;
+   *    nodes whose index, in ascending node id, is below its cut; crashCut = 0 is mode 5 bit for bit),
+   *  7 mode 6 with an arbitrary subset for the prefix (MODE_CRASH_SUBSET: a crasher's last message reaches each
+   *    receiver independently with probability crashReach / 2^32; crashReach = 0 is mode 5 and REACH_ALL is
+   *    mode 6 with a full cut, bit for bit) */
+  mode?: 0 | 1 | 2 | 3 | 4 | 5 | 6 | 7;
   /** event mode: deliveries after which node i is stopped (null = never);
-   *  MODE_CRASH_TALLY, MODE_CRASH_PARTIAL: the step at which node i crashes (null = never) */
+   *  MODE_CRASH_TALLY, MODE_CRASH_PARTIAL, MODE_CRASH_SUBSET: the step at which node i crashes (null = never) */
   crashAt?: (number | null)[];
   /** event mode, random schedule: stop crashCount live nodes at uniform delivery counts in [0, crashWindow);
    *  MODE_CRASH_TALLY: crashCount initially-live nodes crash at uniform steps in [0, crashWindow), per trial */
@@ -103,6 +106,9 @@ export interface TrialsConfig {
   /** MODE_CRASH_PARTIAL: every crasher's cut, 0 .. the initially-live count, or CUT_RANDOM (uniform per trial
    *  and crasher); default 0 */
   crashCut?: number;
+  /** MODE_CRASH_SUBSET: the probability, in units of 2^-32, that a crasher's last message reaches a receiver
+   *  (0 .. REACH_ALL = 2^32 - 1: certainly); it fills the word that crashCut fills, so give one of the two */
+  crashReach?: number;
 }
 
 /** TrialsConfig.mode values (include/benor.h BO_MODE_*). */
@@ -115,6 +121,9 @@ export declare const MODE_CRASH_TALLY: 5;
 export declare const MODE_CRASH_PARTIAL: 6;
 /** TrialsConfig.crashCut: a cut per trial and crasher (include/benor.h BO_CUT_RANDOM). */
 export declare const CUT_RANDOM: 4294967295;
+export declare const MODE_CRASH_SUBSET: 7;
+/** TrialsConfig.crashReach: every crasher reaches every receiver (include/benor.h, crash_reach = UINT32_MAX). */
+export declare const REACH_ALL: 4294967295;
 
 /** Outcome histogram, (kMax + 1) * 3 + 1 bins (include/benor.h). */
 export declare function runTrials(cfg: TrialsConfig): Promise<BigUint64Array>;

@@ -18,9 +18,12 @@ const DEFAULT_K_MAX = 64;             // round cap: the reference runs until /st
 const MODE_LOCKSTEP = 0, MODE_RANDOM_DELIVERY = 1, MODE_EVENT = 2, MODE_RANDOM_TALLY = 3,
   MODE_RANDOM_TALLY3 = 4,
   MODE_CRASH_TALLY = 5,
-  MODE_CRASH_PARTIAL = 6;
+  MODE_CRASH_PARTIAL = 6,
+  MODE_CRASH_SUBSET = 7;
 // runTrials cfg.crashCut (MODE_CRASH_PARTIAL): a cut per trial and crasher (BO_CUT_RANDOM)
 const CUT_RANDOM = 0xFFFFFFFF;
+// runTrials cfg.crashReach (MODE_CRASH_SUBSET): every crasher reaches every receiver
+const REACH_ALL = 0xFFFFFFFF;
 
 let current = null;                   // { handle, N }
 
@@ -216,5 +219,5 @@ module.exports = {
   getNodeState, getNodesState, getNodeStatus, reachedFinality, runTrials, delay,
   waitConsensus, liveStopEvents, getNodesStateAt,
   MODE_LOCKSTEP, MODE_RANDOM_DELIVERY, MODE_EVENT, MODE_RANDOM_TALLY, MODE_RANDOM_TALLY3, MODE_CRASH_TALLY,
-  MODE_CRASH_PARTIAL, CUT_RANDOM,
+  MODE_CRASH_PARTIAL, CUT_RANDOM, MODE_CRASH_SUBSET, REACH_ALL,
 };

@@ -127,9 +127,33 @@ enum {
  * explicit schedule of even steps with crash_cut = m0 gives CRASH_TALLY's results
  * for the schedule with every step one later.  The tables are those of every pool
  * size: with a fixed cut CRASH_TALLY's set, with random cuts every m0 - j, j = 0
- * .. the number of scheduled crashes below step 2 k_max.  Not modelled: subsets
- * that are no prefix, a cut per node given explicitly.  Batch API only (no
- * network API, no `sweep`). */
+ * .. the number of scheduled crashes below step 2 k_max.  Not modelled: a cut
+ * per node given explicitly; subsets that are no prefix are CRASH_SUBSET's.  Batch
+ * API only (no network API, no `sweep`). */
+/* CRASH_SUBSET is CRASH_PARTIAL with the prefix replaced by an arbitrary subset
+ * (DESIGN §4.3.5): the model of the paper, in which the last message of a process
+ * that crashes in the middle of a step is received by any subset of the others,
+ * here an independent one per receiver.  The configuration word that
+ * CRASH_PARTIAL reads as crash_cut is read as crash_reach, a probability in units
+ * of 2^-32; every 32-bit value is valid.  Crasher p's step-s message reaches
+ * receiver c (p, c compact indices) iff crash_reach == UINT32_MAX or
+ * word(p, c) < crash_reach, word(p, c) = element c & 3 of the Philox4x32-10 block
+ * ctr = {trial_lo, trial_hi, p | (c >> 2) << 12, 9 << 24}, key = seed (stream 9;
+ * p < 2^12, c >> 2 < 2^10).  The word is keyed by trial, crasher and receiver
+ * only: not by the schedule's order, the step (a node crashes once per trial) or
+ * the launch split.  crash_reach = 0 reaches nobody, UINT32_MAX everybody, and
+ * neither draws a stream-9 word.  At step s receiver c of the alive set A_s has
+ * H_c = { p crashing at s : p reaches c } and draws its N-F messages from the
+ * pool A_s + H_c: CRASH_TALLY's draw with m = m_s + |H_c| and the class sizes
+ * counted over that pool (the m = N-F shortcut per receiver).  Everything else --
+ * schedule, validation, the class of a crasher's last message, halting, outcome,
+ * per-node states, the table limit -- is CRASH_PARTIAL's.  An empty schedule is
+ * RANDOM_TALLY3's plan; crash_reach = 0 gives CRASH_TALLY's results bit for bit
+ * and crash_reach = UINT32_MAX gives CRASH_PARTIAL's with crash_cut = m0, both on
+ * this mode's kernel.  The tables are those of every m0 - j, j = 0 .. the number
+ * of scheduled crashes below step 2 k_max, at every reach.  Not modelled: a reach
+ * per crasher, explicitly given reach masks.  Batch API only (no network API, no
+ * `sweep`). */
 enum {
   BO_MODE_LOCKSTEP = 0,
   BO_MODE_RANDOM_DELIVERY = 1,
@@ -137,13 +161,14 @@ enum {
   BO_MODE_RANDOM_TALLY = 3,
   BO_MODE_RANDOM_TALLY3 = 4,
   BO_MODE_CRASH_TALLY = 5,
-  BO_MODE_CRASH_PARTIAL = 6
+  BO_MODE_CRASH_PARTIAL = 6,
+  BO_MODE_CRASH_SUBSET = 7
 };
 
 /* BO_MODE_CRASH_PARTIAL, crash_cut: a cut per trial and crasher, uniform on 0..m0. */
 #define BO_CUT_RANDOM 0xFFFFFFFFu
 
-/* BO_MODE_CRASH_TALLY, BO_MODE_CRASH_PARTIAL: most bytes of 64-bit thresholds that the tables of a
+/* BO_MODE_CRASH_TALLY, BO_MODE_CRASH_PARTIAL, BO_MODE_CRASH_SUBSET: most bytes of 64-bit thresholds that the tables of a
  * plan's reachable live counts may hold together (512 MiB).  The table of
  * (m', q = N-F) holds the sum over K = 0..m' of min(K, q) - max(0, q - (m' - K))
  * thresholds. */
@@ -279,15 +304,19 @@ typedef struct bo_trials_cfg {
     uint32_t k_max;           /* round cap, 1..BO_MAX_K */
     uint32_t init_mode;       /* BO_INIT_RANDOM: iid Bernoulli(1/2) per live node; BO_INIT_FIXED */
     uint32_t mode;            /* BO_MODE_* */
-    uint32_t crash_cut;       /* CRASH_PARTIAL: every crasher's cut, 0..m0, or BO_CUT_RANDOM; the other modes ignore it */
+    union {                   /* one word, the layout of the struct is that of ABI version 8 */
+        uint32_t crash_cut;   /* CRASH_PARTIAL: every crasher's cut, 0..m0, or BO_CUT_RANDOM */
+        uint32_t crash_reach; /* CRASH_SUBSET: the probability, in units of 2^-32, that a crasher's last message
+                                 reaches a receiver (0: never, UINT32_MAX: certainly); every value is valid */
+    };                        /* the other modes ignore it */
     uint64_t seed;            /* Philox4x32-10 key */
-    const uint8_t *faulty;    /* host [N]; exactly F set (LOCKSTEP, EVENT), at most F (RANDOM_DELIVERY, RANDOM_TALLY, RANDOM_TALLY3, CRASH_TALLY, CRASH_PARTIAL) */
+    const uint8_t *faulty;    /* host [N]; exactly F set (LOCKSTEP, EVENT), at most F (RANDOM_DELIVERY, RANDOM_TALLY, RANDOM_TALLY3, CRASH_TALLY, CRASH_PARTIAL, CRASH_SUBSET) */
     const int8_t *init;       /* host [N]; used when init_mode == BO_INIT_FIXED */
     /* EVENT mode: GET /stop schedule.  crash_at[i] = number of deliveries
      * after which node i is stopped (UINT32_MAX = never), or, when crash_at is
      * NULL, crash_count distinct live nodes stopped at uniform delivery counts
      * in [0, crash_window), drawn per trial from Philox.
-     * CRASH_TALLY and CRASH_PARTIAL modes: the crash schedule in steps.  crash_at[i] = the step
+     * CRASH_TALLY, CRASH_PARTIAL and CRASH_SUBSET modes: the crash schedule in steps.  crash_at[i] = the step
      * at which node i crashes (UINT32_MAX = never; entries of faulty nodes are
      * ignored), or, when crash_at is NULL, crash_count distinct initially-live
      * nodes at uniform steps in [0, crash_window), drawn per trial.
@@ -336,8 +365,8 @@ int bo_plan_check(bo_plan *plan);
  * (c0 = M - c1); the P-phase counts c1 when M is odd (no tie, so no "?"
  * proposal: c0 = m - c1) and c0, c1 otherwise -- 2 or 3 x ceil(m/32).
  * RANDOM_DELIVERY: both values in both phases, 4 x ceil(m/32).  RANDOM_TALLY,
- * RANDOM_TALLY3, CRASH_TALLY and CRASH_PARTIAL answer RANDOM_DELIVERY's unit, the
- * work they stand in for (the last two with m = the initially-live count, as
+ * RANDOM_TALLY3, CRASH_TALLY, CRASH_PARTIAL and CRASH_SUBSET answer RANDOM_DELIVERY's unit,
+ * the work they stand in for (the last three with m = the initially-live count, as
  * bo_plan_live_nodes reports it). */
 uint64_t bo_plan_popc_words_per_node_round(const bo_plan *plan);
 uint32_t bo_plan_live_nodes(const bo_plan *plan);
@@ -369,9 +398,14 @@ enum {
                               set of each step -- alive, x, proposal and decided ballot planes per trial,
                               one table per reachable live count (an empty schedule runs RANDOM_TALLY3's
                               kernel choice) */
-  BO_KERNEL_TALLY_PARTIAL = 12 /* BO_MODE_CRASH_PARTIAL with a non-empty schedule: TALLY_CRASH's step run once
+  BO_KERNEL_TALLY_PARTIAL = 12, /* BO_MODE_CRASH_PARTIAL with a non-empty schedule: TALLY_CRASH's step run once
                               per segment of receivers that hear the same crashers (the cuts of the step's
                               crashers are the boundaries), one table per pool size */
+  BO_KERNEL_TALLY_SUBSET = 13 /* BO_MODE_CRASH_SUBSET with a non-empty schedule: per receiver group a reach pass
+                              (which of the step's crashers each lane hears, Philox stream 9), then
+                              TALLY_CRASH's wave-uniform draw for the lanes that hear none of them and one
+                              per-lane draw, each lane searching the row of its own pool in global memory,
+                              for the others; one table per pool size */
 };
 
 /* The kernel family bo_plan_launch runs for this plan.  (The per-node-state

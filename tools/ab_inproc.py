@@ -14,7 +14,7 @@ median and minimum ms per launch and the variant's median / first variant's.
 
 A shape may carry a fourth field f < F (the first f nodes crashed, the rest of
 F the random-delivery slack: BO_MODE_RANDOM_DELIVERY).  A variant may also name
-the delivery mode with the pseudo-variable `mode` (lockstep, random, tally, tally3, crash or partial),
+the delivery mode with the pseudo-variable `mode` (lockstep, random, tally, tally3, crash, partial or subset),
 so the mask-level and the count-level random-delivery modes are timed
 alternately on one plan each:
 
@@ -34,6 +34,14 @@ results on its own kernel, so that pair times the kernel's overhead alone:
 
     python tools/ab_inproc.py --rounds 7 --reps 5 --shapes "1024,340,100000,0" --variants \
         "m5=mode:crash,crash_count:16,crash_window:4;cut0=mode:partial,crash_count:16,crash_window:4,crash_cut:0;rand=mode:partial,crash_count:16,crash_window:4,crash_cut:random"
+
+`mode:subset` (BO_MODE_CRASH_SUBSET) takes the same schedule and `crash_reach`: `all`
+(UINT32_MAX), a probability with a decimal point (0.5) or the 32-bit word itself.  At
+`crash_reach:0` it gives mode:crash's results and at `crash_reach:all` those of
+mode:partial with a full cut, both on its own kernel:
+
+    python tools/ab_inproc.py --rounds 7 --reps 5 --shapes "1024,340,100000,0" --variants \
+        "m5=mode:crash,crash_count:16,crash_window:4;r0=mode:subset,crash_count:16,crash_window:4,crash_reach:0;half=mode:subset,crash_count:16,crash_window:4,crash_reach:0.5"
 
 Every line also reports
 the live node-rounds per second its launches represent (bench.py node_rounds),
@@ -75,7 +83,8 @@ def main():
         v = [int(x) for x in sp.split(",")]
         shapes.append((v[0], v[1], v[2], v[3] if len(v) > 3 else v[1]))
     modes = {name: env.pop("mode", None) for name, env in variants}   # `mode` is no environment variable
-    scheds = {name: {k: env.pop(k) for k in ("crash_count", "crash_window", "crash_at", "crash_cut") if k in env}
+    scheds = {name: {k: env.pop(k) for k in ("crash_count", "crash_window", "crash_at", "crash_cut", "crash_reach")
+                     if k in env}
               for name, env in variants}                              # ... nor is the crash schedule
     knobs = sorted({k for _, env in variants for k in env})
 
@@ -85,18 +94,22 @@ def main():
         ap.error(f"not a registered libbenor knob (benor.KNOBS): {unknown}")
     mode_ids = {"lockstep": benor.BO_MODE_LOCKSTEP, "random": benor.BO_MODE_RANDOM_DELIVERY,
                 "tally": benor.BO_MODE_RANDOM_TALLY, "tally3": benor.BO_MODE_RANDOM_TALLY3,
-                "crash": benor.BO_MODE_CRASH_TALLY, "partial": benor.BO_MODE_CRASH_PARTIAL}
+                "crash": benor.BO_MODE_CRASH_TALLY, "partial": benor.BO_MODE_CRASH_PARTIAL,
+                "subset": benor.BO_MODE_CRASH_SUBSET}
     bad = sorted({v for v in modes.values() if v is not None and v not in mode_ids})
     if bad:
         ap.error(f"mode must be one of {sorted(mode_ids)}: {bad}")
-    if any(sc and modes[name] not in ("crash", "partial") for name, sc in scheds.items()):
-        ap.error("crash_count / crash_window / crash_at need mode:crash or mode:partial")
+    if any(sc and modes[name] not in ("crash", "partial", "subset") for name, sc in scheds.items()):
+        ap.error("crash_count / crash_window / crash_at need mode:crash, mode:partial or mode:subset")
     if any("crash_cut" in sc and modes[name] != "partial" for name, sc in scheds.items()):
         ap.error("crash_cut needs mode:partial")
+    if any("crash_reach" in sc and modes[name] != "subset" for name, sc in scheds.items()):
+        ap.error("crash_reach needs mode:subset")
 
     def schedule(name, N):
         sc, kw = dict(scheds[name]), {}
         cut = sc.pop("crash_cut", None)
+        reach = sc.pop("crash_reach", None)
         if "crash_at" in sc:
             kw["crash_at"] = [None] * N
             for part in sc["crash_at"].split("+"):
@@ -106,6 +119,9 @@ def main():
             kw = {k: int(v) for k, v in sc.items()}
         if cut is not None:
             kw["crash_cut"] = benor.CUT_RANDOM if cut == "random" else int(cut)
+        if reach is not None:
+            kw["crash_reach"] = (benor.REACH_ALL if reach == "all" else
+                                 benor.reach_word(float(reach)) if "." in reach else int(reach))
         return kw
 
     import numpy as np
