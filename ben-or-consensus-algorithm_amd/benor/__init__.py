@@ -45,6 +45,11 @@ BO_MODE_CRASH_PARTIAL = 6      # mode 5 with partial broadcasts: a crasher's las
                                # compact index is below its cut (crash_cut = 0..m0 for every crasher, or CUT_RANDOM)
 BO_MODE_CRASH_SUBSET = 7       # mode 6 with an arbitrary subset for the prefix: a crasher's last message reaches each
                                # receiver independently with probability crash_reach / 2^32 (REACH_ALL: certainly)
+BO_MODE_BYZ_TALLY = 8          # mode 4 with Byzantine senders: byzantine[i] marks node i (it sends at every step and
+                               # lies, it never receives); byz_one / 2^32 is the probability that a Byzantine message
+                               # carries 1, byz_strategy BYZ_RANDOM (independently per receiver) or BYZ_OPPOSE
+BYZ_RANDOM = 0                 # byz_strategy: each Byzantine message is 1 with probability byz_one / 2^32 (equivocation)
+BYZ_OPPOSE = 1                 # ... every one carries the value fewer honest senders hold (byz_one's step on a tie)
 CRASH_TABLE_MAX_BYTES = 512 << 20   # modes 5, 6 and 7: thresholds of the tables of all reachable live counts, at most
 CUT_RANDOM = 0xFFFFFFFF        # crash_cut: a cut per trial and crasher, uniform on 0..m0 (Philox stream 8)
 REACH_ALL = 0xFFFFFFFF         # crash_reach: every crasher reaches every receiver (no Philox stream 9 word is drawn)
@@ -64,6 +69,7 @@ BO_KERNEL_TALLY3 = 10
 BO_KERNEL_TALLY_CRASH = 11
 BO_KERNEL_TALLY_PARTIAL = 12
 BO_KERNEL_TALLY_SUBSET = 13
+BO_KERNEL_TALLY_BYZ = 14
 KERNEL_NAMES = {BO_KERNEL_NONE: "none", BO_KERNEL_BLOCKED: "blocked popcount", BO_KERNEL_W: "W popcount",
                 BO_KERNEL_RANDOM: "random delivery", BO_KERNEL_EVENT: "event level", BO_KERNEL_LANE: "lane",
                 BO_KERNEL_MFMA: "matrix core (e2m1 MFMA)", BO_KERNEL_MFMA_SMALL: "packed matrix core (e2m1 MFMA, m <= 32)",
@@ -73,7 +79,9 @@ KERNEL_NAMES = {BO_KERNEL_NONE: "none", BO_KERNEL_BLOCKED: "blocked popcount", B
                 BO_KERNEL_TALLY_PARTIAL: "count-level random delivery with crashes cutting a broadcast short "
                                          "(a segment of receivers per cut)",
                 BO_KERNEL_TALLY_SUBSET: "count-level random delivery with crashes whose last broadcast reaches a random "
-                                        "subset (a reach pass per group, per-lane draws for the receivers it reaches)"}
+                                        "subset (a reach pass per group, per-lane draws for the receivers it reaches)",
+                BO_KERNEL_TALLY_BYZ: "count-level random delivery with Byzantine senders (an honest plane, wave-uniform "
+                                     "steps from a staged row, per-lane Binomial lies and draws otherwise)"}
 BO_MAX_N = 4096
 BO_MAX_K = 1024
 
@@ -100,7 +108,7 @@ EXPORTED_SYMBOLS = (
     "bo_popc_peak", "bo_last_error", "bo_abi_version", "bo_kernel_version", "bo_plan_kernel", "bo_kernel_for",
     "bo_mfma_peak", "bo_consensus_start_sched", "bo_plan_check",
     "bo_consensus_start_live", "bo_consensus_wait", "bo_live_stop_events", "bo_get_states", "bo_consensus_poll",
-    "bo_tally_cdf",
+    "bo_tally_cdf", "bo_byz_cdf",
 )
 
 
@@ -186,6 +194,7 @@ def lib() -> ctypes.CDLL:
     L.bo_kernel_for.argtypes = [P(TrialsCfgC), P(ctypes.c_int)]
     L.bo_tally_cdf.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P(ctypes.c_uint32),
                                P(ctypes.c_uint64), ctypes.c_uint32, P(ctypes.c_uint32)]
+    L.bo_byz_cdf.argtypes = [ctypes.c_uint32, ctypes.c_uint32, P(ctypes.c_uint64), ctypes.c_uint32, P(ctypes.c_uint32)]
     L.bo_last_error.restype = ctypes.c_char_p
     L.bo_abi_version.restype = ctypes.c_int
     L.bo_kernel_version.restype = ctypes.c_char_p
@@ -471,13 +480,45 @@ def reach_word(p: float) -> int:
     return REACH_ALL if p >= 1.0 else int(p * 2.0 ** 32)
 
 
+def _byz_words(mode, crash_cut, crash_count, byzantine, byz_one, byz_strategy):
+    """Mode 8 reads the crash_cut word as byz_one and the crash_count word as byz_strategy."""
+    if byzantine is None and byz_one is None and byz_strategy is None:
+        return crash_cut, crash_count
+    if mode != BO_MODE_BYZ_TALLY:
+        raise ValueError("byzantine, byz_one and byz_strategy need mode=BO_MODE_BYZ_TALLY")
+    if crash_cut or crash_count:
+        raise ValueError("byz_one / byz_strategy name the configuration words of crash_cut / crash_count: give one")
+    byz_one = 0 if byz_one is None else byz_one
+    if not 0 <= byz_one <= 0xFFFFFFFF:
+        raise ValueError("byz_one is a probability in units of 2**-32: 0 .. 2**32 - 1")
+    return byz_one, (BYZ_RANDOM if byz_strategy is None else byz_strategy)
+
+
+def _faulty_array(N, faulty, byzantine, mode):
+    """The faulty bytes: 1 for a faulty node, and in mode 8 2 for a Byzantine one (an int entry of
+    `faulty` goes through as it is there, so that the library's validation can be reached)."""
+    raw = mode == BO_MODE_BYZ_TALLY
+    fl = [v if raw and type(v) is int else (1 if v else 0) for v in faulty]
+    if byzantine is not None:
+        if len(byzantine) != len(fl):
+            raise ValueError("byzantine holds one flag per node")
+        for i, v in enumerate(byzantine):
+            if v and fl[i]:
+                raise ValueError(f"node {i} is both faulty and Byzantine")
+            if v:
+                fl[i] = 2
+    return (ctypes.c_uint8 * max(1, N))(*fl)
+
+
 def _trials_cfg(N, F, faulty=None, *, seed=0, k_max=DEFAULT_K_MAX, initial_values=None, mode=BO_MODE_LOCKSTEP,
-                crash_at=None, crash_count=0, crash_window=0, crash_cut=0, crash_reach=None):
+                crash_at=None, crash_count=0, crash_window=0, crash_cut=0, crash_reach=None, byzantine=None,
+                byz_one=None, byz_strategy=None):
     """bo_trials_cfg for a shape, and the ctypes arrays it points into."""
     crash_cut = _cut_word(crash_cut, crash_reach)
+    crash_cut, crash_count = _byz_words(mode, crash_cut, crash_count, byzantine, byz_one, byz_strategy)
     if faulty is None:                       # start.ts:7-18 placement: the first F nodes
         faulty = [i < F for i in range(N)]
-    fl = (ctypes.c_uint8 * max(1, N))(*[1 if v else 0 for v in faulty])
+    fl = _faulty_array(N, faulty, byzantine, mode)
     if initial_values is None:
         init = (ctypes.c_int8 * max(1, N))()
         init_mode = BO_INIT_RANDOM
@@ -508,12 +549,15 @@ class TrialsPlan:
     def __init__(self, N: int, F: int, faulty: Sequence[bool] | None = None, *, seed: int = 0,
                  k_max: int = DEFAULT_K_MAX, initial_values: Sequence | None = None,
                  mode: int = BO_MODE_LOCKSTEP, crash_at: Sequence | None = None, crash_count: int = 0,
-                 crash_window: int = 0, crash_cut: int = 0, crash_reach: int | None = None):
+                 crash_window: int = 0, crash_cut: int = 0, crash_reach: int | None = None,
+                 byzantine: Sequence[bool] | None = None, byz_one: int | None = None,
+                 byz_strategy: int | None = None):
         self.N, self.F, self.k_max, self.seed = N, F, k_max, seed
         self.mode = mode
         self._cfg, self._keep = _trials_cfg(N, F, faulty, seed=seed, k_max=k_max, initial_values=initial_values,
                                             mode=mode, crash_at=crash_at, crash_count=crash_count,
-                                            crash_window=crash_window, crash_cut=crash_cut, crash_reach=crash_reach)
+                                            crash_window=crash_window, crash_cut=crash_cut, crash_reach=crash_reach,
+                                            byzantine=byzantine, byz_one=byz_one, byz_strategy=byz_strategy)
         h = ctypes.c_void_p()
         _check(lib().bo_plan_create(ctypes.byref(self._cfg), ctypes.byref(h)))
         self._h = h
@@ -563,10 +607,13 @@ class TrialsPlan:
 def run_trial_states(N: int, F: int, faulty: Sequence[bool], *, seed: int = 0, trial: int = 0,
                      k_max: int = DEFAULT_K_MAX, initial_values: Sequence | None = None,
                      mode: int = BO_MODE_LOCKSTEP, crash_at: Sequence | None = None, crash_count: int = 0,
-                     crash_window: int = 0, crash_cut: int = 0, crash_reach: int | None = None):
+                     crash_window: int = 0, crash_cut: int = 0, crash_reach: int | None = None,
+                     byzantine: Sequence[bool] | None = None, byz_one: int | None = None,
+                     byz_strategy: int | None = None):
     """Per-node final states of one trial: (rounds, [NodeState dict] * N)."""
     crash_cut = _cut_word(crash_cut, crash_reach)
-    fl = (ctypes.c_uint8 * max(1, N))(*[1 if v else 0 for v in faulty])
+    crash_cut, crash_count = _byz_words(mode, crash_cut, crash_count, byzantine, byz_one, byz_strategy)
+    fl = _faulty_array(N, faulty, byzantine, mode)
     if initial_values is None:
         init = (ctypes.c_int8 * max(1, N))()
         init_mode = BO_INIT_RANDOM
@@ -593,6 +640,16 @@ def tally_cdf(m: int, q: int, K: int) -> tuple[int, list[int]]:
     lo, n = ctypes.c_uint32(), ctypes.c_uint32()
     _check(lib().bo_tally_cdf(m, q, K, ctypes.byref(lo), thr, cap, ctypes.byref(n)))
     return int(lo.value), [int(v) for v in thr[:n.value]]
+
+
+def byz_cdf(b: int, byz_one: int) -> list[int]:
+    """The b thresholds of Binomial(b, byz_one / 2**32) that BO_MODE_BYZ_TALLY searches (bo_byz_cdf;
+    host only): a 64-bit draw u gives the number of Byzantine messages that carry 1 as
+    #{j : thresholds[j] <= u}."""
+    thr = (ctypes.c_uint64 * max(1, b))()
+    n = ctypes.c_uint32()
+    _check(lib().bo_byz_cdf(b, byz_one, thr, b, ctypes.byref(n)))
+    return [int(v) for v in thr[:n.value]]
 
 
 def kernel_version() -> str:

@@ -11,6 +11,8 @@
                                                                           # ... each crash cutting its last broadcast short
     python -m benor.cli trials --N 1024 --F 340 --mode subset --crashed 0 --crash-count 16 --crash-window 4 --crash-reach 0.5
                                                                           # ... or reaching each receiver with probability 1/2
+    python -m benor.cli trials --N 1024 --F 340 --mode byz --crashed 0 --byzantine 100 --byz-one 0.5 --byz-strategy random
+                                                                          # 100 Byzantine senders, a fair coin per receiver and step
     python -m benor.cli sweep --N 64,128,...,4096 --steps 32 --trials 2**30 --out sweep.csv
                                                                           # C5 phase diagram
     python -m benor.cli sweep --cells 4096:0,4096:1984 --per-cell 4793490  # two cells of it
@@ -90,7 +92,7 @@ def cmd_trials(a) -> int:
     mode = {"lockstep": benor.BO_MODE_LOCKSTEP, "random": benor.BO_MODE_RANDOM_DELIVERY,
             "tally": benor.BO_MODE_RANDOM_TALLY, "tally3": benor.BO_MODE_RANDOM_TALLY3,
             "crash": benor.BO_MODE_CRASH_TALLY, "partial": benor.BO_MODE_CRASH_PARTIAL,
-            "subset": benor.BO_MODE_CRASH_SUBSET}[a.mode]
+            "subset": benor.BO_MODE_CRASH_SUBSET, "byz": benor.BO_MODE_BYZ_TALLY}[a.mode]
     crashed = a.F if a.crashed is None else a.crashed            # the first f nodes (start.ts:7-18 placement)
     sched = {}
     if a.mode in ("crash", "partial", "subset"):                  # crashes during the run, in steps
@@ -120,6 +122,16 @@ def cmd_trials(a) -> int:
         sched["crash_reach"] = benor.reach_word(a.crash_reach)
     elif a.crash_reach is not None:
         raise SystemExit("--crash-reach needs --mode subset")
+    if a.mode == "byz":                                           # Byzantine senders
+        if not 0.0 <= a.byz_one <= 1.0:
+            raise SystemExit("--byz-one is a probability in [0, 1]")
+        if not 0 <= a.byzantine <= a.N - crashed:
+            raise SystemExit("--byzantine counts live nodes: 0 .. N - crashed")
+        sched = {"byzantine": [crashed <= i < crashed + a.byzantine for i in range(a.N)],   # the live nodes after the crashed
+                 "byz_one": benor.reach_word(a.byz_one),
+                 "byz_strategy": {"random": benor.BYZ_RANDOM, "oppose": benor.BYZ_OPPOSE}[a.byz_strategy]}
+    elif a.byzantine:
+        raise SystemExit("--byzantine needs --mode byz")
     plan = benor.TrialsPlan(a.N, a.F, [i < crashed for i in range(a.N)], seed=a.seed, k_max=a.k_max, mode=mode,
                             **sched)
     t0 = time.perf_counter()
@@ -135,6 +147,9 @@ def cmd_trials(a) -> int:
         row.update(crash_cut=a.crash_cut)
     if a.mode == "subset":
         row.update(crash_reach=a.crash_reach, crash_reach_word=sched["crash_reach"])
+    if a.mode == "byz":
+        row.update(byzantine=a.byzantine, byz_one=a.byz_one, byz_one_word=sched["byz_one"], byz_strategy=a.byz_strategy,
+                   kernel=benor.KERNEL_NAMES[plan.kernel])
     row["seconds"] = dt
     print(json.dumps(row))
     return 0
@@ -270,12 +285,13 @@ def main(argv=None) -> int:
     t.add_argument("--begin", type=int, default=0)
     t.add_argument("--seed", type=int, default=0x243F6A8885A308D3)
     t.add_argument("--k-max", type=int, default=16)
-    t.add_argument("--mode", choices=["lockstep", "random", "tally", "tally3", "crash", "partial", "subset"],
+    t.add_argument("--mode", choices=["lockstep", "random", "tally", "tally3", "crash", "partial", "subset", "byz"],
                    default="lockstep",
                    help="delivery model: lockstep, random (mask-level), tally (count-level random delivery: odd "
                         "quorum, no '?'), tally3 (count-level, any quorum), crash (tally3 with crashes during the run), "
                         "partial (crash with the crasher's last broadcast reaching a prefix of the receivers) or "
-                        "subset (... reaching each receiver independently with probability --crash-reach)")
+                        "subset (... reaching each receiver independently with probability --crash-reach); byz (tally3 "
+                        "with --byzantine senders that lie)")
     t.add_argument("--crashed", type=int, default=None,
                    help="crash the first f nodes (default F; random, tally, tally3 and crash take f <= F)")
     t.add_argument("--crash-count", type=int, default=0,
@@ -289,6 +305,15 @@ def main(argv=None) -> int:
     t.add_argument("--crash-reach", type=float, default=None,
                    help="subset: the probability in [0, 1] that a crasher's last message reaches a receiver (0: nobody, "
                         "as crash; 1: everybody), independently per trial, crasher and receiver")
+    t.add_argument("--byzantine", type=int, default=0,
+                   help="byz: the b live nodes after the --crashed ones are Byzantine (they send at every step and lie; "
+                        "crashed + b <= F)")
+    t.add_argument("--byz-one", type=float, default=0.5,
+                   help="byz: the probability in [0, 1] that a Byzantine message carries 1, independently per trial, "
+                        "sender, receiver and step")
+    t.add_argument("--byz-strategy", choices=["random", "oppose"], default="random",
+                   help="byz: random (each message by --byz-one) or oppose (every message carries the value fewer honest "
+                        "senders hold; --byz-one on a tie)")
     w = sub.add_parser("sweep", help="C5 decision-round phase diagram")
     w.add_argument("--N", default="64,128,256,512,1024,2048,4096")
     w.add_argument("--steps", type=int, default=32)

@@ -21,6 +21,7 @@ constexpr uint32_t kStreamWalk = 6u;       // BO_MODE_RANDOM_TALLY3: the smalles
 constexpr uint32_t kStreamSchedule = 7u;   // BO_MODE_CRASH_TALLY: a trial's random crash schedule (Floyd's algorithm)
 constexpr uint32_t kStreamCut = 8u;        // BO_MODE_CRASH_PARTIAL: a crasher's random cut, keyed by its compact index
 constexpr uint32_t kStreamReach = 9u;      // BO_MODE_CRASH_SUBSET: whether crasher p's last message reaches receiver c
+constexpr uint32_t kStreamLie = 10u;       // BO_MODE_BYZ_TALLY: a receiver's Binomial count of Byzantine messages that carry 1
 
 constexpr int kWavesPerBlock = 4;          // 256-thread workgroups, one trial per wave
 
@@ -66,14 +67,16 @@ struct KParams {
                             // 10: three-valued count-level random delivery (benor_tally3.hip),
                             // 11: the same with crashes during the run (benor_tally_crash.hip),
                             // 12: ... whose last broadcast reaches a prefix of the receivers (benor_tally_partial.hip),
-                            // 13: ... or a random subset of them, receiver by receiver (benor_tally_subset.hip)
+                            // 13: ... or a random subset of them, receiver by receiver (benor_tally_subset.hip),
+                            // 14: three-valued count-level random delivery with Byzantine senders (benor_tally_byz.hip)
   uint32_t base_variant;    // variant 7: the popcount kernel (1 W, 0 blocked) that serves the state
   uint32_t base_G;          //   launches and the deferred trials, and its G
   uint32_t mode;            // BO_MODE_LOCKSTEP / BO_MODE_RANDOM_DELIVERY / BO_MODE_EVENT / BO_MODE_RANDOM_TALLY /
                             // BO_MODE_RANDOM_TALLY3 / BO_MODE_CRASH_TALLY (a BO_MODE_RANDOM_TALLY3 plan inside
                             // mode 3's scope holds BO_MODE_RANDOM_TALLY here: it is that mode's plan; a
                             // BO_MODE_CRASH_TALLY, BO_MODE_CRASH_PARTIAL or BO_MODE_CRASH_SUBSET plan with an empty
-                            // schedule is BO_MODE_RANDOM_TALLY3's)
+                            // schedule is BO_MODE_RANDOM_TALLY3's, and so is a BO_MODE_BYZ_TALLY plan without a
+                            // Byzantine node)
   uint32_t q;               // quorum N - F (messages each receiver tallies per phase)
   uint32_t k_max;
   uint32_t init_mode;       // BO_INIT_RANDOM / BO_INIT_FIXED
@@ -170,6 +173,14 @@ struct KParams {
     uint32_t cr_cut;
     uint32_t cr_reach;
   };
+  // count-level random delivery with Byzantine senders (variant 14): m counts the live nodes, honest
+  // and Byzantine; byz_plane[W] holds the honest nodes' bits (the receivers), byz_n = b > 0 is the
+  // number of Byzantine senders, byz_thr[b] the thresholds of Binomial(b, byz_one / 2^32)
+  // (bo_byz_cdf; device), searched in LDS (byz_lds, a copy per workgroup behind the waves' regions)
+  // or where they lie in global memory.  tally_off / tally_thr hold the one table of (m, q)
+  const unsigned long long *byz_plane;
+  const unsigned long long *byz_thr;
+  uint32_t byz_n, byz_strategy, byz_one, byz_lds;
 };
 
 constexpr uint32_t kTimelineWords = 12;
@@ -239,6 +250,16 @@ hipError_t launch_tally_partial(const KParams &p, int grid_blocks, hipStream_t s
 uint32_t subset_wave_bytes(uint32_t W, uint32_t cap, uint32_t ncr, bool random);
 int subset_blocks_per_cu(const KParams &p);       // resident workgroups per CU (registers, LDS); 0 = unknown
 hipError_t launch_tally_subset(const KParams &p, int grid_blocks, hipStream_t stream);
+
+// Count-level random delivery with Byzantine senders (benor_tally_byz.hip): per-wave LDS
+// of a batch launch (four ballot planes and one staged row; a per-node-state launch adds
+// a decided plane by itself), and whether the workgroup keeps the b Binomial thresholds
+// in LDS behind the waves' regions (byz_thr_in_lds: when that costs no resident workgroup).
+uint32_t byz_wave_bytes(uint32_t W, uint32_t cap);
+uint32_t byz_state_bytes(uint32_t W);
+bool byz_thr_in_lds(uint32_t lds_bytes, uint32_t b);
+int byz_blocks_per_cu(const KParams &p);          // resident workgroups per CU (registers, LDS); 0 = unknown
+hipError_t launch_tally_byz(const KParams &p, int grid_blocks, hipStream_t stream);
 
 // Event level for kMaxEventN < N <= BO_MAX_N (benor_event_big.hip): one wave per trial.
 // The wave-per-trial event kernel keeps its message pool in LDS when it is at

@@ -687,6 +687,20 @@ void plan_geometry(KParams &p) {
     p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
     return;
   }
+  if (p.mode == BO_MODE_BYZ_TALLY) {
+    // three-valued count-level random delivery with Byzantine senders (benor_tally_byz.hip): mode 4's
+    // table and row region; the Binomial thresholds ride in LDS when that costs no resident workgroup
+    p.G = 1;
+    p.nblocks = W;
+    p.variant = 14u;
+    const uint32_t e = p.m - p.q;
+    p.tally_cap = p.q <= e ? p.q : e;
+    p.wave_bytes = (byz_wave_bytes(W, p.tally_cap) + 15u) & ~15u;
+    p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
+    p.byz_lds = byz_thr_in_lds(p.lds_bytes, p.byz_n) ? 1u : 0u;
+    if (p.byz_lds) p.lds_bytes += 8u * p.byz_n;
+    return;
+  }
   if (p.m <= kMaxLaneM) {                           // lane kernel: one trial per lane
     const uint32_t M1 = p.m - p.init_q;
     const bool odd = (p.m & 1u) && (M1 & 1u);        // every vote count odd: no tie, no coin
@@ -823,6 +837,7 @@ hipError_t launch_lockstep(const KParams &p, int grid, hipStream_t s) {
   if (p.variant == 11) return launch_tally_crash(p, grid, s);
   if (p.variant == 12) return launch_tally_partial(p, grid, s);
   if (p.variant == 13) return launch_tally_subset(p, grid, s);
+  if (p.variant == 14) return launch_tally_byz(p, grid, s);
   if (p.variant == 2 && p.rd_a) return launch_random_bern(p, grid, s);
   if (p.variant == 2) {                      // Floyd sampler
     if (p.lds_bytes > 64u * 1024u) {
@@ -947,6 +962,10 @@ int lockstep_grid(const KParams &p, int device) {
   }
   if (p.variant == 13) {                     // ... that reach a random subset
     const uint64_t fit = (uint64_t)subset_blocks_per_cu(p);
+    if (fit >= 1u && fit < per_cu) per_cu = fit;
+  }
+  if (p.variant == 14) {                     // ... and its form with Byzantine senders
+    const uint64_t fit = (uint64_t)byz_blocks_per_cu(p);
     if (fit >= 1u && fit < per_cu) per_cu = fit;
   }
   // Lane kernel: a short launch spread over every wave slot (~2 trials per

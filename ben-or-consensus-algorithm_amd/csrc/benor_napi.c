@@ -587,12 +587,14 @@ static napi_value run_trials(napi_env env, napi_callback_info info) {
     j->trial_begin = prop_u64(env, o, "trialBegin", 0);
     j->trial_count = prop_u64(env, o, "trialCount", 1);
     uint32_t mode = BO_MODE_LOCKSTEP;
-    prop_u32(env, o, "mode", BO_MODE_LOCKSTEP, &mode);          /* 0 lockstep, 1 random delivery, 2 event, 3 random tally, 4 random tally3, 5 crash tally, 6 crash partial, 7 crash subset */
+    prop_u32(env, o, "mode", BO_MODE_LOCKSTEP, &mode);          /* 0 lockstep, 1 random delivery, 2 event, 3 random tally, 4 random tally3, 5 crash tally, 6 crash partial, 7 crash subset, 8 byz tally */
     j->cfg.mode = mode;
     prop_u32(env, o, "crashCount", 0, &j->cfg.crash_count);
     prop_u32(env, o, "crashWindow", 0, &j->cfg.crash_window);
     prop_u32(env, o, "crashCut", 0, &j->cfg.crash_cut);          /* mode 6: 0 .. N - f, or BO_CUT_RANDOM */
     prop_u32(env, o, "crashReach", j->cfg.crash_cut, &j->cfg.crash_reach);   /* mode 7: the same word, a probability in units of 2^-32 */
+    prop_u32(env, o, "byzOne", j->cfg.crash_cut, &j->cfg.byz_one);           /* mode 8: the same word, the probability that a Byzantine message carries 1 */
+    prop_u32(env, o, "byzStrategy", j->cfg.crash_count, &j->cfg.byz_strategy);   /* mode 8: the crash_count word, BO_BYZ_RANDOM / BO_BYZ_OPPOSE */
     const uint32_t N = j->cfg.N;
     j->faulty = (uint8_t *)calloc(N + 1, 1);
     j->init = (int8_t *)calloc(N + 1, 1);
@@ -612,6 +614,19 @@ static napi_value run_trials(napi_env env, napi_callback_info info) {
             }
     } else {
         for (uint32_t i = 0; i < N && i < j->cfg.F; ++i) j->faulty[i] = 1;   /* start.ts:7-18 placement */
+    }
+    napi_has_named_property(env, o, "byzantineList", &has);
+    if (has && mode == BO_MODE_BYZ_TALLY) {                      /* mode 8: a live node that lies; faulty[i] = 2 */
+        napi_get_named_property(env, o, "byzantineList", &arr);
+        uint32_t n = 0;
+        if (read_array(env, arr, &n))
+            for (uint32_t i = 0; i < n && i < N; ++i) {
+                napi_value e;
+                bool b = false;
+                napi_get_element(env, arr, i, &e);
+                napi_get_value_bool(env, e, &b);
+                if (b) j->faulty[i] = j->faulty[i] ? 3 : 2;      /* crashed and Byzantine: the library rejects 3 */
+            }
     }
     napi_has_named_property(env, o, "initialValues", &has);
     j->cfg.init_mode = has ? BO_INIT_FIXED : BO_INIT_RANDOM;

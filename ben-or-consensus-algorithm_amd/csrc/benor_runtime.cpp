@@ -500,6 +500,42 @@ int bo_tally_cdf(uint32_t m, uint32_t q, uint32_t K, uint32_t *lo_out, uint64_t 
   return BO_OK;
 }
 
+// ------------------------------------------------- BYZ_TALLY thresholds (host)
+// The b thresholds of Binomial(b, p), p = one / 2^32 (exact in double, as 1 - p is):
+// T[j] = min(2^64 - 1, floor(CDF(j) * 2^64)), j = 0..b-1.  tally_row's construction:
+// weights by the ratio recurrence pmf(j + 1) / pmf(j) = (b - j) p / ((j + 1)(1 - p))
+// outward from the mode (weight 1), then running sums over their total.
+static void byz_row(uint32_t b, uint32_t one, std::vector<uint64_t> &thr) {
+  thr.clear();
+  if (b == 0u) return;
+  const double p = std::ldexp((double)one, -32), np = 1.0 - p;
+  uint32_t mode = (uint32_t)(((uint64_t)b + 1u) * one >> 32);   // floor((b + 1) p) <= b
+  std::vector<double> w(b + 1u, 0.0);
+  auto ratio = [&](uint32_t j) { return ((double)(b - j) * p) / ((double)(j + 1u) * np); };   // 0 <= j < b
+  w[mode] = 1.0;
+  for (uint32_t j = mode; j < b; ++j) w[j + 1u] = w[j] * ratio(j);
+  for (uint32_t j = mode; j > 0u; --j) w[j - 1u] = w[j] / ratio(j - 1u);   // mode > 0 only if p > 0
+  double total = 0.0;
+  for (uint32_t j = 0; j <= b; ++j) total += w[j];
+  double run = 0.0;
+  for (uint32_t j = 0; j < b; ++j) {
+    run += w[j];
+    const double t = std::ldexp(run / total, 64);
+    thr.push_back(t >= 18446744073709551616.0 ? ~0ull : (uint64_t)t);
+  }
+}
+
+int bo_byz_cdf(uint32_t b, uint32_t byz_one, uint64_t *thr_out, uint32_t cap, uint32_t *n_out) {
+  if (!n_out) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (b > BO_MAX_N) return fail(BO_ERR_INVALID_ARGUMENT, "bo_byz_cdf needs b <= 4096");
+  if (b > cap || (b && !thr_out)) return fail(BO_ERR_INVALID_ARGUMENT, "bo_byz_cdf: thr_out is too short for b thresholds");
+  std::vector<uint64_t> thr;
+  byz_row(b, byz_one, thr);
+  *n_out = b;
+  if (b) std::memcpy(thr_out, thr.data(), sizeof(uint64_t) * b);
+  return BO_OK;
+}
+
 // -------------------------------------------------------------- batch API
 // Validation and kernel planning of a trial configuration, host only: the
 // live-node map, the fixed-init plane and the KParams shape (no device fields).
@@ -507,9 +543,12 @@ int bo_tally_cdf(uint32_t m, uint32_t q, uint32_t K, uint32_t *lo_out, uint64_t 
 // (step << 12 | compact index, ascending, steps below 2 k_max: no run reaches a
 // later one) and, per number of crashes so far d = 0 .. kp.cr_n, whether the
 // live count m0 - d is reachable and so needs a table.
+// BO_MODE_BYZ_TALLY with Byzantine nodes: the honest plane, bit c of word c / 64 set for
+// an honest compact index c.
 struct CrashPlan {
   std::vector<uint32_t> list;
   std::vector<uint8_t> reach;
+  std::vector<uint64_t> honest;
 };
 
 // Thresholds of the table of (m, q): sum over K = 0..m of min(K, q) - max(0, q - (m - K)).
@@ -526,27 +565,43 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   if (cfg->k_max < 1 || cfg->k_max > BO_MAX_K) return fail(BO_ERR_INVALID_ARGUMENT, "k_max must be in [1, 1024]");
   if (cfg->mode != BO_MODE_LOCKSTEP && cfg->mode != BO_MODE_RANDOM_DELIVERY && cfg->mode != BO_MODE_EVENT &&
       cfg->mode != BO_MODE_RANDOM_TALLY && cfg->mode != BO_MODE_RANDOM_TALLY3 && cfg->mode != BO_MODE_CRASH_TALLY &&
-      cfg->mode != BO_MODE_CRASH_PARTIAL && cfg->mode != BO_MODE_CRASH_SUBSET)
+      cfg->mode != BO_MODE_CRASH_PARTIAL && cfg->mode != BO_MODE_CRASH_SUBSET && cfg->mode != BO_MODE_BYZ_TALLY)
     return fail(BO_ERR_UNSUPPORTED, "unknown delivery mode");
+  const bool byz_mode = cfg->mode == BO_MODE_BYZ_TALLY;
   const bool crash_mode = cfg->mode == BO_MODE_CRASH_TALLY || cfg->mode == BO_MODE_CRASH_PARTIAL ||
                           cfg->mode == BO_MODE_CRASH_SUBSET;
   const bool random_mode = cfg->mode == BO_MODE_RANDOM_DELIVERY || cfg->mode == BO_MODE_RANDOM_TALLY ||
-                           cfg->mode == BO_MODE_RANDOM_TALLY3 || crash_mode;
+                           cfg->mode == BO_MODE_RANDOM_TALLY3 || crash_mode || byz_mode;
   if (cfg->init_mode != BO_INIT_RANDOM && cfg->init_mode != BO_INIT_FIXED)
     return fail(BO_ERR_INVALID_ARGUMENT, "unknown init_mode");
   if (!cfg->faulty) return fail(BO_ERR_INVALID_ARGUMENT, "faulty is NULL");
   if (cfg->init_mode == BO_INIT_FIXED && !cfg->init) return fail(BO_ERR_INVALID_ARGUMENT, "init is NULL");
-  uint32_t f = 0;
-  for (uint32_t i = 0; i < cfg->N; ++i) f += cfg->faulty[i] ? 1u : 0u;
+  // BO_MODE_BYZ_TALLY alone reads the value of a faulty entry: 1 crashed from the start, 2
+  // Byzantine (live: it sends); every other mode reads non-zero as faulty.
+  if (byz_mode) {
+    for (uint32_t i = 0; i < cfg->N; ++i)
+      if (cfg->faulty[i] > 2u)
+        return fail(BO_ERR_INVALID_ARGUMENT, "BO_MODE_BYZ_TALLY: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)");
+    if (cfg->byz_strategy != BO_BYZ_RANDOM && cfg->byz_strategy != BO_BYZ_OPPOSE)
+      return fail(BO_ERR_INVALID_ARGUMENT, "byz_strategy must be BO_BYZ_RANDOM or BO_BYZ_OPPOSE");
+  }
+  const auto crashed = [&](uint32_t i) { return byz_mode ? cfg->faulty[i] == 1u : cfg->faulty[i] != 0u; };
+  uint32_t f = 0, nbyz = 0;
+  for (uint32_t i = 0; i < cfg->N; ++i) {
+    f += crashed(i) ? 1u : 0u;
+    nbyz += byz_mode && cfg->faulty[i] == 2u ? 1u : 0u;
+  }
   // Lockstep = the reference's admissible inputs: exactly F crash faults
   // (launchNodes.ts:12-13).  Random delivery admits f <= F.
   if (!random_mode && f != cfg->F)
     return fail(BO_ERR_FAULTY_COUNT, "faultyList doesnt have F faulties");
   if (random_mode && f > cfg->F)
     return fail(BO_ERR_FAULTY_COUNT, "random delivery needs at most F crash-faulty nodes");
+  if (f + nbyz > cfg->F)
+    return fail(BO_ERR_FAULTY_COUNT, "BO_MODE_BYZ_TALLY needs at most F nodes crashed or Byzantine");
   live.clear();
   for (uint32_t i = 0; i < cfg->N; ++i)
-    if (!cfg->faulty[i]) live.push_back(i);
+    if (!crashed(i)) live.push_back(i);
   const uint32_t m = (uint32_t)live.size();
   // Crashes during the run (BO_MODE_CRASH_TALLY, BO_MODE_CRASH_PARTIAL, BO_MODE_CRASH_SUBSET): with
   // the initially faulty nodes at most F, so every step has a quorum of live senders.
@@ -580,14 +635,16 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   kp.seed = cfg->seed;
   kp.mode = cfg->mode;
   kp.q = cfg->N - cfg->F;
-  kp.crash_count = cfg->crash_count;
+  kp.crash_count = byz_mode ? 0u : cfg->crash_count;   // (BO_MODE_BYZ_TALLY reads the word as byz_strategy)
   kp.crash_window = cfg->crash_window;
   if (cfg->mode == BO_MODE_EVENT && !cfg->crash_at && cfg->crash_count > 0 && cfg->crash_window > 0)
     kp.ev_rstops = std::min<uint32_t>(cfg->crash_count, m);   // per-trial random /stop schedule
   kp.live = live_run && cfg->mode == BO_MODE_EVENT ? 1u : 0u;
   for (uint32_t i = 0; i < cfg->N && i < 4u * 64u; ++i)
     if (cfg->faulty[i]) kp.faulty_mask[i >> 6] |= 1ull << (i & 63u);
-  if (m == 0) {
+  if (m == 0 || m == nbyz) {                        // no live node, or (N = F only) no honest one: bin[2], no kernel
+    kp.m = 0;
+    kp.W = 0;
     kp.hist_len = bo_hist_len(cfg->k_max);
     return BO_OK;
   }
@@ -615,6 +672,18 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   // (its kernel, its results bit for bit); outside, benor_tally3.hip.
   // A BO_MODE_CRASH_TALLY plan with an empty schedule is the three-valued mode's plan.
   if (crash_mode && n_crash == 0) kp.mode = BO_MODE_RANDOM_TALLY3;
+  // ... and so is a BO_MODE_BYZ_TALLY plan without a Byzantine node, at every byz_one and strategy.
+  if (byz_mode && nbyz == 0) kp.mode = BO_MODE_RANDOM_TALLY3;
+  if (kp.mode == BO_MODE_BYZ_TALLY) {
+    kp.byz_n = nbyz;
+    kp.byz_strategy = cfg->byz_strategy;
+    kp.byz_one = cfg->byz_one;
+    if (crash) {
+      crash->honest.assign(kp.W, 0ull);
+      for (uint32_t c = 0; c < m; ++c)
+        if (cfg->faulty[live[c]] == 0u) crash->honest[c >> 6] |= 1ull << (c & 63u);
+    }
+  }
   if (kp.mode == BO_MODE_RANDOM_TALLY3 && (kp.q & 1u) && !kp.init_q) kp.mode = BO_MODE_RANDOM_TALLY;
   if (kp.mode == BO_MODE_CRASH_TALLY || kp.mode == BO_MODE_CRASH_PARTIAL || kp.mode == BO_MODE_CRASH_SUBSET) {
     CrashPlan local;
@@ -778,7 +847,8 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
       kp.init_x = pl->d_init_x;
       kp.crash_at = pl->d_crash;
       kp.scratch = pl->d_scratch;
-    } else if (kp.variant == 9 || kp.variant == 10) {   // BO_MODE_RANDOM_TALLY, BO_MODE_RANDOM_TALLY3
+    } else if (kp.variant == 9 || kp.variant == 10 || kp.variant == 14) {
+      // BO_MODE_RANDOM_TALLY, BO_MODE_RANDOM_TALLY3, BO_MODE_BYZ_TALLY:
       // the whole table HG(m, K, q), K = 0..m: at most ~3.7 * 10^6 thresholds (30 MB) at m = 4096
       std::vector<uint32_t> off(m + 2u, 0u);
       std::vector<uint64_t> thr;
@@ -789,13 +859,28 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
       }
       off[m + 1u] = (uint32_t)thr.size();
       const size_t off_bytes = (sizeof(uint32_t) * off.size() + 7u) & ~size_t(7);
-      e = hipMalloc(&pl->d_tally, off_bytes + sizeof(uint64_t) * std::max<size_t>(thr.size(), 1u));
+      const size_t thr_bytes = sizeof(uint64_t) * std::max<size_t>(thr.size(), 1u);
+      // ... and, with Byzantine senders, the Binomial thresholds and the honest plane behind it
+      std::vector<uint64_t> lie;
+      if (kp.variant == 14) byz_row(kp.byz_n, kp.byz_one, lie);
+      const size_t lie_bytes = sizeof(uint64_t) * lie.size();
+      const size_t plane_bytes = kp.variant == 14 ? sizeof(uint64_t) * crash.honest.size() : 0u;
+      e = hipMalloc(&pl->d_tally, off_bytes + thr_bytes + lie_bytes + plane_bytes);
       if (e == hipSuccess) e = hipMemcpy(pl->d_tally, off.data(), sizeof(uint32_t) * off.size(), hipMemcpyHostToDevice);
       if (e == hipSuccess && !thr.empty())
         e = hipMemcpy(pl->d_tally + off_bytes, thr.data(), sizeof(uint64_t) * thr.size(), hipMemcpyHostToDevice);
+      if (e == hipSuccess && lie_bytes)
+        e = hipMemcpy(pl->d_tally + off_bytes + thr_bytes, lie.data(), lie_bytes, hipMemcpyHostToDevice);
+      if (e == hipSuccess && plane_bytes)
+        e = hipMemcpy(pl->d_tally + off_bytes + thr_bytes + lie_bytes, crash.honest.data(), plane_bytes,
+                      hipMemcpyHostToDevice);
       if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "tally table upload"); }
       kp.tally_off = reinterpret_cast<const uint32_t *>(pl->d_tally);
       kp.tally_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + off_bytes);
+      if (kp.variant == 14) {
+        kp.byz_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + off_bytes + thr_bytes);
+        kp.byz_plane = reinterpret_cast<const unsigned long long *>(pl->d_tally + off_bytes + thr_bytes + lie_bytes);
+      }
     } else if (kp.variant == 11 || kp.variant == 12 || kp.variant == 13) {
       // BO_MODE_CRASH_TALLY, BO_MODE_CRASH_PARTIAL, BO_MODE_CRASH_SUBSET: one table per reachable live count (pool
       // size), and their directory
@@ -878,7 +963,8 @@ uint64_t bo_plan_popc_words_per_node_round(const bo_plan *pl) {
   uint64_t counts = 4ull;
   if (pl->kp.mode != BO_MODE_RANDOM_DELIVERY && pl->kp.mode != BO_MODE_RANDOM_TALLY &&
       pl->kp.mode != BO_MODE_RANDOM_TALLY3 && pl->kp.mode != BO_MODE_CRASH_TALLY &&
-      pl->kp.mode != BO_MODE_CRASH_PARTIAL && pl->kp.mode != BO_MODE_CRASH_SUBSET)
+      pl->kp.mode != BO_MODE_CRASH_PARTIAL && pl->kp.mode != BO_MODE_CRASH_SUBSET &&
+      pl->kp.mode != BO_MODE_BYZ_TALLY)
     counts = ((pl->kp.m - pl->kp.init_q) & 1u) ? 2ull : 3ull;
   return counts * ((pl->kp.m + 31ull) / 32ull);
 }
@@ -1199,7 +1285,9 @@ void initial_states(const bo_trials_cfg *cfg, std::vector<bo_node_state> &st) {
   st.resize(cfg->N);
   for (uint32_t i = 0; i < cfg->N; ++i) {
     const bool f = cfg->faulty[i] != 0;
-    st[i].killed = f ? 1 : 0;
+    // (BO_MODE_BYZ_TALLY: a Byzantine node is alive and has no protocol state; no kernel writes its entry)
+    const bool byz = cfg->mode == BO_MODE_BYZ_TALLY && cfg->faulty[i] == 2u;
+    st[i].killed = f && !byz ? 1 : 0;
     st[i].x = f ? -1 : (cfg->init_mode == BO_INIT_FIXED ? cfg->init[i] : -1);
     st[i].decided = f ? -1 : 0;
     st[i].pad = 0;

@@ -1,0 +1,358 @@
+// benor_tally_byz.hip -- three-valued count-level random delivery with Byzantine
+// senders (BO_MODE_BYZ_TALLY with b > 0 Byzantine nodes).
+//
+// The model is benor_tally3.hip's with b of the m live nodes Byzantine: they send
+// at every step and lie, they never receive.  The h = m - b honest nodes run the
+// rule; honest receiver c draws q messages from all m senders.  With (H0, H1, Hq)
+// the class sizes over the honest senders and B1 of the b Byzantine messages that
+// could reach c carrying a 1, its (c0, c1) is draw3 among m senders with the class
+// sizes (H0 + b - B1, H1 + B1, Hq).  B1 is
+//   BO_BYZ_RANDOM: Binomial(b, byz_one / 2^32) per (receiver, round, phase):
+//     #{ j : thr[j] <= u }, thr the plan's b thresholds (bo_byz_cdf), u from the
+//     Philox block {trial_lo, trial_hi, c, (r - 1) | 10 << 24} (stream 10; R-phase
+//     out[1] << 32 | out[0], P-phase out[3] << 32 | out[2]); 0 at byz_one = 0 and b
+//     at UINT32_MAX without a draw;
+//   BO_BYZ_OPPOSE: 0 if H1 > H0, b if H0 > H1, for every receiver; BO_BYZ_RANDOM's
+//     step on H0 == H1.
+//
+// One wave = one trial, lane l of receiver group j = compact index 64 j + l over
+// the m live nodes, as in benor_tally_crash.hip, whose helpers this kernel runs
+// on.  Its alive plane is here the honest plane HP, constant per plan: class
+// sizes are popcounts of the x and proposal planes ANDed with it, a group without
+// an honest lane draws nothing, and a Byzantine lane never writes a plane bit.  A
+// step is one of two kinds, wave-uniformly:
+//   * every receiver hears the same Byzantine messages (OPPOSE off a tie, byz_one 0
+//     or UINT32_MAX): the phase is set up once with its row staged in LDS and the
+//     honest lanes draw from it (phase_setup and draw3, mode 4's step with shifted
+//     class sizes);
+//   * each receiver has a B1 of its own: one stream-10 block per lane next to the
+//     stream-5 block, a binary search of the Binomial thresholds, and one per-lane
+//     draw from the lane's own row of the (m, q) table in global memory
+//     (benor_tally_subset.hip's draw3_own with one table and no directory).
+//     Neighbouring lanes' B1 differ by O(sqrt b), so the rows they touch lie close.
+// The thresholds, 8 b <= 32 KiB shared by every trial, are copied into LDS once
+// per workgroup, behind the four waves' regions, when that costs no resident
+// workgroup (byz_thr_in_lds); otherwise they are searched in global memory.
+//
+// Per-wave LDS: the planes HP, X1, P1, P0 of W words (X0, read only by round 1's
+// class sizes, lies in P0's words), a decided plane in a per-node-state launch,
+// and the row region.  Histogram and the state launch are benor_tally_crash.hip's
+// with the honest nodes in the place of the alive ones; a Byzantine node's state is
+// not written (the host reports it).  No floating point runs on the device, and no
+// launch leaves overflow or deferral state.
+#include "benor_tally_crash.h"
+
+namespace benor {
+
+namespace {
+
+constexpr uint32_t kByzCertain = 0xFFFFFFFFu;      // KParams::byz_one: every Byzantine message carries 1
+constexpr uint32_t kByzWgPerCu = 6u;               // resident workgroups the registers allow (__launch_bounds__ below)
+
+// #{ j < n : thr[j] <= u } in global memory: row_count's search from the largest power of
+// two not above n (a probe at or beyond n fails).
+__device__ __forceinline__ uint32_t count_global(const unsigned long long *__restrict__ thr, uint32_t n, uint64_t u) {
+  uint32_t pos = 0u;
+  for (uint32_t st = 1u << (31u - (uint32_t)__builtin_clz(n | 1u)); st != 0u; st >>= 1) {
+    const uint32_t i = pos + st - 1u;
+    if (i < n && thr[i] <= u) pos += st;
+  }
+  return pos;
+}
+
+// draw3 for a lane with class sizes of its own among the m senders: phase_setup's class
+// choice, row_count and draw3's walk with every quantity per lane, the row searched where
+// it lies in global memory (the plan's one table).  K0 + K1 <= m; a lane that is not
+// `active` loads nothing and its result is not used.
+__device__ __forceinline__ void draw3_lane(const KParams &p, uint32_t K0, uint32_t K1, uint32_t k0, uint32_t k1,
+                                           uint32_t tlo, uint32_t thi, uint32_t c, uint32_t r, uint32_t phase,
+                                           uint64_t u, bool active, uint32_t &c0, uint32_t &c1) {
+  const uint32_t m = p.m, q = p.q, Kq = m - K0 - K1;
+  uint32_t sel, KS, KA;
+  if (Kq <= K0 && Kq <= K1) sel = 0u, KS = Kq, KA = K1;
+  else if (K0 <= K1) sel = 1u, KS = K0, KA = K1;
+  else sel = 2u, KS = K1, KA = K0;
+  uint32_t cA = KA + q > m ? KA + q - m : 0u;
+  if (active && KA != 0u && KA != m && m != q) {   // else the row is a point
+    const uint32_t o = p.tally_off[KA];
+    uint32_t n = p.tally_off[KA + 1u] - o;
+    if (n > p.tally_cap) n = p.tally_cap;
+    cA += count_global(p.tally_thr + o, n, u);
+  }
+  if (!active) KS = 0u;
+  uint32_t cS = 0u;
+  if (m == q) {
+    cS = KS;                                       // every sender is in the inbox
+  } else {
+    const uint32_t slots = q - cA;                 // inbox slots left to the senders outside A
+    const uint32_t dtop = m - KA;                  // ... of which there are this many (>= slots, >= KS)
+    const uint32_t c3 = (r - 1u) | (phase << 16) | (kStreamWalk << 24);
+    uint32_t i = 0;
+    const auto word = [&](uint32_t w) {
+      if (i < KS) {
+        const uint32_t d = dtop - i;               // member i's denominator, >= 1
+        const uint64_t mm = (uint64_t)w * d;
+        const uint32_t l = (uint32_t)mm;
+        bool ok = true;
+        if (l < d) ok = l >= (0u - d) % d;
+        if (ok) {
+          if ((uint32_t)(mm >> 32) < slots - cS) ++cS;
+          ++i;
+        }
+      }
+    };
+    for (uint32_t blk = 0; __any(i < KS); ++blk) {
+      const uint4 b = philox4x32_10(k0, k1, make_uint4(tlo, thi, c | (blk << 12), c3));
+      word(b.x), word(b.y), word(b.z), word(b.w);
+    }
+  }
+  const uint32_t cT = q - cA - cS;
+  c1 = sel == 2u ? cS : cA;
+  c0 = sel == 0u ? cT : (sel == 1u ? cS : cA);
+}
+
+// (six waves per SIMD: one more than benor_tally_crash.hip, there is no schedule and no alive plane to maintain)
+__global__ void __launch_bounds__(256, 6) benor_tally_byz_kernel(KParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wv = threadIdx.x >> 6;
+  const uint32_t m = p.m, F = p.F, W = p.W, q = p.q, nb = p.byz_n;
+  const uint32_t WP = (W + 1u) & ~1u;
+
+  uint32_t *lhist = reinterpret_cast<uint32_t *>(smem);
+  const bool states = p.node_out != nullptr;       // a state launch: a DEC plane of its own
+  uint64_t *HP = reinterpret_cast<uint64_t *>(smem + p.hist_bytes + wv * p.wave_bytes);   // [W] honest (constant)
+  uint64_t *X1 = HP + WP;                                                                 // [W] x = 1
+  uint64_t *P1 = X1 + WP, *P0 = P1 + WP;                                                  // [W] proposals 1, 0
+  uint64_t *X0 = P0;                                                                      // [W] x = 0 (round 1)
+  uint64_t *DEC = P0 + WP;                                                                // [W] decided (state launch)
+  uint64_t *row = HP + (states ? 5u : 4u) * WP;                                           // [tally_cap] thresholds
+  uint64_t *BT = reinterpret_cast<uint64_t *>(smem + p.hist_bytes + kWavesPerBlock * p.wave_bytes);   // [b] (byz_lds)
+  const bool in_lds = p.byz_lds != 0u;
+  const uint32_t bsteps = 32u - (uint32_t)__builtin_clz(nb | 1u);
+
+  for (uint32_t i = threadIdx.x; i < p.hist_len; i += blockDim.x) lhist[i] = 0u;
+  if (in_lds)
+    for (uint32_t i = threadIdx.x; i < nb; i += blockDim.x) BT[i] = p.byz_thr[i];
+  for (uint32_t w = lane; w < W; w += 64u) HP[w] = p.byz_plane[w];
+  __syncthreads();
+
+  uint32_t h = 0u;                                 // honest nodes
+  for (uint32_t j = 0; j < W; ++j) h += (uint32_t)__builtin_popcountll(HP[j]);
+  h = uni(h);
+
+  Table tb;                                        // the plan's one table
+  tb.m = m;
+  tb.off = p.tally_off;
+  tb.thr = p.tally_thr;
+
+  const uint32_t k0 = (uint32_t)p.seed, k1 = (uint32_t)(p.seed >> 32);
+  const uint64_t waves_total = (uint64_t)gridDim.x * kWavesPerBlock;
+
+  // What the Byzantine senders say at a step with honest class sizes (H0, H1): true if every
+  // receiver has a B1 of its own, else B1u for all of them.
+  uint32_t B1u = 0u;
+  const auto per_lane_step = [&](uint32_t H0, uint32_t H1) {
+    if (p.byz_strategy == BO_BYZ_OPPOSE && H0 != H1) {
+      B1u = H0 > H1 ? nb : 0u;
+      return false;
+    }
+    B1u = p.byz_one == kByzCertain ? nb : 0u;
+    return p.byz_one != 0u && p.byz_one != kByzCertain;
+  };
+  // Receiver c's B1 from its stream-10 uniform.
+  const auto lies = [&](uint64_t u) {
+    return in_lds ? row_count(BT, nb, bsteps, u) : count_global(p.byz_thr, nb, u);
+  };
+
+  for (uint64_t t = (uint64_t)blockIdx.x * kWavesPerBlock + wv; t < p.trial_count; t += waves_total) {
+    const uint64_t trial = p.trial_begin + t;
+    const uint32_t tlo = uni((uint32_t)trial), thi = uni((uint32_t)(trial >> 32));
+    __builtin_amdgcn_wave_barrier();               // the previous trial's state reads are done
+    if (p.init_mode == BO_INIT_RANDOM) {           // /start (node.ts:167-188): stream 1, as every batch mode
+      const uint32_t nph = (W + 1u) >> 1;
+      if (lane < nph) {
+        uint4 r;
+        if (m <= 32u) r = make_uint4(init_word_small(k0, k1, trial), 0u, 0u, 0u);   // shared block (m <= 32)
+        else r = philox4x32_10(k0, k1, make_uint4(tlo, thi, lane, kStreamInit << 24));
+        const uint32_t w0 = 2u * lane, w1 = w0 + 1u;
+        const uint64_t g0 = group_mask(w0, m), a0 = ((uint64_t)r.y << 32 | r.x) & g0;
+        X1[w0] = a0, X0[w0] = g0 & ~a0;
+        if (w1 < W) {
+          const uint64_t g1 = group_mask(w1, m), a1 = ((uint64_t)r.w << 32 | r.z) & g1;
+          X1[w1] = a1, X0[w1] = g1 & ~a1;
+        }
+      }
+    } else {
+      for (uint32_t w = lane; w < W; w += 64u) {
+        const uint4 rc = p.init_plane[w];
+        X0[w] = (uint64_t)rc.y << 32 | rc.x;
+        X1[w] = (uint64_t)rc.w << 32 | rc.z;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+
+    uint64_t dec = 0ull;                           // bit j: node 64 j + lane has decided (sticky)
+    uint32_t R = 0;
+    bool all_dec = false;
+    for (uint32_t r = 1; r <= p.k_max; ++r) {
+      // ---- R-phase ("proposal phase", node.ts:46-82)
+      uint32_t H0 = 0, H1 = 0;
+      for (uint32_t j = 0; j < W; ++j) {
+        const uint64_t hp = HP[j];
+        if (r == 1u) H0 += (uint32_t)__builtin_popcountll(X0[j] & hp);
+        H1 += (uint32_t)__builtin_popcountll(X1[j] & hp);
+      }
+      H1 = uni(H1);
+      H0 = r == 1u ? uni(H0) : h - H1;             // after a P-phase every honest x is binary
+      bool own = per_lane_step(H0, H1);
+      PhaseC ph;
+      ph.sel = 0u, ph.KA = 0u, ph.KS = 0u, ph.lo = 0u, ph.n = 0u, ph.steps = 0u;
+      if (!own) ph = phase_setup(row, p, tb, H0 + nb - B1u, H1 + B1u, h - H0 - H1, lane);
+      else __builtin_amdgcn_wave_barrier();        // the class sizes are read before P0 takes X0's words
+      for (uint32_t j = 0; j < W; ++j) {
+        const uint64_t hp = uni64(HP[j]);
+        uint64_t p0 = 0ull, p1 = 0ull;
+        if (hp) {                                  // a group without an honest lane draws nothing
+          const uint32_t c = j * 64u + lane;
+          // the round's block of receiver c: u_R = out[1] << 32 | out[0], u_P = out[3] << 32 | out[2]
+          const uint4 b = philox4x32_10(k0, k1, make_uint4(tlo, thi, c, (r - 1u) | (kStreamTally << 24)));
+          const uint64_t u = (uint64_t)b.y << 32 | b.x;
+          uint32_t c0, c1;
+          if (!own) {
+            draw3(row, ph, m, q, k0, k1, tlo, thi, c, r, 0u, u, c0, c1);
+          } else {
+            const uint4 l = philox4x32_10(k0, k1, make_uint4(tlo, thi, c, (r - 1u) | (kStreamLie << 24)));
+            const uint32_t B1 = lies((uint64_t)l.y << 32 | l.x);
+            draw3_lane(p, H0 + nb - B1, H1 + B1, k0, k1, tlo, thi, c, r, 0u, u, (hp >> lane) & 1ull, c0, c1);
+          }
+          p0 = ballot(c0 > c1) & hp;
+          p1 = ballot(c1 > c0) & hp;
+        }
+        if (lane == 0) P0[j] = p0, P1[j] = p1;
+      }
+      // ---- P-phase ("voting phase", node.ts:83-158)
+      __builtin_amdgcn_wave_barrier();
+      H0 = 0, H1 = 0;
+      for (uint32_t j = 0; j < W; ++j) {
+        H0 += (uint32_t)__builtin_popcountll(P0[j]);   // proposals are honest nodes' only
+        H1 += (uint32_t)__builtin_popcountll(P1[j]);
+      }
+      H0 = uni(H0), H1 = uni(H1);
+      own = per_lane_step(H0, H1);
+      if (!own) ph = phase_setup(row, p, tb, H0 + nb - B1u, H1 + B1u, h - H0 - H1, lane);
+      bool undecided = false;
+      for (uint32_t j = 0; j < W; ++j) {
+        const uint64_t hp = uni64(HP[j]);
+        if (!hp) continue;
+        const uint32_t c = j * 64u + lane;
+        const uint4 b = philox4x32_10(k0, k1, make_uint4(tlo, thi, c, (r - 1u) | (kStreamTally << 24)));
+        const uint64_t u = (uint64_t)b.w << 32 | b.z;
+        const bool mine = (hp >> lane) & 1ull;     // this lane's node is honest
+        uint32_t c0, c1;
+        if (!own) {
+          draw3(row, ph, m, q, k0, k1, tlo, thi, c, r, 1u, u, c0, c1);
+        } else {
+          const uint4 l = philox4x32_10(k0, k1, make_uint4(tlo, thi, c, (r - 1u) | (kStreamLie << 24)));
+          const uint32_t B1 = lies((uint64_t)l.w << 32 | l.z);
+          draw3_lane(p, H0 + nb - B1, H1 + B1, k0, k1, tlo, thi, c, r, 1u, u, mine, c0, c1);
+        }
+        const bool d0l = c0 > F, d1l = !d0l && c1 > F;
+        const uint64_t d0 = ballot(d0l) & hp;
+        const uint64_t d1 = ballot(d1l) & hp;
+        const uint64_t rest = hp & ~(d0 | d1);
+        uint64_t x1 = d1;
+        if (rest) {
+          x1 |= ballot(c1 > c0) & rest;
+          const uint64_t tie = ballot(c1 == c0) & rest;                  // an empty tally included
+          if (tie) x1 |= coin_ballot(k0, k1, tlo, thi, j, r, tie);
+        }
+        if (mine && (d0l || d1l)) dec |= 1ull << j;                      // sticky
+        undecided = undecided || (mine && !((dec >> j) & 1ull));
+        if (lane == 0) X1[j] = (X1[j] & ~hp) | x1;                       // a Byzantine node's bit is never written
+      }
+      R = r;
+      all_dec = !__any(undecided);                 // over the honest nodes
+      if (all_dec) break;
+    }
+    __builtin_amdgcn_wave_barrier();
+    uint32_t K = 0;                                // the honest nodes with x = 1
+    for (uint32_t j = 0; j < W; ++j) K += (uint32_t)__builtin_popcountll(X1[j] & HP[j]);
+    K = uni(K);
+    const uint32_t v = (K != 0u && K != h) ? 2u : (K != 0u ? 1u : 0u);
+    if (lane == 0) {
+      atomicAdd(&lhist[all_dec ? (R * 3u + v) : v], 1u);
+      if (all_dec && v == 2u) atomicAdd(&lhist[p.hist_len - 1u], 1u);
+      if (p.rounds_out) *p.rounds_out = all_dec ? R : 0u;
+    }
+    if (states) {
+      for (uint32_t j = 0; j < W; ++j) {
+        const uint64_t d = ballot((dec >> j) & 1ull);
+        if (lane == 0) DEC[j] = d;
+      }
+      __builtin_amdgcn_wave_barrier();
+      for (uint32_t c = lane; c < m; c += 64u) {
+        const uint32_t j = c >> 6;
+        if (!((HP[j] >> lane) & 1ull)) continue;   // Byzantine: alive, no protocol state (the host's entry stays)
+        bo_node_state ns;
+        ns.killed = 0;
+        ns.x = (int8_t)((X1[j] >> lane) & 1ull);
+        ns.decided = (int8_t)((DEC[j] >> lane) & 1ull);
+        ns.pad = 0;
+        ns.k = (int32_t)R + 1;
+        p.node_out[p.live_ids[c]] = ns;
+      }
+    }
+  }
+
+  __syncthreads();
+  flush_hist(lhist, p);
+}
+
+}  // namespace
+
+// A batch launch's per-wave LDS: four planes and the row region.
+uint32_t byz_wave_bytes(uint32_t W, uint32_t cap) {
+  const uint32_t WP = (W + 1u) & ~1u, capE = (cap + 1u) & ~1u;
+  return (4u * WP + capE) * 8u;
+}
+
+// ... and what a per-node-state launch adds to it: the DEC plane.
+uint32_t byz_state_bytes(uint32_t W) { return ((W + 1u) & ~1u) * 8u; }
+
+// The b Binomial thresholds go into LDS, once per workgroup, when a CU then holds as many
+// workgroups as without them: the fewer of what `lds_bytes` (histogram and the four waves'
+// regions) allows and the six that the registers allow.
+bool byz_thr_in_lds(uint32_t lds_bytes, uint32_t b) {
+  const uint32_t without = lds_groups_per_cu(lds_bytes) < kByzWgPerCu ? lds_groups_per_cu(lds_bytes) : kByzWgPerCu;
+  return lds_groups_per_cu(lds_bytes + 8u * b) >= without;
+}
+
+// Workgroups of the kernel that one CU holds at once (registers and LDS; 0 = unknown).
+int byz_blocks_per_cu(const KParams &p) {
+  int n = 0;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, benor_tally_byz_kernel, 64 * kWavesPerBlock,
+                                                                    p.lds_bytes);
+  return e == hipSuccess ? n : 0;
+}
+
+hipError_t launch_tally_byz(const KParams &plan, int grid, hipStream_t s) {
+  KParams p = plan;
+  if (p.node_out) {                                // a state launch (one trial): one more plane per wave
+    p.wave_bytes += byz_state_bytes(p.W);
+    p.lds_bytes += kWavesPerBlock * byz_state_bytes(p.W);
+  }
+  if (!p.tally_off || !p.tally_thr || !p.byz_plane || !p.byz_thr || p.W > kMaxW || p.byz_n == 0u ||
+      p.byz_n > p.m - p.q || plan.wave_bytes < byz_wave_bytes(p.W, p.tally_cap) ||
+      plan.lds_bytes < p.hist_bytes + kWavesPerBlock * plan.wave_bytes + (p.byz_lds ? 8u * p.byz_n : 0u))
+    return hipErrorInvalidValue;
+  if (p.lds_bytes > 64u * 1024u) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&benor_tally_byz_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(benor_tally_byz_kernel, dim3(grid), dim3(64 * kWavesPerBlock), p.lds_bytes, s, p);
+  return hipGetLastError();
+}
+
+}  // namespace benor

@@ -94,8 +94,10 @@ export interface TrialsConfig {
    *    nodes whose index, in ascending node id, is below its cut; crashCut = 0 is mode 5 bit for bit),
    *  7 mode 6 with an arbitrary subset for the prefix (MODE_CRASH_SUBSET: a crasher's last message reaches each
    *    receiver independently with probability crashReach / 2^32; crashReach = 0 is mode 5 and REACH_ALL is
-   *    mode 6 with a full cut, bit for bit) */
-  mode?: 0 | 1 | 2 | 3 | 4 | 5 | 6 | 7;
+   *    mode 6 with a full cut, bit for bit),
+   *  8 mode 4 with Byzantine senders (MODE_BYZ_TALLY: the nodes of byzantineList send at every step and lie,
+   *    they never receive; crashed + Byzantine <= F; without a Byzantine node it is mode 4 bit for bit) */
+  mode?: 0 | 1 | 2 | 3 | 4 | 5 | 6 | 7 | 8;
   /** event mode: deliveries after which node i is stopped (null = never);
    *  MODE_CRASH_TALLY, MODE_CRASH_PARTIAL, MODE_CRASH_SUBSET: the step at which node i crashes (null = never) */
   crashAt?: (number | null)[];
@@ -109,6 +111,14 @@ export interface TrialsConfig {
   /** MODE_CRASH_SUBSET: the probability, in units of 2^-32, that a crasher's last message reaches a receiver
    *  (0 .. REACH_ALL = 2^32 - 1: certainly); it fills the word that crashCut fills, so give one of the two */
   crashReach?: number;
+  /** MODE_BYZ_TALLY: true marks node i Byzantine (a node of faultyList is crashed and may not be in both) */
+  byzantineList?: boolean[];
+  /** MODE_BYZ_TALLY: the probability, in units of 2^-32, that a Byzantine message carries 1, independently per
+   *  trial, sender, receiver, round and phase (0 .. 2^32 - 1: certainly); it fills the word that crashCut fills */
+  byzOne?: number;
+  /** MODE_BYZ_TALLY: BYZ_RANDOM (default; each message by byzOne) or BYZ_OPPOSE (every message carries the value
+   *  fewer honest senders hold at the step, byzOne's step on a tie); it fills the word that crashCount fills */
+  byzStrategy?: 0 | 1;
 }
 
 /** TrialsConfig.mode values (include/benor.h BO_MODE_*). */
@@ -124,6 +134,10 @@ export declare const CUT_RANDOM: 4294967295;
 export declare const MODE_CRASH_SUBSET: 7;
 /** TrialsConfig.crashReach: every crasher reaches every receiver (include/benor.h, crash_reach = UINT32_MAX). */
 export declare const REACH_ALL: 4294967295;
+export declare const MODE_BYZ_TALLY: 8;
+/** TrialsConfig.byzStrategy (include/benor.h BO_BYZ_RANDOM, BO_BYZ_OPPOSE). */
+export declare const BYZ_RANDOM: 0;
+export declare const BYZ_OPPOSE: 1;
 
 /** Outcome histogram, (kMax + 1) * 3 + 1 bins (include/benor.h). */
 export declare function runTrials(cfg: TrialsConfig): Promise<BigUint64Array>;

@@ -154,6 +154,46 @@ enum {
  * of scheduled crashes below step 2 k_max, at every reach.  Not modelled: a reach
  * per crasher, explicitly given reach masks.  Batch API only (no network API, no
  * `sweep`). */
+/* BYZ_TALLY is RANDOM_TALLY3 with Byzantine senders: faulty
+ * processes that keep talking and lie, a different value to each receiver if they
+ * like (equivocation).  In this mode only, faulty[i] == 2 marks node i Byzantine;
+ * faulty[i] == 1 is crashed from the start, as in every mode; any other non-zero
+ * value is BO_ERR_INVALID_ARGUMENT.  With f crashed and b Byzantine nodes,
+ * f + b <= F (BO_ERR_FAULTY_COUNT otherwise); the rest of validation is
+ * RANDOM_DELIVERY's.  The m = N - f live nodes, honest and Byzantine together,
+ * carry compact indices in ascending node id, so with b = 0 every Philox key is
+ * RANDOM_TALLY3's.  f + b <= F gives m >= q + b, q = N-F: m > q whenever b > 0.
+ * All m live nodes send at every step (a silent node is a crash); only the
+ * h = m - b honest nodes receive and run the rule.  Honest receiver c draws q
+ * messages uniformly from the m senders, independently per (receiver, round,
+ * phase).  What a Byzantine message says is chosen by byz_strategy and byz_one, a
+ * probability in units of 2^-32 (every value valid, 0: never, UINT32_MAX:
+ * certainly):
+ *   BO_BYZ_RANDOM: each Byzantine message carries 1 with probability
+ *     byz_one / 2^32, else 0, independently per (trial, Byzantine sender,
+ *     receiver, round, phase).  At the level of counts receiver c hears
+ *     B1 ~ Binomial(b, p) ones and b - B1 zeros from the Byzantine senders that
+ *     could reach it: B1 = #{ j : thr[j] <= u }, thr = bo_byz_cdf(b, byz_one), u
+ *     from the Philox4x32-10 block ctr = {trial_lo, trial_hi, c, (r-1) | 10 << 24},
+ *     key = seed (stream 10): the R-phase takes out[1] << 32 | out[0], the P-phase
+ *     out[3] << 32 | out[2] (stream 5's convention).  byz_one = 0 gives B1 = 0,
+ *     UINT32_MAX gives B1 = b, and neither draws a stream-10 word.
+ *   BO_BYZ_OPPOSE: at each step every Byzantine message carries the value held by
+ *     fewer honest senders at that step -- 0 if H1 > H0, 1 if H0 > H1 -- the same
+ *     to every receiver; on H0 == H1 the step is BO_BYZ_RANDOM's with byz_one.
+ *   Any other strategy is BO_ERR_INVALID_ARGUMENT.
+ * H0, H1, Hq are the class sizes over the honest senders at the step (a sender's
+ * x at an R-step, its proposal at a P-step; decided nodes keep sending).
+ * Receiver c's (c0, c1) is RANDOM_TALLY3's draw among m senders with the class
+ * sizes (H0 + b - B1, H1 + B1, Hq), from its stream-5 uniform and stream-6 walk.
+ * Rule, coins, k and the histogram layout are RANDOM_TALLY3's.  The run halts
+ * after the round in which every honest node has decided; the outcome and the
+ * common value are taken over the honest nodes.  bo_run_trial_states reports a
+ * Byzantine node as {killed 0, x -1, decided -1, k -1}: alive, no protocol state.
+ * b = 0 is RANDOM_TALLY3's plan at every byz_one and strategy: its kernel choice
+ * and its results bit for bit.  Not modelled: Byzantine nodes together with
+ * crashes during the run, a strategy that reads a receiver's inbox, explicit lie
+ * masks.  Batch API only (no network API, no `sweep`). */
 enum {
   BO_MODE_LOCKSTEP = 0,
   BO_MODE_RANDOM_DELIVERY = 1,
@@ -162,8 +202,12 @@ enum {
   BO_MODE_RANDOM_TALLY3 = 4,
   BO_MODE_CRASH_TALLY = 5,
   BO_MODE_CRASH_PARTIAL = 6,
-  BO_MODE_CRASH_SUBSET = 7
+  BO_MODE_CRASH_SUBSET = 7,
+  BO_MODE_BYZ_TALLY = 8
 };
+
+/* BO_MODE_BYZ_TALLY, byz_strategy. */
+enum { BO_BYZ_RANDOM = 0, BO_BYZ_OPPOSE = 1 };
 
 /* BO_MODE_CRASH_PARTIAL, crash_cut: a cut per trial and crasher, uniform on 0..m0. */
 #define BO_CUT_RANDOM 0xFFFFFFFFu
@@ -308,9 +352,12 @@ typedef struct bo_trials_cfg {
         uint32_t crash_cut;   /* CRASH_PARTIAL: every crasher's cut, 0..m0, or BO_CUT_RANDOM */
         uint32_t crash_reach; /* CRASH_SUBSET: the probability, in units of 2^-32, that a crasher's last message
                                  reaches a receiver (0: never, UINT32_MAX: certainly); every value is valid */
+        uint32_t byz_one;     /* BYZ_TALLY: the probability, in units of 2^-32, that a Byzantine message carries 1
+                                 (0: never, UINT32_MAX: certainly); every value is valid */
     };                        /* the other modes ignore it */
     uint64_t seed;            /* Philox4x32-10 key */
-    const uint8_t *faulty;    /* host [N]; exactly F set (LOCKSTEP, EVENT), at most F (RANDOM_DELIVERY, RANDOM_TALLY, RANDOM_TALLY3, CRASH_TALLY, CRASH_PARTIAL, CRASH_SUBSET) */
+    const uint8_t *faulty;    /* host [N]; non-zero = faulty: exactly F set (LOCKSTEP, EVENT), at most F (RANDOM_DELIVERY, RANDOM_TALLY, RANDOM_TALLY3, CRASH_TALLY, CRASH_PARTIAL, CRASH_SUBSET);
+                                 BYZ_TALLY alone reads the value: 1 crashed from the start, 2 Byzantine, together at most F */
     const int8_t *init;       /* host [N]; used when init_mode == BO_INIT_FIXED */
     /* EVENT mode: GET /stop schedule.  crash_at[i] = number of deliveries
      * after which node i is stopped (UINT32_MAX = never), or, when crash_at is
@@ -320,9 +367,13 @@ typedef struct bo_trials_cfg {
      * at which node i crashes (UINT32_MAX = never; entries of faulty nodes are
      * ignored), or, when crash_at is NULL, crash_count distinct initially-live
      * nodes at uniform steps in [0, crash_window), drawn per trial.
-     * The other modes ignore the three fields. */
+     * The other modes ignore the three fields, except that BYZ_TALLY reads the
+     * crash_count word as byz_strategy. */
     const uint32_t *crash_at; /* host [N] or NULL */
-    uint32_t crash_count;
+    union {                   /* one word, the layout of the struct is that of ABI version 8 */
+        uint32_t crash_count;
+        uint32_t byz_strategy; /* BYZ_TALLY: BO_BYZ_RANDOM or BO_BYZ_OPPOSE */
+    };
     uint32_t crash_window;
 } bo_trials_cfg;
 
@@ -365,9 +416,9 @@ int bo_plan_check(bo_plan *plan);
  * (c0 = M - c1); the P-phase counts c1 when M is odd (no tie, so no "?"
  * proposal: c0 = m - c1) and c0, c1 otherwise -- 2 or 3 x ceil(m/32).
  * RANDOM_DELIVERY: both values in both phases, 4 x ceil(m/32).  RANDOM_TALLY,
- * RANDOM_TALLY3, CRASH_TALLY, CRASH_PARTIAL and CRASH_SUBSET answer RANDOM_DELIVERY's unit,
- * the work they stand in for (the last three with m = the initially-live count, as
- * bo_plan_live_nodes reports it). */
+ * RANDOM_TALLY3, CRASH_TALLY, CRASH_PARTIAL, CRASH_SUBSET and BYZ_TALLY answer RANDOM_DELIVERY's
+ * unit, the work they stand in for (the crash modes with m = the initially-live count,
+ * BYZ_TALLY with m = the live nodes, honest and Byzantine, as bo_plan_live_nodes reports it). */
 uint64_t bo_plan_popc_words_per_node_round(const bo_plan *plan);
 uint32_t bo_plan_live_nodes(const bo_plan *plan);
 
@@ -401,11 +452,18 @@ enum {
   BO_KERNEL_TALLY_PARTIAL = 12, /* BO_MODE_CRASH_PARTIAL with a non-empty schedule: TALLY_CRASH's step run once
                               per segment of receivers that hear the same crashers (the cuts of the step's
                               crashers are the boundaries), one table per pool size */
-  BO_KERNEL_TALLY_SUBSET = 13 /* BO_MODE_CRASH_SUBSET with a non-empty schedule: per receiver group a reach pass
+  BO_KERNEL_TALLY_SUBSET = 13, /* BO_MODE_CRASH_SUBSET with a non-empty schedule: per receiver group a reach pass
                               (which of the step's crashers each lane hears, Philox stream 9), then
                               TALLY_CRASH's wave-uniform draw for the lanes that hear none of them and one
                               per-lane draw, each lane searching the row of its own pool in global memory,
                               for the others; one table per pool size */
+  BO_KERNEL_TALLY_BYZ = 14  /* BO_MODE_BYZ_TALLY with b > 0 Byzantine nodes: TALLY3's draw among all m live
+                              senders for the honest receivers (a constant honest plane in place of the alive
+                              plane); a step whose Byzantine messages are the same for every receiver is
+                              wave-uniform with its row staged in LDS, otherwise every lane draws its own
+                              Binomial count of lying 1s (Philox stream 10) and searches the row of its own
+                              class sizes in global memory; one table, (m, q) (b = 0 runs RANDOM_TALLY3's
+                              kernel choice) */
 };
 
 /* The kernel family bo_plan_launch runs for this plan.  (The per-node-state
@@ -436,6 +494,13 @@ int bo_run_trial_states(const bo_trials_cfg *cfg, uint64_t trial, bo_node_state 
  * double; a draw u (uniform 64 bits) gives the count lo + #{ j : thr[j] <= u }. */
 int bo_tally_cdf(uint32_t m, uint32_t q, uint32_t K, uint32_t *lo_out,
                  uint64_t *thr_out, uint32_t cap, uint32_t *n_out);
+
+/* The BYZ_TALLY thresholds of Binomial(b, p), p = byz_one / 2^32: thr_out[j] =
+ * min(2^64 - 1, floor(CDF(j) * 2^64)), j = 0 .. b-1, built in double (*n_out = b;
+ * BO_ERR_INVALID_ARGUMENT if cap < b or b > BO_MAX_N).  Exactly what bo_plan_create
+ * uploads.  Host only, no device needed.  A draw u (uniform 64 bits) gives the
+ * number of Byzantine messages that carry 1, B1 = #{ j : thr[j] <= u }. */
+int bo_byz_cdf(uint32_t b, uint32_t byz_one, uint64_t *thr_out, uint32_t cap, uint32_t *n_out);
 
 /* ---- diagnostics ---- */
 

@@ -14,7 +14,7 @@ median and minimum ms per launch and the variant's median / first variant's.
 
 A shape may carry a fourth field f < F (the first f nodes crashed, the rest of
 F the random-delivery slack: BO_MODE_RANDOM_DELIVERY).  A variant may also name
-the delivery mode with the pseudo-variable `mode` (lockstep, random, tally, tally3, crash, partial or subset),
+the delivery mode with the pseudo-variable `mode` (lockstep, random, tally, tally3, crash, partial, subset or byz),
 so the mask-level and the count-level random-delivery modes are timed
 alternately on one plan each:
 
@@ -42,6 +42,13 @@ mode:partial with a full cut, both on its own kernel:
 
     python tools/ab_inproc.py --rounds 7 --reps 5 --shapes "1024,340,100000,0" --variants \
         "m5=mode:crash,crash_count:16,crash_window:4;r0=mode:subset,crash_count:16,crash_window:4,crash_reach:0;half=mode:subset,crash_count:16,crash_window:4,crash_reach:0.5"
+
+`mode:byz` (BO_MODE_BYZ_TALLY) takes `byzantine` (the b live nodes after the crashed
+ones lie), `byz_one` (`all`, a probability with a decimal point or the 32-bit word) and
+`byz_strategy` (random or oppose); next to mode:tally3 it times what the liars cost:
+
+    python tools/ab_inproc.py --rounds 7 --reps 5 --shapes "1024,340,100000,0" --variants \
+        "t3=mode:tally3;half=mode:byz,byzantine:100,byz_one:0.5;all=mode:byz,byzantine:100,byz_one:all;opp=mode:byz,byzantine:100,byz_one:0.5,byz_strategy:oppose"
 
 Every line also reports
 the live node-rounds per second its launches represent (bench.py node_rounds),
@@ -83,7 +90,8 @@ def main():
         v = [int(x) for x in sp.split(",")]
         shapes.append((v[0], v[1], v[2], v[3] if len(v) > 3 else v[1]))
     modes = {name: env.pop("mode", None) for name, env in variants}   # `mode` is no environment variable
-    scheds = {name: {k: env.pop(k) for k in ("crash_count", "crash_window", "crash_at", "crash_cut", "crash_reach")
+    scheds = {name: {k: env.pop(k) for k in ("crash_count", "crash_window", "crash_at", "crash_cut", "crash_reach",
+                                             "byzantine", "byz_one", "byz_strategy")
                      if k in env}
               for name, env in variants}                              # ... nor is the crash schedule
     knobs = sorted({k for _, env in variants for k in env})
@@ -95,19 +103,28 @@ def main():
     mode_ids = {"lockstep": benor.BO_MODE_LOCKSTEP, "random": benor.BO_MODE_RANDOM_DELIVERY,
                 "tally": benor.BO_MODE_RANDOM_TALLY, "tally3": benor.BO_MODE_RANDOM_TALLY3,
                 "crash": benor.BO_MODE_CRASH_TALLY, "partial": benor.BO_MODE_CRASH_PARTIAL,
-                "subset": benor.BO_MODE_CRASH_SUBSET}
+                "subset": benor.BO_MODE_CRASH_SUBSET, "byz": benor.BO_MODE_BYZ_TALLY}
     bad = sorted({v for v in modes.values() if v is not None and v not in mode_ids})
     if bad:
         ap.error(f"mode must be one of {sorted(mode_ids)}: {bad}")
-    if any(sc and modes[name] not in ("crash", "partial", "subset") for name, sc in scheds.items()):
+    byz_keys = ("byzantine", "byz_one", "byz_strategy")
+    if any(any(k in sc for k in byz_keys) != (modes[name] == "byz") for name, sc in scheds.items()):
+        ap.error("byzantine / byz_one / byz_strategy go with mode:byz, and it with them")
+    if any(any(k not in byz_keys for k in sc) and modes[name] not in ("crash", "partial", "subset")
+           for name, sc in scheds.items()):
         ap.error("crash_count / crash_window / crash_at need mode:crash, mode:partial or mode:subset")
     if any("crash_cut" in sc and modes[name] != "partial" for name, sc in scheds.items()):
         ap.error("crash_cut needs mode:partial")
     if any("crash_reach" in sc and modes[name] != "subset" for name, sc in scheds.items()):
         ap.error("crash_reach needs mode:subset")
 
-    def schedule(name, N):
+    def schedule(name, N, f):
         sc, kw = dict(scheds[name]), {}
+        if modes[name] == "byz":
+            b, one = int(sc.get("byzantine", 0)), sc.get("byz_one", "0.5")
+            return {"byzantine": [f <= i < f + b for i in range(N)],
+                    "byz_one": 0xFFFFFFFF if one == "all" else benor.reach_word(float(one)) if "." in one else int(one),
+                    "byz_strategy": {"random": benor.BYZ_RANDOM, "oppose": benor.BYZ_OPPOSE}[sc.get("byz_strategy", "random")]}
         cut = sc.pop("crash_cut", None)
         reach = sc.pop("crash_reach", None)
         if "crash_at" in sc:
@@ -147,7 +164,7 @@ def main():
             key = (mode, tuple(sorted(scheds[name].items())))
             if key not in plans:
                 plans[key] = benor.TrialsPlan(N, F, [i < f for i in range(N)], seed=0x5EED + N, k_max=32, mode=mode,
-                                              **schedule(name, N))
+                                              **schedule(name, N, f))
             plans[name] = plans[key]
         h = torch.zeros(plans[variants[0][0]].hist_len, dtype=torch.int64, device="cuda")
         for name, env in variants:                    # warm-up per variant (allocations, code load)
