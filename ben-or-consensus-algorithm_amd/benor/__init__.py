@@ -47,9 +47,13 @@ BO_MODE_CRASH_SUBSET = 7       # mode 6 with an arbitrary subset for the prefix:
                                # receiver independently with probability crash_reach / 2^32 (REACH_ALL: certainly)
 BO_MODE_BYZ_TALLY = 8          # mode 4 with Byzantine senders: byzantine[i] marks node i (it sends at every step and
                                # lies, it never receives); byz_one / 2^32 is the probability that a Byzantine message
-                               # carries 1, byz_strategy BYZ_RANDOM (independently per receiver) or BYZ_OPPOSE
+                               # carries 1, byz_strategy BYZ_RANDOM (independently per receiver), BYZ_OPPOSE, or one of
+                               # the two that read the receiver's inbox and ignore byz_one, BYZ_BALANCE and BYZ_SPLIT
 BYZ_RANDOM = 0                 # byz_strategy: each Byzantine message is 1 with probability byz_one / 2^32 (equivocation)
 BYZ_OPPOSE = 1                 # ... every one carries the value fewer honest senders hold (byz_one's step on a tie)
+BYZ_BALANCE = 3                # ... the Byzantine messages a receiver drew make its two tallies as equal as they can
+BYZ_SPLIT = 4                  # ... they all say 1 to a receiver of odd compact index and 0 to one of even index
+BO_BYZ_RANDOM, BO_BYZ_OPPOSE, BO_BYZ_BALANCE, BO_BYZ_SPLIT = BYZ_RANDOM, BYZ_OPPOSE, BYZ_BALANCE, BYZ_SPLIT   # include/benor.h's names
 CRASH_TABLE_MAX_BYTES = 512 << 20   # modes 5, 6 and 7: thresholds of the tables of all reachable live counts, at most
 CUT_RANDOM = 0xFFFFFFFF        # crash_cut: a cut per trial and crasher, uniform on 0..m0 (Philox stream 8)
 REACH_ALL = 0xFFFFFFFF         # crash_reach: every crasher reaches every receiver (no Philox stream 9 word is drawn)

@@ -129,7 +129,8 @@ def cmd_trials(a) -> int:
             raise SystemExit("--byzantine counts live nodes: 0 .. N - crashed")
         sched = {"byzantine": [crashed <= i < crashed + a.byzantine for i in range(a.N)],   # the live nodes after the crashed
                  "byz_one": benor.reach_word(a.byz_one),
-                 "byz_strategy": {"random": benor.BYZ_RANDOM, "oppose": benor.BYZ_OPPOSE}[a.byz_strategy]}
+                 "byz_strategy": {"random": benor.BYZ_RANDOM, "oppose": benor.BYZ_OPPOSE, "balance": benor.BYZ_BALANCE,
+                                  "split": benor.BYZ_SPLIT}[a.byz_strategy]}
     elif a.byzantine:
         raise SystemExit("--byzantine needs --mode byz")
     plan = benor.TrialsPlan(a.N, a.F, [i < crashed for i in range(a.N)], seed=a.seed, k_max=a.k_max, mode=mode,
@@ -311,9 +312,11 @@ def main(argv=None) -> int:
     t.add_argument("--byz-one", type=float, default=0.5,
                    help="byz: the probability in [0, 1] that a Byzantine message carries 1, independently per trial, "
                         "sender, receiver and step")
-    t.add_argument("--byz-strategy", choices=["random", "oppose"], default="random",
-                   help="byz: random (each message by --byz-one) or oppose (every message carries the value fewer honest "
-                        "senders hold; --byz-one on a tie)")
+    t.add_argument("--byz-strategy", choices=["random", "oppose", "balance", "split"], default="random",
+                   help="byz: random (each message by --byz-one), oppose (every message carries the value fewer honest "
+                        "senders hold; --byz-one on a tie), balance (the liars in a receiver's inbox see its honest "
+                        "messages and make its two tallies as equal as they can) or split (they say 1 to receivers of odd "
+                        "compact index and 0 to the others); the last two do not read --byz-one")
     w = sub.add_parser("sweep", help="C5 decision-round phase diagram")
     w.add_argument("--N", default="64,128,256,512,1024,2048,4096")
     w.add_argument("--steps", type=int, default=32)

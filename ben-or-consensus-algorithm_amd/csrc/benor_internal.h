@@ -22,6 +22,7 @@ constexpr uint32_t kStreamSchedule = 7u;   // BO_MODE_CRASH_TALLY: a trial's ran
 constexpr uint32_t kStreamCut = 8u;        // BO_MODE_CRASH_PARTIAL: a crasher's random cut, keyed by its compact index
 constexpr uint32_t kStreamReach = 9u;      // BO_MODE_CRASH_SUBSET: whether crasher p's last message reaches receiver c
 constexpr uint32_t kStreamLie = 10u;       // BO_MODE_BYZ_TALLY: a receiver's Binomial count of Byzantine messages that carry 1
+constexpr uint32_t kStreamHeard = 11u;     // ... BO_BYZ_BALANCE / BO_BYZ_SPLIT: how many of a receiver's messages are Byzantine (selection sampling)
 
 constexpr int kWavesPerBlock = 4;          // 256-thread workgroups, one trial per wave
 
@@ -177,7 +178,8 @@ struct KParams {
   // and Byzantine; byz_plane[W] holds the honest nodes' bits (the receivers), byz_n = b > 0 is the
   // number of Byzantine senders, byz_thr[b] the thresholds of Binomial(b, byz_one / 2^32)
   // (bo_byz_cdf; device), searched in LDS (byz_lds, a copy per workgroup behind the waves' regions)
-  // or where they lie in global memory.  tally_off / tally_thr hold the one table of (m, q)
+  // or where they lie in global memory.  tally_off / tally_thr hold the one table of (m, q).
+  // BO_BYZ_BALANCE and BO_BYZ_SPLIT read no thresholds: byz_thr is unused and byz_lds is 0
   const unsigned long long *byz_plane;
   const unsigned long long *byz_thr;
   uint32_t byz_n, byz_strategy, byz_one, byz_lds;
@@ -258,6 +260,7 @@ hipError_t launch_tally_subset(const KParams &p, int grid_blocks, hipStream_t st
 uint32_t byz_wave_bytes(uint32_t W, uint32_t cap);
 uint32_t byz_state_bytes(uint32_t W);
 bool byz_thr_in_lds(uint32_t lds_bytes, uint32_t b);
+bool byz_heard(const KParams &p);                 // BO_BYZ_BALANCE, BO_BYZ_SPLIT: the kernel without thresholds
 int byz_blocks_per_cu(const KParams &p);          // resident workgroups per CU (registers, LDS); 0 = unknown
 hipError_t launch_tally_byz(const KParams &p, int grid_blocks, hipStream_t stream);
 

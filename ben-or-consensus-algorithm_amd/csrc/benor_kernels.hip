@@ -697,7 +697,7 @@ void plan_geometry(KParams &p) {
     p.tally_cap = p.q <= e ? p.q : e;
     p.wave_bytes = (byz_wave_bytes(W, p.tally_cap) + 15u) & ~15u;
     p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
-    p.byz_lds = byz_thr_in_lds(p.lds_bytes, p.byz_n) ? 1u : 0u;
+    p.byz_lds = !byz_heard(p) && byz_thr_in_lds(p.lds_bytes, p.byz_n) ? 1u : 0u;   // (the inbox-reading strategies have none)
     if (p.byz_lds) p.lds_bytes += 8u * p.byz_n;
     return;
   }

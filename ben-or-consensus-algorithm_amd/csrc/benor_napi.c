@@ -594,7 +594,7 @@ static napi_value run_trials(napi_env env, napi_callback_info info) {
     prop_u32(env, o, "crashCut", 0, &j->cfg.crash_cut);          /* mode 6: 0 .. N - f, or BO_CUT_RANDOM */
     prop_u32(env, o, "crashReach", j->cfg.crash_cut, &j->cfg.crash_reach);   /* mode 7: the same word, a probability in units of 2^-32 */
     prop_u32(env, o, "byzOne", j->cfg.crash_cut, &j->cfg.byz_one);           /* mode 8: the same word, the probability that a Byzantine message carries 1 */
-    prop_u32(env, o, "byzStrategy", j->cfg.crash_count, &j->cfg.byz_strategy);   /* mode 8: the crash_count word, BO_BYZ_RANDOM / BO_BYZ_OPPOSE */
+    prop_u32(env, o, "byzStrategy", j->cfg.crash_count, &j->cfg.byz_strategy);   /* mode 8: the crash_count word, a BO_BYZ_* strategy */
     const uint32_t N = j->cfg.N;
     j->faulty = (uint8_t *)calloc(N + 1, 1);
     j->init = (int8_t *)calloc(N + 1, 1);

@@ -582,8 +582,10 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
     for (uint32_t i = 0; i < cfg->N; ++i)
       if (cfg->faulty[i] > 2u)
         return fail(BO_ERR_INVALID_ARGUMENT, "BO_MODE_BYZ_TALLY: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)");
-    if (cfg->byz_strategy != BO_BYZ_RANDOM && cfg->byz_strategy != BO_BYZ_OPPOSE)
-      return fail(BO_ERR_INVALID_ARGUMENT, "byz_strategy must be BO_BYZ_RANDOM or BO_BYZ_OPPOSE");
+    if (cfg->byz_strategy != BO_BYZ_RANDOM && cfg->byz_strategy != BO_BYZ_OPPOSE && cfg->byz_strategy != BO_BYZ_BALANCE &&
+        cfg->byz_strategy != BO_BYZ_SPLIT)
+      return fail(BO_ERR_INVALID_ARGUMENT,
+                  "byz_strategy must be BO_BYZ_RANDOM, BO_BYZ_OPPOSE, BO_BYZ_BALANCE or BO_BYZ_SPLIT");
   }
   const auto crashed = [&](uint32_t i) { return byz_mode ? cfg->faulty[i] == 1u : cfg->faulty[i] != 0u; };
   uint32_t f = 0, nbyz = 0;
@@ -862,7 +864,7 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
       const size_t thr_bytes = sizeof(uint64_t) * std::max<size_t>(thr.size(), 1u);
       // ... and, with Byzantine senders, the Binomial thresholds and the honest plane behind it
       std::vector<uint64_t> lie;
-      if (kp.variant == 14) byz_row(kp.byz_n, kp.byz_one, lie);
+      if (kp.variant == 14 && !benor::byz_heard(kp)) byz_row(kp.byz_n, kp.byz_one, lie);   // (BALANCE, SPLIT: no thresholds)
       const size_t lie_bytes = sizeof(uint64_t) * lie.size();
       const size_t plane_bytes = kp.variant == 14 ? sizeof(uint64_t) * crash.honest.size() : 0u;
       e = hipMalloc(&pl->d_tally, off_bytes + thr_bytes + lie_bytes + plane_bytes);

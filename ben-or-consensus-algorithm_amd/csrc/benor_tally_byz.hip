@@ -14,6 +14,8 @@
 //     at UINT32_MAX without a draw;
 //   BO_BYZ_OPPOSE: 0 if H1 > H0, b if H0 > H1, for every receiver; BO_BYZ_RANDOM's
 //     step on H0 == H1.
+// BO_BYZ_BALANCE and BO_BYZ_SPLIT, whose liars see the receiver's inbox, run a second
+// kernel of this file, benor_tally_heard_kernel (further down).
 //
 // One wave = one trial, lane l of receiver group j = compact index 64 j + l over
 // the m live nodes, as in benor_tally_crash.hip, whose helpers this kernel runs
@@ -309,7 +311,230 @@ __global__ void __launch_bounds__(256, 6) benor_tally_byz_kernel(KParams p) {
   flush_hist(lhist, p);
 }
 
+// ---- BO_BYZ_BALANCE, BO_BYZ_SPLIT: Byzantine senders that see the receiver's inbox
+//
+// The Byzantine messages are a class of their own inside the draw.  Stage 1 is mode 4's
+// draw among m senders with the class sizes (H0, H1, Hq + b): wave-uniform, so every step
+// is phase_setup + draw3 from the LDS row, and (h0, h1) are the honest 0s and 1s heard.
+// Stage 2 splits the rest = q - h0 - h1 messages of the merged class into honest "?" and
+// Byzantine ones, nB ~ Hypergeometric(Hq + b, b, rest): nothing is drawn at Hq = 0 (nB =
+// rest; every step but a round-1 R-phase with "?" starts), else draw3's selection sampling
+// over the smaller of the two sub-classes (the Byzantine one on a tie) from stream 11.
+// The nB liars then say l1 ones and nB - l1 zeros, having seen (h0, h1).
+
+// Stage 2: how many of receiver c's `rest` messages from the merged class of Hq honest "?"
+// and nb Byzantine senders are Byzantine.  Hq and nb are wave-uniform, Hq != 0; a lane
+// with rest = 0 draws nothing, and a lane whose count is settled stops taking words.
+__device__ __forceinline__ uint32_t heard_byz(uint32_t Hq, uint32_t nb, uint32_t rest, uint32_t k0, uint32_t k1,
+                                              uint32_t tlo, uint32_t thi, uint32_t c, uint32_t r, uint32_t phase) {
+  const bool walk_byz = nb <= Hq;                  // the smaller sub-class is walked
+  const uint32_t KW = walk_byz ? nb : Hq;
+  const uint32_t dtop = Hq + nb;                   // >= rest, >= KW
+  const uint32_t c3 = (r - 1u) | (phase << 16) | (kStreamHeard << 24);
+  uint32_t i = 0, cS = 0;
+  const auto word = [&](uint32_t w) {
+    if (i < KW) {
+      const uint32_t d = dtop - i;                 // member i's denominator, >= 1
+      const uint64_t mm = (uint64_t)w * d;
+      const uint32_t l = (uint32_t)mm;
+      bool ok = true;
+      if (l < d) ok = l >= (0u - d) % d;
+      if (ok) {
+        if ((uint32_t)(mm >> 32) < rest - cS) ++cS;
+        ++i;
+      }
+    }
+  };
+  for (uint32_t blk = 0; __any(i < KW && cS < rest); ++blk) {
+    const uint4 b = philox4x32_10(k0, k1, make_uint4(tlo, thi, c | (blk << 12), c3));
+    word(b.x), word(b.y), word(b.z), word(b.w);
+  }
+  return walk_byz ? cS : rest - cS;
+}
+
+// Of the nB Byzantine messages in receiver c's inbox, how many say 1, given the honest
+// (h0, h1) next to them.
+__device__ __forceinline__ uint32_t heard_lies(uint32_t strategy, uint32_t c, uint32_t h0, uint32_t h1, uint32_t nB) {
+  if (strategy == BO_BYZ_SPLIT) return (c & 1u) ? nB : 0u;
+  const int32_t d = (int32_t)(h0 + nB) - (int32_t)h1;   // BO_BYZ_BALANCE: the tallies as equal as nB lies allow
+  if (d <= 0) return 0u;
+  const uint32_t half = (uint32_t)d >> 1;
+  return half < nB ? half : nB;
+}
+
+// benor_tally_byz_kernel's trial loop with every step of the first kind: no Binomial
+// thresholds (byz_thr and byz_lds are not read), no per-lane row.
+__global__ void __launch_bounds__(256, 6) benor_tally_heard_kernel(KParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wv = threadIdx.x >> 6;
+  const uint32_t m = p.m, F = p.F, W = p.W, q = p.q, nb = p.byz_n, strategy = p.byz_strategy;
+  const uint32_t WP = (W + 1u) & ~1u;
+
+  uint32_t *lhist = reinterpret_cast<uint32_t *>(smem);
+  const bool states = p.node_out != nullptr;       // a state launch: a DEC plane of its own
+  uint64_t *HP = reinterpret_cast<uint64_t *>(smem + p.hist_bytes + wv * p.wave_bytes);   // [W] honest (constant)
+  uint64_t *X1 = HP + WP;                                                                 // [W] x = 1
+  uint64_t *P1 = X1 + WP, *P0 = P1 + WP;                                                  // [W] proposals 1, 0
+  uint64_t *X0 = P0;                                                                      // [W] x = 0 (round 1)
+  uint64_t *DEC = P0 + WP;                                                                // [W] decided (state launch)
+  uint64_t *row = HP + (states ? 5u : 4u) * WP;                                           // [tally_cap] thresholds
+
+  for (uint32_t i = threadIdx.x; i < p.hist_len; i += blockDim.x) lhist[i] = 0u;
+  for (uint32_t w = lane; w < W; w += 64u) HP[w] = p.byz_plane[w];
+  __syncthreads();
+
+  uint32_t h = 0u;                                 // honest nodes
+  for (uint32_t j = 0; j < W; ++j) h += (uint32_t)__builtin_popcountll(HP[j]);
+  h = uni(h);
+
+  Table tb;                                        // the plan's one table
+  tb.m = m;
+  tb.off = p.tally_off;
+  tb.thr = p.tally_thr;
+
+  const uint32_t k0 = (uint32_t)p.seed, k1 = (uint32_t)(p.seed >> 32);
+  const uint64_t waves_total = (uint64_t)gridDim.x * kWavesPerBlock;
+
+  for (uint64_t t = (uint64_t)blockIdx.x * kWavesPerBlock + wv; t < p.trial_count; t += waves_total) {
+    const uint64_t trial = p.trial_begin + t;
+    const uint32_t tlo = uni((uint32_t)trial), thi = uni((uint32_t)(trial >> 32));
+    __builtin_amdgcn_wave_barrier();               // the previous trial's state reads are done
+    if (p.init_mode == BO_INIT_RANDOM) {           // /start (node.ts:167-188): stream 1, as every batch mode
+      const uint32_t nph = (W + 1u) >> 1;
+      if (lane < nph) {
+        uint4 r;
+        if (m <= 32u) r = make_uint4(init_word_small(k0, k1, trial), 0u, 0u, 0u);   // shared block (m <= 32)
+        else r = philox4x32_10(k0, k1, make_uint4(tlo, thi, lane, kStreamInit << 24));
+        const uint32_t w0 = 2u * lane, w1 = w0 + 1u;
+        const uint64_t g0 = group_mask(w0, m), a0 = ((uint64_t)r.y << 32 | r.x) & g0;
+        X1[w0] = a0, X0[w0] = g0 & ~a0;
+        if (w1 < W) {
+          const uint64_t g1 = group_mask(w1, m), a1 = ((uint64_t)r.w << 32 | r.z) & g1;
+          X1[w1] = a1, X0[w1] = g1 & ~a1;
+        }
+      }
+    } else {
+      for (uint32_t w = lane; w < W; w += 64u) {
+        const uint4 rc = p.init_plane[w];
+        X0[w] = (uint64_t)rc.y << 32 | rc.x;
+        X1[w] = (uint64_t)rc.w << 32 | rc.z;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+
+    uint64_t dec = 0ull;                           // bit j: node 64 j + lane has decided (sticky)
+    uint32_t R = 0;
+    bool all_dec = false;
+    for (uint32_t r = 1; r <= p.k_max; ++r) {
+      // ---- R-phase ("proposal phase", node.ts:46-82)
+      uint32_t H0 = 0, H1 = 0;
+      for (uint32_t j = 0; j < W; ++j) {
+        const uint64_t hp = HP[j];
+        if (r == 1u) H0 += (uint32_t)__builtin_popcountll(X0[j] & hp);
+        H1 += (uint32_t)__builtin_popcountll(X1[j] & hp);
+      }
+      H1 = uni(H1);
+      H0 = r == 1u ? uni(H0) : h - H1;             // after a P-phase every honest x is binary
+      uint32_t Hq = h - H0 - H1;                   // "?" starts: round 1 only
+      PhaseC ph = phase_setup(row, p, tb, H0, H1, Hq + nb, lane);   // (reads the class sizes before P0 takes X0's words)
+      for (uint32_t j = 0; j < W; ++j) {
+        const uint64_t hp = uni64(HP[j]);
+        uint64_t p0 = 0ull, p1 = 0ull;
+        if (hp) {                                  // a group without an honest lane draws nothing
+          const uint32_t c = j * 64u + lane;
+          // the round's block of receiver c: u_R = out[1] << 32 | out[0], u_P = out[3] << 32 | out[2]
+          const uint4 b = philox4x32_10(k0, k1, make_uint4(tlo, thi, c, (r - 1u) | (kStreamTally << 24)));
+          uint32_t h0, h1;
+          draw3(row, ph, m, q, k0, k1, tlo, thi, c, r, 0u, (uint64_t)b.y << 32 | b.x, h0, h1);
+          const uint32_t rest = ((hp >> lane) & 1ull) ? q - h0 - h1 : 0u;   // (a Byzantine lane hears nothing)
+          const uint32_t nB = Hq != 0u ? heard_byz(Hq, nb, rest, k0, k1, tlo, thi, c, r, 0u) : rest;
+          const uint32_t l1 = heard_lies(strategy, c, h0, h1, nB);
+          const uint32_t c0 = h0 + nB - l1, c1 = h1 + l1;
+          p0 = ballot(c0 > c1) & hp;
+          p1 = ballot(c1 > c0) & hp;
+        }
+        if (lane == 0) P0[j] = p0, P1[j] = p1;
+      }
+      // ---- P-phase ("voting phase", node.ts:83-158)
+      __builtin_amdgcn_wave_barrier();
+      H0 = 0, H1 = 0;
+      for (uint32_t j = 0; j < W; ++j) {
+        H0 += (uint32_t)__builtin_popcountll(P0[j]);   // proposals are honest nodes' only
+        H1 += (uint32_t)__builtin_popcountll(P1[j]);
+      }
+      H0 = uni(H0), H1 = uni(H1);
+      Hq = h - H0 - H1;
+      ph = phase_setup(row, p, tb, H0, H1, Hq + nb, lane);
+      bool undecided = false;
+      for (uint32_t j = 0; j < W; ++j) {
+        const uint64_t hp = uni64(HP[j]);
+        if (!hp) continue;
+        const uint32_t c = j * 64u + lane;
+        const uint4 b = philox4x32_10(k0, k1, make_uint4(tlo, thi, c, (r - 1u) | (kStreamTally << 24)));
+        const bool mine = (hp >> lane) & 1ull;     // this lane's node is honest
+        uint32_t h0, h1;
+        draw3(row, ph, m, q, k0, k1, tlo, thi, c, r, 1u, (uint64_t)b.w << 32 | b.z, h0, h1);
+        const uint32_t rest = mine ? q - h0 - h1 : 0u;
+        const uint32_t nB = Hq != 0u ? heard_byz(Hq, nb, rest, k0, k1, tlo, thi, c, r, 1u) : rest;
+        const uint32_t l1 = heard_lies(strategy, c, h0, h1, nB);
+        const uint32_t c0 = h0 + nB - l1, c1 = h1 + l1;
+        const bool d0l = c0 > F, d1l = !d0l && c1 > F;
+        const uint64_t d0 = ballot(d0l) & hp;
+        const uint64_t d1 = ballot(d1l) & hp;
+        const uint64_t left = hp & ~(d0 | d1);
+        uint64_t x1 = d1;
+        if (left) {
+          x1 |= ballot(c1 > c0) & left;
+          const uint64_t tie = ballot(c1 == c0) & left;                  // an empty tally included
+          if (tie) x1 |= coin_ballot(k0, k1, tlo, thi, j, r, tie);
+        }
+        if (mine && (d0l || d1l)) dec |= 1ull << j;                      // sticky
+        undecided = undecided || (mine && !((dec >> j) & 1ull));
+        if (lane == 0) X1[j] = (X1[j] & ~hp) | x1;                       // a Byzantine node's bit is never written
+      }
+      R = r;
+      all_dec = !__any(undecided);                 // over the honest nodes
+      if (all_dec) break;
+    }
+    __builtin_amdgcn_wave_barrier();
+    uint32_t K = 0;                                // the honest nodes with x = 1
+    for (uint32_t j = 0; j < W; ++j) K += (uint32_t)__builtin_popcountll(X1[j] & HP[j]);
+    K = uni(K);
+    const uint32_t v = (K != 0u && K != h) ? 2u : (K != 0u ? 1u : 0u);
+    if (lane == 0) {
+      atomicAdd(&lhist[all_dec ? (R * 3u + v) : v], 1u);
+      if (all_dec && v == 2u) atomicAdd(&lhist[p.hist_len - 1u], 1u);
+      if (p.rounds_out) *p.rounds_out = all_dec ? R : 0u;
+    }
+    if (states) {
+      for (uint32_t j = 0; j < W; ++j) {
+        const uint64_t d = ballot((dec >> j) & 1ull);
+        if (lane == 0) DEC[j] = d;
+      }
+      __builtin_amdgcn_wave_barrier();
+      for (uint32_t c = lane; c < m; c += 64u) {
+        const uint32_t j = c >> 6;
+        if (!((HP[j] >> lane) & 1ull)) continue;   // Byzantine: alive, no protocol state (the host's entry stays)
+        bo_node_state ns;
+        ns.killed = 0;
+        ns.x = (int8_t)((X1[j] >> lane) & 1ull);
+        ns.decided = (int8_t)((DEC[j] >> lane) & 1ull);
+        ns.pad = 0;
+        ns.k = (int32_t)R + 1;
+        p.node_out[p.live_ids[c]] = ns;
+      }
+    }
+  }
+
+  __syncthreads();
+  flush_hist(lhist, p);
+}
+
 }  // namespace
+
+// The strategies whose liars see the receiver's inbox run benor_tally_heard_kernel.
+bool byz_heard(const KParams &p) { return p.byz_strategy == BO_BYZ_BALANCE || p.byz_strategy == BO_BYZ_SPLIT; }
 
 // A batch launch's per-wave LDS: four planes and the row region.
 uint32_t byz_wave_bytes(uint32_t W, uint32_t cap) {
@@ -331,8 +556,8 @@ bool byz_thr_in_lds(uint32_t lds_bytes, uint32_t b) {
 // Workgroups of the kernel that one CU holds at once (registers and LDS; 0 = unknown).
 int byz_blocks_per_cu(const KParams &p) {
   int n = 0;
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, benor_tally_byz_kernel, 64 * kWavesPerBlock,
-                                                                    p.lds_bytes);
+  const auto kernel = byz_heard(p) ? benor_tally_heard_kernel : benor_tally_byz_kernel;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 64 * kWavesPerBlock, p.lds_bytes);
   return e == hipSuccess ? n : 0;
 }
 
@@ -342,16 +567,18 @@ hipError_t launch_tally_byz(const KParams &plan, int grid, hipStream_t s) {
     p.wave_bytes += byz_state_bytes(p.W);
     p.lds_bytes += kWavesPerBlock * byz_state_bytes(p.W);
   }
-  if (!p.tally_off || !p.tally_thr || !p.byz_plane || !p.byz_thr || p.W > kMaxW || p.byz_n == 0u ||
-      p.byz_n > p.m - p.q || plan.wave_bytes < byz_wave_bytes(p.W, p.tally_cap) ||
+  const bool heard = byz_heard(p);                 // BO_BYZ_BALANCE, BO_BYZ_SPLIT: no thresholds, none in LDS
+  if (!p.tally_off || !p.tally_thr || !p.byz_plane || (heard ? p.byz_lds != 0u : !p.byz_thr) || p.W > kMaxW ||
+      p.byz_n == 0u || p.byz_n > p.m - p.q || plan.wave_bytes < byz_wave_bytes(p.W, p.tally_cap) ||
       plan.lds_bytes < p.hist_bytes + kWavesPerBlock * plan.wave_bytes + (p.byz_lds ? 8u * p.byz_n : 0u))
     return hipErrorInvalidValue;
+  const auto kernel = heard ? benor_tally_heard_kernel : benor_tally_byz_kernel;
   if (p.lds_bytes > 64u * 1024u) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&benor_tally_byz_kernel),
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(benor_tally_byz_kernel, dim3(grid), dim3(64 * kWavesPerBlock), p.lds_bytes, s, p);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * kWavesPerBlock), p.lds_bytes, s, p);
   return hipGetLastError();
 }
 

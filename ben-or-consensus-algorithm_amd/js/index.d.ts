@@ -116,9 +116,12 @@ export interface TrialsConfig {
   /** MODE_BYZ_TALLY: the probability, in units of 2^-32, that a Byzantine message carries 1, independently per
    *  trial, sender, receiver, round and phase (0 .. 2^32 - 1: certainly); it fills the word that crashCut fills */
   byzOne?: number;
-  /** MODE_BYZ_TALLY: BYZ_RANDOM (default; each message by byzOne) or BYZ_OPPOSE (every message carries the value
-   *  fewer honest senders hold at the step, byzOne's step on a tie); it fills the word that crashCount fills */
-  byzStrategy?: 0 | 1;
+  /** MODE_BYZ_TALLY: BYZ_RANDOM (default; each message by byzOne), BYZ_OPPOSE (every message carries the value
+   *  fewer honest senders hold at the step, byzOne's step on a tie), BYZ_BALANCE (the Byzantine messages in a
+   *  receiver's inbox make its two tallies as equal as they can) or BYZ_SPLIT (they say 1 to a receiver of odd
+   *  compact index, 0 to one of even index); the last two do not read byzOne.  It fills the word that crashCount
+   *  fills */
+  byzStrategy?: 0 | 1 | 3 | 4;
 }
 
 /** TrialsConfig.mode values (include/benor.h BO_MODE_*). */
@@ -135,9 +138,11 @@ export declare const MODE_CRASH_SUBSET: 7;
 /** TrialsConfig.crashReach: every crasher reaches every receiver (include/benor.h, crash_reach = UINT32_MAX). */
 export declare const REACH_ALL: 4294967295;
 export declare const MODE_BYZ_TALLY: 8;
-/** TrialsConfig.byzStrategy (include/benor.h BO_BYZ_RANDOM, BO_BYZ_OPPOSE). */
+/** TrialsConfig.byzStrategy (include/benor.h BO_BYZ_RANDOM, BO_BYZ_OPPOSE, BO_BYZ_BALANCE, BO_BYZ_SPLIT). */
 export declare const BYZ_RANDOM: 0;
 export declare const BYZ_OPPOSE: 1;
+export declare const BYZ_BALANCE: 3;
+export declare const BYZ_SPLIT: 4;
 
 /** Outcome histogram, (kMax + 1) * 3 + 1 bins (include/benor.h). */
 export declare function runTrials(cfg: TrialsConfig): Promise<BigUint64Array>;

@@ -181,19 +181,45 @@ enum {
  *   BO_BYZ_OPPOSE: at each step every Byzantine message carries the value held by
  *     fewer honest senders at that step -- 0 if H1 > H0, 1 if H0 > H1 -- the same
  *     to every receiver; on H0 == H1 the step is BO_BYZ_RANDOM's with byz_one.
+ *   BO_BYZ_BALANCE, BO_BYZ_SPLIT: the Byzantine senders see the receiver's inbox
+ *     before they choose (below); byz_one is not read, every value is valid.
  *   Any other strategy is BO_ERR_INVALID_ARGUMENT.
  * H0, H1, Hq are the class sizes over the honest senders at the step (a sender's
  * x at an R-step, its proposal at a P-step; decided nodes keep sending).
  * Receiver c's (c0, c1) is RANDOM_TALLY3's draw among m senders with the class
  * sizes (H0 + b - B1, H1 + B1, Hq), from its stream-5 uniform and stream-6 walk.
+ * Under BO_BYZ_BALANCE and BO_BYZ_SPLIT the Byzantine messages are
+ * a class of their own inside the draw, which has two stages per (receiver c,
+ * round r, phase):
+ *   1. (h0, h1), the honest 0s and 1s heard, is RANDOM_TALLY3's draw among m
+ *      senders with the class sizes (H0, H1, Hq + b), from the same stream-5
+ *      uniform and stream-6 walk; rest = q - h0 - h1 messages come from the
+ *      merged class of Hq honest "?" and b Byzantine senders.
+ *   2. nB ~ Hypergeometric(Hq + b, b, rest) of them are Byzantine.  Hq == 0:
+ *      nB = rest; rest == 0: nB = 0; neither draws.  Otherwise the smaller
+ *      sub-class is walked by RANDOM_TALLY3's selection sampling: KW = min(b, Hq)
+ *      members, the Byzantine class on a tie; member i is in the inbox iff
+ *      v_i < rest - (members taken so far), v_i uniform below Hq + b - i by the
+ *      same multiply-shift with exact rejection, from the words .x .y .z .w of
+ *      the Philox4x32-10 blocks ctr = {trial_lo, trial_hi, c | blk << 12,
+ *      (r-1) | phase << 16 | 11 << 24}, blk = 0, 1, .., key = seed (stream 11).
+ *      nB is the number taken if the Byzantine class was walked, else rest
+ *      minus it.
+ * The nB Byzantine senders then see (h0, h1); l1 of them say 1 and nB - l1 say 0,
+ * (c0, c1) = (h0 + nB - l1, h1 + l1), in both phases:
+ *   BO_BYZ_BALANCE: the receiver's two tallies as equal as the lies allow: with
+ *     d = h0 + nB - h1 (signed), l1 = 0 if d <= 0, else min(nB, floor(d / 2)).  A
+ *     liveness attack and a heuristic, not the optimal adversary.
+ *   BO_BYZ_SPLIT: l1 = nB if the receiver's compact index c is odd, else 0: the
+ *     classic equivocation attack on agreement.
  * Rule, coins, k and the histogram layout are RANDOM_TALLY3's.  The run halts
  * after the round in which every honest node has decided; the outcome and the
  * common value are taken over the honest nodes.  bo_run_trial_states reports a
  * Byzantine node as {killed 0, x -1, decided -1, k -1}: alive, no protocol state.
  * b = 0 is RANDOM_TALLY3's plan at every byz_one and strategy: its kernel choice
  * and its results bit for bit.  Not modelled: Byzantine nodes together with
- * crashes during the run, a strategy that reads a receiver's inbox, explicit lie
- * masks.  Batch API only (no network API, no `sweep`). */
+ * crashes during the run, lies that say "?", explicit lie masks.  Batch API only
+ * (no network API, no `sweep`). */
 enum {
   BO_MODE_LOCKSTEP = 0,
   BO_MODE_RANDOM_DELIVERY = 1,
@@ -207,7 +233,8 @@ enum {
 };
 
 /* BO_MODE_BYZ_TALLY, byz_strategy. */
-enum { BO_BYZ_RANDOM = 0, BO_BYZ_OPPOSE = 1 };
+/* (2 is not a strategy: it stays BO_ERR_INVALID_ARGUMENT, as it was before BALANCE and SPLIT existed) */
+enum { BO_BYZ_RANDOM = 0, BO_BYZ_OPPOSE = 1, BO_BYZ_BALANCE = 3, BO_BYZ_SPLIT = 4 };
 
 /* BO_MODE_CRASH_PARTIAL, crash_cut: a cut per trial and crasher, uniform on 0..m0. */
 #define BO_CUT_RANDOM 0xFFFFFFFFu
@@ -372,7 +399,7 @@ typedef struct bo_trials_cfg {
     const uint32_t *crash_at; /* host [N] or NULL */
     union {                   /* one word, the layout of the struct is that of ABI version 8 */
         uint32_t crash_count;
-        uint32_t byz_strategy; /* BYZ_TALLY: BO_BYZ_RANDOM or BO_BYZ_OPPOSE */
+        uint32_t byz_strategy; /* BYZ_TALLY: a BO_BYZ_* strategy */
     };
     uint32_t crash_window;
 } bo_trials_cfg;

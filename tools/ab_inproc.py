@@ -45,14 +45,18 @@ mode:partial with a full cut, both on its own kernel:
 
 `mode:byz` (BO_MODE_BYZ_TALLY) takes `byzantine` (the b live nodes after the crashed
 ones lie), `byz_one` (`all`, a probability with a decimal point or the 32-bit word) and
-`byz_strategy` (random or oppose); next to mode:tally3 it times what the liars cost:
+`byz_strategy` (random, oppose, balance or split; the last two read the receiver's inbox
+and not `byz_one`); next to mode:tally3 it times what the liars cost:
 
     python tools/ab_inproc.py --rounds 7 --reps 5 --shapes "1024,340,100000,0" --variants \
         "t3=mode:tally3;half=mode:byz,byzantine:100,byz_one:0.5;all=mode:byz,byzantine:100,byz_one:all;opp=mode:byz,byzantine:100,byz_one:0.5,byz_strategy:oppose"
+    python tools/ab_inproc.py --rounds 7 --reps 5 --shapes "1024,340,100000,0" --variants \
+        "t3=mode:tally3;half=mode:byz,byzantine:100,byz_one:0.5;bal=mode:byz,byzantine:100,byz_strategy:balance;split=mode:byz,byzantine:100,byz_strategy:split"
 
 Every line also reports
-the live node-rounds per second its launches represent (bench.py node_rounds),
-so variants that change the outcome (a diagnostic cap) compare per unit of work.
+the live node-rounds per second its launches represent (bench.py node_rounds)
+and the rounds a trial ran on average (k_max for an undecided one),
+so variants that change the outcome (a diagnostic cap, a lie strategy) compare per unit of work.
 """
 import argparse
 import json
@@ -124,7 +128,8 @@ def main():
             b, one = int(sc.get("byzantine", 0)), sc.get("byz_one", "0.5")
             return {"byzantine": [f <= i < f + b for i in range(N)],
                     "byz_one": 0xFFFFFFFF if one == "all" else benor.reach_word(float(one)) if "." in one else int(one),
-                    "byz_strategy": {"random": benor.BYZ_RANDOM, "oppose": benor.BYZ_OPPOSE}[sc.get("byz_strategy", "random")]}
+                    "byz_strategy": {"random": benor.BYZ_RANDOM, "oppose": benor.BYZ_OPPOSE, "balance": benor.BYZ_BALANCE,
+                                     "split": benor.BYZ_SPLIT}[sc.get("byz_strategy", "random")]}
         cut = sc.pop("crash_cut", None)
         reach = sc.pop("crash_reach", None)
         if "crash_at" in sc:
@@ -155,7 +160,7 @@ def main():
             os.environ.pop(k, None)
         os.environ.update(env)
 
-    times, work = {}, {}
+    times, work, length = {}, {}, {}
     for N, F, T, f in shapes:
         dflt = benor.BO_MODE_RANDOM_DELIVERY if f < F else benor.BO_MODE_LOCKSTEP
         plans = {}                                    # one plan per delivery mode the variants name
@@ -186,8 +191,9 @@ def main():
                 torch.cuda.synchronize()
                 ms = e0.elapsed_time(e1) / a.reps
                 times.setdefault((N, F, T, f, name), []).append(ms)
-                nr, _ = node_rounds(h.cpu().numpy().astype(np.uint64), N - f, 32)
+                nr, tr = node_rounds(h.cpu().numpy().astype(np.uint64), N - f, 32)
                 work.setdefault((N, F, T, f, name), []).append(nr / a.reps / (ms * 1e-3))
+                length.setdefault((N, F, T, f, name), []).append(tr / (a.reps * T))
     set_env({})
     for N, F, T, f in shapes:
         base = statistics.median(times[(N, F, T, f, variants[0][0])])
@@ -199,6 +205,7 @@ def main():
                               "trials_per_s": T / (statistics.median(t) * 1e-3),
                               "us_per_trial": statistics.median(t) * 1e3 / T, **scheds[name],
                               "node_rounds_per_s": statistics.median(work[(N, F, T, f, name)]),
+                              "rounds_per_trial": statistics.median(length[(N, F, T, f, name)]),
                               "kernel_version": benor.kernel_version()}), flush=True)
 
 
