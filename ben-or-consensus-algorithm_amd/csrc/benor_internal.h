@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "benor.h"
+#include "benor_mfma_sched.h"
 
 namespace benor {
 
@@ -121,7 +122,8 @@ struct KParams {
   uint32_t defer_seg_cap;
   // per-plan device flag word, set (atomic OR) when a launch broke a capacity
   // invariant -- bit 0: an owner deferred more than defer_seg_cap trials (its
-  // extra trials are dropped); bit 1: an event-level message pool filled up.
+  // extra trials are dropped); bit 1: an event-level message pool filled up;
+  // bit 2: the dynamic matrix-core form's claim counter was off at the end.
   // The launch's histogram is then incomplete; bo_plan_check / bo_plan_run
   // report BO_ERR_INTERNAL.
   uint32_t *overflow;
@@ -152,8 +154,10 @@ struct KParams {
   // round r of the trials trial_begin + trial_list[i], i < *trial_list_len,
   // which tied in every round before r (x = their round r-1 coins); 0: round 1
   uint32_t cont_round;
-  // diagnostics (BENOR_TIMELINE=<file>, packed matrix-core kernel): per wave,
-  // kTimelineWords u64 -- wall-clock stamps of its phases and its batch counts
+  // diagnostics (BENOR_TIMELINE=<file>): per wave, kTimelineWords u64 -- packed
+  // matrix-core kernel: wall-clock stamps of its phases and its batch counts;
+  // matrix-core kernel (benor_mfma.h): [0] entry and [1] last-group stamps, [2]
+  // groups run, [3] XCC, [4] SE and [5] CU (SH << 4 | CU) ids, [6] HW_ID, [7] claims
   unsigned long long *timeline;
   // count-level random delivery with crashes during the run (variant 11; last, so that the
   // fields above keep their offsets): m is the initially-live count m0 and
@@ -183,6 +187,11 @@ struct KParams {
   const unsigned long long *byz_plane;
   const unsigned long long *byz_thr;
   uint32_t byz_n, byz_strategy, byz_one, byz_lds;
+  // matrix-core kernel, KIND 0, dynamic form (benor_mfma_sched.h): the plan's
+  // claim words (`next` at 0, `done` at sched::kDoneWord; both 0 between
+  // launches) and the chunk C, set per launch; mfma_chunk = 0: the static form
+  uint32_t *mfma_claim;
+  uint32_t mfma_chunk;
 };
 
 constexpr uint32_t kTimelineWords = 12;
@@ -322,6 +331,13 @@ bool small_on_lane(const KParams &p);
 template <int W>
 hipError_t launch_mfma(const KParams &p, int grid_blocks, hipStream_t stream);
 hipError_t launch_mfma_big(const KParams &p, int grid_blocks, hipStream_t stream);
+// KIND 0's default (paired) instantiation for W: resident workgroups per CU at
+// its dynamic LDS size (the occupancy query; 0 = unknown).
+template <int W>
+int mfma_sure_blocks_per_cu(const KParams &p);
+// Scheduling of a KIND 0 batch launch of W <= 16 (benor_mfma_sched.h): the
+// chunk C of the dynamic form, or 0 for the static one.
+uint32_t mfma_chunk(const KParams &p, int device);
 uint32_t mfma_big_lds_bytes(const KParams &p, uint32_t block_waves);   // dynamic LDS of one workgroup of the big form
 uint32_t mfma_big_block_waves(const KParams &p);                       // its waves per workgroup (1, 2 or 4)
 // Workgroup-cooperative big-network form (benor_mfma_coop.hip): the waves of a

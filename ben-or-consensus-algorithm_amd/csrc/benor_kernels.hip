@@ -885,6 +885,48 @@ bool small_on_lane(const KParams &p) {
   return p.trial_count < knob_u32("BENOR_SMALL_MIN_TRIALS", (uint32_t)kSmallMinTrials);
 }
 
+template <int... Is>
+static int dispatch_mfma_blocks(const KParams &p, std::integer_sequence<int, Is...>) {
+  int n = 0;
+  (void)((p.W == (uint32_t)(Is + 2) ? (n = mfma_sure_blocks_per_cu<Is + 2>(p), true) : false) || ...);
+  return n;
+}
+
+// Resident workgroups per CU of the KIND 0 matrix-core kernel (W <= 16): the
+// occupancy query, 8 where it fails; the last answer is kept per thread.
+static uint32_t mfma_resident_per_cu(const KParams &p) {
+  struct Last {
+    uint32_t W, m, lds, v;
+  };
+  static thread_local Last last = {0u, 0u, 0u, 0u};
+  if (last.v && last.W == p.W && last.m == p.m && last.lds == p.hist_bytes) return last.v;
+  const int n = dispatch_mfma_blocks(p, std::make_integer_sequence<int, 15>{});
+  const uint32_t v = n >= 1 && n <= 8 ? (uint32_t)n : 8u;
+  last = Last{p.W, p.m, p.hist_bytes, v};
+  return v;
+}
+
+// The planner's rule (benor_mfma_sched.h) for a KIND 0 batch launch of the
+// paired kernel.  BENOR_MFMA_DYNAMIC (validation): "0" static, "1" dynamic on
+// any such launch; BENOR_MFMA_CHUNK (tuning): C of the dynamic form, 1..64.
+uint32_t mfma_chunk(const KParams &p, int device) {
+  if (p.variant != 7 || p.G != 0u || p.W > 16u || p.node_out || p.rounds_out) return 0u;
+  const bool forced = knob_is("BENOR_MFMA_DYNAMIC", "1");
+  if (knob_is("BENOR_MFMA_DYNAMIC", "0") || knob_is("BENOR_MFMA_PAIR", "0")) return 0u;
+  int cus = 256;
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+  const uint32_t MT = 2u * p.W - (p.m <= 64u * (p.W - 1u) + 32u ? 1u : 0u);
+  const uint64_t ngroups = (p.trial_count + 31u) / 32u;
+  sched::Rule r = sched::rule(p.W, MT, ngroups, 0u);
+  if (!forced && r.chunk > sched::kMaxChunk) return 0u;          // no occupancy query for the short-group shapes
+  r = sched::rule(p.W, MT, ngroups, (uint64_t)mfma_resident_per_cu(p) * (uint64_t)cus * kWavesPerBlock);
+  if (!forced && !r.dynamic) return 0u;
+  uint32_t c = r.chunk < sched::kMaxChunk ? r.chunk : sched::kMaxChunk;
+  const uint32_t v = knob_u32("BENOR_MFMA_CHUNK", 0u);
+  if (v >= 1u && v <= 64u) c = v;
+  return c;
+}
+
 int lockstep_grid(const KParams &p, int device) {
   int cus = 256;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
@@ -983,9 +1025,14 @@ int lockstep_grid(const KParams &p, int device) {
     const uint64_t v = want < 2u ? 2u : want;
     if (v < per_cu) per_cu = v;
   }
-  {                                          // tuning knob (tools/lane_grid_sweep.py)
+  // Matrix-core kernel, dynamic form (p.mfma_chunk, benor_mfma_sched.h): the
+  // resident workgroups, which claim their groups; the static form keeps 8 per
+  // CU, in rounds of the resident ones.
+  const bool mfma_small_w = mfma && p.W <= 16u;
+  if (mfma_small_w && p.mfma_chunk) per_cu = mfma_resident_per_cu(p);
+  {                                          // tuning knob (tools/lane_grid_sweep.py); matrix-core kernel: 1..16
     const uint64_t v = knob_u32("BENOR_BLOCKS_PER_CU", 0u);
-    if (v >= 1u && v < per_cu) per_cu = v;
+    if (mfma_small_w ? v >= 1u && v <= 16u : v >= 1u && v < per_cu) per_cu = v;
   }
   uint64_t grid = (uint64_t)cus * per_cu;
   if (blocks_needed < grid) grid = blocks_needed;

@@ -81,16 +81,46 @@
 //    (profiles/r11-a_mfma_pair_forms_ab.jsonl), and bench.py 22.95 / 22.97 ->
 //    22.61 / 22.63 ms per step against the parent commit, alternated on one
 //    box (profiles/r11-c_bench_parent_pair.jsonl): a gain of 1-1.5 %.
+//  * Scheduling (benor_mfma_sched.h has the rule and the protocol,
+//    tests/mfma_sched_check.cpp their host check).  Static form: wave w runs
+//    groups w, w + waves, ... on 8 workgroups per CU.  At 165 VGPRs three
+//    workgroups are resident per CU, so the 8 live in rounds of 3 + 3 + 2 and a
+//    wave's share is fixed at launch although waves on one SIMD run at very
+//    different rates.  Dynamic form (KIND 0, paired, DYN): the resident
+//    workgroups only (the occupancy query), and each wave claims chunks of C
+//    consecutive groups with one returning atomic add by lane 0 on a
+//    plan-owned word.  The next claim is issued before the current chunk's
+//    groups and read after them, so its latency (1.4-3 us) hides behind ~8
+//    groups of ~21 us; the last wave to arrive checks the word (KParams::overflow
+//    bit 2 otherwise) and zeroes both for the next launch.  No wave waits for
+//    another.  The planner (mfma_chunk) takes it where C = ceil(groups per us /
+//    20) <= 16 and the launch has >= 4 C groups per resident wave: C = 8 at the
+//    headline, 4 at m = 1023; W <= 7 and short launches stay static, as
+//    do KIND 1, 2 (their deferral segments are sized from the stride) and the
+//    one-tile form.  BENOR_TIMELINE at the headline (tools/timeline_report.py,
+//    profiles/r15_timeline_{static,dynamic}.md): a CU's wave slots are filled
+//    88.4 % of the span in the static form and 99.5 % in the dynamic one, the
+//    waves' end times spread over 83 % and 1.0 % of it, and a dynamic wave runs
+//    168 .. 2272 groups against the static 381 / 382.  In one process, median
+//    of 7 rounds (profiles/r15_mfma_sched_ab.jsonl): headline 22.07 -> 21.37 ms
+//    (0.968, ranges 21.94-22.34 and 21.33-21.49), N=1000/F=333 0.973, N=1023/F=0
+//    0.987; static at 3 or 9 workgroups per CU is slower than at 8 (1.036,
+//    1.007), and C = 4, 8, 16 are within 0.7 % of each other.
 #pragma once
 
 #include "benor_device.h"
 #include "benor_mfma_pair.h"
+#include "benor_mfma_sched.h"
 
 namespace benor {
 
 typedef int mf_v4i __attribute__((ext_vector_type(4)));
 typedef int mf_v8i __attribute__((ext_vector_type(8)));
 typedef float mf_v16f __attribute__((ext_vector_type(16)));
+
+// s_getreg operands (id | (size - 1) << 11, offset 0): the whole HW_ID
+// (SE_ID 15:13, SH_ID 12, CU_ID 11:8) and XCC_ID (3:0) registers.
+constexpr int kHwRegHwId = 4 | (31 << 11), kHwRegXccId = 20 | (31 << 11);
 
 // 32 receivers x 32 trials x 64 senders, e2m1 operands; A scaled by 2^SA
 // (E8M0 127 + SA), B unit scale.
@@ -174,10 +204,37 @@ __device__ __forceinline__ uint32_t pack_pair4(const mf_v16f &acc, int base) {
   return (x & pairf::kMaskX) | (y & pairf::kMaskY);
 }
 
+// The claim words of the dynamic form as benor_mfma_sched.h's atomics policy
+// (one lane of a wave calls it): agent-scope atomics on the plan's two words.
+struct ClaimWords {
+  uint32_t *w;
+  __device__ __forceinline__ uint32_t claim(uint32_t C) {
+    // The address in VGPRs: on a uniform address the compiler's atomic
+    // optimizer rewrites the add as a wave reduction whose broadcast reads
+    // the result at once, and the claim's latency could not hide.  A global
+    // pointer: a flat atomic would also count in the LDS reads' lgkmcnt.
+    auto q = (__attribute__((address_space(1))) uint32_t *)w;
+    asm volatile("" : "+v"(q));
+    return __hip_atomic_fetch_add(q, C, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __device__ __forceinline__ uint32_t arrive() {
+    return __hip_atomic_fetch_add(w + sched::kDoneWord, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __device__ __forceinline__ uint32_t take_next() {
+    return __hip_atomic_exchange(w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __device__ __forceinline__ void clear_done() {
+    __hip_atomic_store(w + sched::kDoneWord, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+};
+
 // PAIR (KIND 0 only): two receiver tiles per accumulator instead of one.
-template <int W, bool HALF, int KIND, bool PAIR = false>
+// DYN (the paired form only): the waves claim chunks of p.mfma_chunk groups
+// from the plan's claim words (benor_mfma_sched.h) instead of striding.
+template <int W, bool HALF, int KIND, bool PAIR = false, bool DYN = false>
 __global__ void __launch_bounds__(256) benor_mfma_kernel(KParams p) {
   static_assert(!PAIR || KIND == 0, "the paired form is KIND 0's");
+  static_assert(!DYN || PAIR, "dynamic claims are the paired form's");
   constexpr int MT = 2 * W - (HALF ? 1 : 0);   // 32-receiver tiles (HALF: the last chunk holds <= 32 senders)
   constexpr int KP = (MT + 1) / 2;             // P-phase K chunks: two tiles' results each
   constexpr int NB = (W + 1) / 2;              // Philox init blocks per trial (128 senders each)
@@ -295,7 +352,31 @@ __global__ void __launch_bounds__(256) benor_mfma_kernel(KParams p) {
   // list p.defer_list at the end with one atomic per wave.
   uint32_t n_def = 0;
   uint32_t *seg = SURE ? nullptr : p.defer_seg + (size_t)wave_id * p.defer_seg_cap;
-  for (uint32_t g = wave_id; g < ngroups; g += waves_total) {
+  // diagnostics (BENOR_TIMELINE): this wave's slot, stamped outside the group loop
+  unsigned long long *tl = p.timeline ? p.timeline + (size_t)wave_id * kTimelineWords : nullptr;
+  if (tl && lane == 0u) tl[0] = (unsigned long long)wall_clock64();
+  // Dynamic form (benor_mfma_sched.h): lane 0 claims chunks of C groups; the
+  // next claim is issued before the current chunk's groups and read after
+  // them (`pending`, lane 0's VGPR), so its latency hides behind the products.
+  [[maybe_unused]] ClaimWords cw{p.mfma_claim};
+  [[maybe_unused]] const uint32_t C = DYN ? p.mfma_chunk : 0u;
+  [[maybe_unused]] uint32_t pending = 0u, g_end = 0u, n_run = 0u, n_claims = 0u;
+  if constexpr (DYN) {
+    if (lane == 0u) pending = sched::claim(cw, C);
+  }
+  for (uint32_t g = DYN ? 0u : wave_id; DYN || g < ngroups; g += DYN ? 1u : waves_total) {
+    if constexpr (DYN) {
+      if (g == g_end) {
+        asm volatile("" : "+v"(pending));      // read here, behind the chunk: the wait for the claim sits here too
+        const uint32_t base = (uint32_t)__builtin_amdgcn_readfirstlane((int)pending);
+        if (base >= ngroups) break;            // this wave's one failing claim
+        g = base;
+        g_end = sched::chunk_end(base, ngroups, C);
+        n_run += g_end - base;
+        ++n_claims;
+        if (lane == 0u) pending = sched::claim(cw, C);
+      }
+    }
     const uint32_t t = (g << 5) + (lane & 31u);
     const bool valid = t < trial_count;
     const uint32_t toff = cont ? (valid ? p.trial_list[t] : 0u) : t;   // the trial's offset in the launch
@@ -619,6 +700,21 @@ __global__ void __launch_bounds__(256) benor_mfma_kernel(KParams p) {
     f_1 += (uint32_t)__builtin_popcount(any1);
     f_2 += (uint32_t)__builtin_popcount(any1 & any0);
   }
+  if (tl && lane == 0u) {
+    tl[1] = (unsigned long long)wall_clock64();
+    if constexpr (!DYN) n_run = wave_id < ngroups ? (ngroups - wave_id + waves_total - 1u) / waves_total : 0u;
+    const uint32_t hw = __builtin_amdgcn_s_getreg(kHwRegHwId), xcc = __builtin_amdgcn_s_getreg(kHwRegXccId);
+    tl[2] = n_run;
+    tl[3] = xcc & 0xFu;
+    tl[4] = (hw >> 13) & 0x7u;                 // SE_ID
+    tl[5] = (hw >> 8) & 0x1Fu;                 // SH_ID << 4 | CU_ID
+    tl[6] = hw;
+    tl[7] = n_claims;
+  }
+  if constexpr (DYN) {
+    // the arrival count and, for the last wave, the invariant and the reset
+    if (lane == 0u && !sched::finish(cw, ngroups, waves_total, C)) atomicOr(p.overflow, sched::kInvariantBit);
+  }
   if constexpr (!SURE) {
     // The waves' deferred trials -> the compact list, one global atomic per
     // workgroup: atomics on one counter serialise across the grid (~12 ns
@@ -658,20 +754,33 @@ __global__ void __launch_bounds__(256) benor_mfma_kernel(KParams p) {
   flush_hist(lhist, p);
 }
 
-template <int W, int KIND, bool PAIR = false>
+template <int W, int KIND, bool PAIR = false, bool DYN = false>
 static inline void launch_mfma_kind(const KParams &p, int grid, hipStream_t s) {
   if (p.m <= 64u * (uint32_t)(W - 1) + 32u)
-    hipLaunchKernelGGL((benor_mfma_kernel<W, true, KIND, PAIR>), dim3(grid), dim3(64 * kWavesPerBlock), p.hist_bytes, s, p);
+    hipLaunchKernelGGL((benor_mfma_kernel<W, true, KIND, PAIR, DYN>), dim3(grid), dim3(64 * kWavesPerBlock), p.hist_bytes, s, p);
   else
-    hipLaunchKernelGGL((benor_mfma_kernel<W, false, KIND, PAIR>), dim3(grid), dim3(64 * kWavesPerBlock), p.hist_bytes, s, p);
+    hipLaunchKernelGGL((benor_mfma_kernel<W, false, KIND, PAIR, DYN>), dim3(grid), dim3(64 * kWavesPerBlock), p.hist_bytes, s, p);
 }
 
 // KIND 0's form: two receiver tiles per accumulator; BENOR_MFMA_PAIR=0
-// (validation) runs the one-tile form on the same trials.
+// (validation) runs the one-tile form on the same trials, always statically
+// scheduled.  p.mfma_chunk > 0 (mfma_chunk(), per launch): the dynamic form.
 template <int W>
 static inline void launch_mfma_sure(const KParams &p, int grid, hipStream_t s) {
   if (knob_is("BENOR_MFMA_PAIR", "0")) launch_mfma_kind<W, 0, false>(p, grid, s);
+  else if (p.mfma_chunk && p.mfma_claim) launch_mfma_kind<W, 0, true, true>(p, grid, s);
   else launch_mfma_kind<W, 0, true>(p, grid, s);
+}
+
+template <int W>
+int mfma_sure_blocks_per_cu(const KParams &p) {
+  int n = 0;
+  const hipError_t e =
+      p.m <= 64u * (uint32_t)(W - 1) + 32u
+          ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, benor_mfma_kernel<W, true, 0, true, true>, 64 * kWavesPerBlock, p.hist_bytes)
+          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, benor_mfma_kernel<W, false, 0, true, true>, 64 * kWavesPerBlock, p.hist_bytes);
+  if (e != hipSuccess) (void)hipGetLastError();
+  return e == hipSuccess ? n : 0;
 }
 
 template <int W>

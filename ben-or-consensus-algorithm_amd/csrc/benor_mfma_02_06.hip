@@ -5,10 +5,15 @@
 
 namespace benor {
 template hipError_t launch_mfma<2>(const KParams &, int, hipStream_t);
+template int mfma_sure_blocks_per_cu<2>(const KParams &);
 template hipError_t launch_mfma<3>(const KParams &, int, hipStream_t);
+template int mfma_sure_blocks_per_cu<3>(const KParams &);
 template hipError_t launch_mfma<4>(const KParams &, int, hipStream_t);
+template int mfma_sure_blocks_per_cu<4>(const KParams &);
 template hipError_t launch_mfma<5>(const KParams &, int, hipStream_t);
+template int mfma_sure_blocks_per_cu<5>(const KParams &);
 template hipError_t launch_mfma<6>(const KParams &, int, hipStream_t);
+template int mfma_sure_blocks_per_cu<6>(const KParams &);
 }  // namespace benor
 
 namespace benor {

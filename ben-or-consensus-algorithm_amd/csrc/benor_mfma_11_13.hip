@@ -5,6 +5,9 @@
 
 namespace benor {
 template hipError_t launch_mfma<11>(const KParams &, int, hipStream_t);
+template int mfma_sure_blocks_per_cu<11>(const KParams &);
 template hipError_t launch_mfma<12>(const KParams &, int, hipStream_t);
+template int mfma_sure_blocks_per_cu<12>(const KParams &);
 template hipError_t launch_mfma<13>(const KParams &, int, hipStream_t);
+template int mfma_sure_blocks_per_cu<13>(const KParams &);
 }  // namespace benor

@@ -5,6 +5,9 @@
 
 namespace benor {
 template hipError_t launch_mfma<14>(const KParams &, int, hipStream_t);
+template int mfma_sure_blocks_per_cu<14>(const KParams &);
 template hipError_t launch_mfma<15>(const KParams &, int, hipStream_t);
+template int mfma_sure_blocks_per_cu<15>(const KParams &);
 template hipError_t launch_mfma<16>(const KParams &, int, hipStream_t);
+template int mfma_sure_blocks_per_cu<16>(const KParams &);
 }  // namespace benor

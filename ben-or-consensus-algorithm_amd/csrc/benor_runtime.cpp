@@ -81,6 +81,8 @@ constexpr KnobSpec kKnobs[] = {
     {"BENOR_NO_MFMA", "validation"},            // "1": popcount kernels instead of the matrix-core ones
     {"BENOR_NO_MFMA_BIG", "validation"},        // "1": popcount kernels for m > 1024
     {"BENOR_MFMA_PAIR", "validation"},          // "0": KIND 0 matrix-core kernel, one receiver tile per accumulator
+    {"BENOR_MFMA_DYNAMIC", "validation"},       // "0" / "1": KIND 0 matrix-core kernel, static stride / claimed chunks
+    {"BENOR_MFMA_CHUNK", "tuning"},             // its dynamic form: groups per claim (1..64)
     {"BENOR_BIG_FORM", "validation"},           // "wave" / "coop": big-network matrix-core form
     {"BENOR_COOP_BW", "validation"},            // 4 / 8: waves per cooperative workgroup
     {"BENOR_SMALL_MIN_TRIALS", "validation"},   // packed matrix-core kernel from this launch size
@@ -90,7 +92,7 @@ constexpr KnobSpec kKnobs[] = {
     {"BENOR_LIVE_WAVES", "tuning"},             // 1 / 3 / 7 / 15: event waves of the workgroup-batched kernel
     {"BENOR_EVENT_STATS", "diagnostic"},        // workgroup-batched kernel: batch counters and cycle split to a file
     {"BENOR_TEST_DEFER_SEG_CAP", "test"},       // deferral segment capacity below the sizing rule
-    {"BENOR_TIMELINE", "diagnostic"},           // packed matrix-core kernel: per-wave phase stamps to a file
+    {"BENOR_TIMELINE", "diagnostic"},           // packed and KIND 0 matrix-core kernels: per-wave stamps to a file
 };
 
 const char *knob(const char *name) {
@@ -142,6 +144,7 @@ struct bo_plan {
   uint32_t *d_defer = nullptr;     // matrix-core KIND > 0: deferred-trial list, its length, per-wave segments
   uint64_t defer_words = 0;
   uint32_t *d_flag = nullptr;      // KParams::overflow (bo_plan_check)
+  uint32_t *d_claim = nullptr;     // KParams::mfma_claim: the claim words of the matrix-core kernel's dynamic form
   uint64_t *d_stops = nullptr;     // event level, N > 256: sorted /stop schedule
   unsigned char *d_tally = nullptr;   // RANDOM_TALLY: u32 row offsets [m + 2] (padded to 8 bytes), u64 thresholds;
                                       // CRASH_TALLY: directory, row offsets, explicit schedule list, thresholds
@@ -780,6 +783,14 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
     if (e == hipSuccess) e = hipMemset(pl->d_flag, 0, sizeof(uint32_t));
     if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "plan flag"); }
   }
+  if (kp.variant == 7 && kp.G == 0u && kp.W <= 16u) {
+    // benor.h orders a plan's launches on one stream, and every launch leaves
+    // the words 0 (benor_mfma_sched.h): one pair per plan, zeroed once
+    hipError_t e = hipMalloc(&pl->d_claim, sizeof(uint32_t) * benor::sched::kWords);
+    if (e == hipSuccess) e = hipMemset(pl->d_claim, 0, sizeof(uint32_t) * benor::sched::kWords);
+    if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "plan claim words"); }
+    kp.mfma_claim = pl->d_claim;
+  }
   if (m > 0) {
     hipError_t e = hipMalloc(&pl->d_live, sizeof(uint32_t) * m);
     if (e == hipSuccess) e = hipMalloc(&pl->d_init, sizeof(uint4) * kp.W);
@@ -941,6 +952,7 @@ void bo_plan_destroy(bo_plan *pl) {
   if (pl->d_scratch) (void)hipFree(pl->d_scratch);
   if (pl->d_defer) (void)hipFree(pl->d_defer);
   if (pl->d_flag) (void)hipFree(pl->d_flag);
+  if (pl->d_claim) (void)hipFree(pl->d_claim);
   if (pl->d_stops) (void)hipFree(pl->d_stops);
   if (pl->d_tally) (void)hipFree(pl->d_tally);
   delete pl;
@@ -972,7 +984,9 @@ uint64_t bo_plan_popc_words_per_node_round(const bo_plan *pl) {
 }
 
 // Diagnostics (BENOR_TIMELINE=<file>): the packed matrix-core kernel stamps
-// each wave's phases; one CSV line per wave is appended to the file
+// each wave's phases, the KIND 0 matrix-core kernel each wave's entry and last
+// group, with its group count and its XCC, SE and CU ids (kernel=mfma in the
+// header line); one CSV line per wave is appended to the file
 // (tools/timeline_report.py).  Synchronous; not for timing the launch itself.
 static hipError_t launch_with_timeline(benor::KParams kp, int grid, hipStream_t s, const char *path) {
   const size_t words = (size_t)grid * benor::kWavesPerBlock * benor::kTimelineWords;
@@ -988,8 +1002,10 @@ static hipError_t launch_with_timeline(benor::KParams kp, int grid, hipStream_t 
   (void)hipFree(d);
   if (e != hipSuccess) return e;
   if (FILE *f = std::fopen(path, "a")) {
-    std::fprintf(f, "# launch m=%u trials=%llu grid=%d waves=%d\n", kp.m, (unsigned long long)kp.trial_count, grid,
+    std::fprintf(f, "# launch m=%u trials=%llu grid=%d waves=%d", kp.m, (unsigned long long)kp.trial_count, grid,
                  grid * benor::kWavesPerBlock);
+    if (kp.variant == 7) std::fprintf(f, " kernel=mfma chunk=%u", kp.mfma_chunk);
+    std::fprintf(f, "\n");
     for (size_t w = 0; w < (size_t)grid * benor::kWavesPerBlock; ++w) {
       const unsigned long long *t = h.data() + w * benor::kTimelineWords;
       std::fprintf(f, "%zu", w);
@@ -1110,8 +1126,10 @@ static int plan_launch_impl(bo_plan *pl, uint64_t trial_begin, uint64_t trial_co
     const uint64_t n = std::min<uint64_t>(trial_count - done, benor::kMaxTrialsPerLaunch);
     kp.trial_begin = trial_begin + done;
     kp.trial_count = n;
+    kp.mfma_chunk = benor::mfma_chunk(kp, pl->device);   // KIND 0 matrix-core launch: static (0) or dynamic
     const int grid = benor::lockstep_grid(kp, pl->device);
-    const char *tl_path = kp.variant == 8 ? benor::knob("BENOR_TIMELINE") : nullptr;
+    const bool mfma_sure = kp.variant == 7 && kp.G == 0u && kp.W <= 16u && !node_out && !rounds_out;
+    const char *tl_path = kp.variant == 8 || mfma_sure ? benor::knob("BENOR_TIMELINE") : nullptr;
     if (tl_path) {
       HIP_TRY(launch_with_timeline(kp, grid, s, tl_path));
     } else {
@@ -1179,6 +1197,9 @@ int plan_flag_error(uint32_t v) {
   if (v & 1u)
     return fail(BO_ERR_INTERNAL, "a matrix-core launch deferred more trials than its segment holds: "
                                  "its histogram is incomplete (deferral segment sizing)");
+  if (v & benor::sched::kInvariantBit)
+    return fail(BO_ERR_INTERNAL, "a matrix-core launch ended with its claim counter off: "
+                                 "groups were skipped or run twice (benor_mfma_sched.h)");
   return fail(BO_ERR_INTERNAL, "an event-level message pool filled up: the affected trials stopped early");
 }
 }  // namespace
