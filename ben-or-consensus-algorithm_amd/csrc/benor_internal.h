@@ -230,47 +230,23 @@ hipError_t launch_lockstep(const KParams &p, int grid_blocks, hipStream_t stream
 uint32_t random_bern_rows(uint32_t m, uint32_t b);
 hipError_t launch_random_bern(const KParams &p, int grid_blocks, hipStream_t stream);
 
-// Count-level random delivery (benor_tally.hip): per-wave LDS (x ballots and
-// one table row).
-uint32_t tally_wave_bytes(uint32_t W, uint32_t cap);
-int tally_blocks_per_cu(const KParams &p);        // resident workgroups per CU (registers, LDS); 0 = unknown
+// The count-level kernels (their per-wave LDS sizes: benor_tally_common.h).
+// *_blocks_per_cu: resident workgroups per CU (registers, LDS); 0 = unknown.
+int tally_blocks_per_cu(const KParams &p);        // benor_tally.hip: count-level random delivery
 hipError_t launch_tally(const KParams &p, int grid_blocks, hipStream_t stream);
-
-// Three-valued count-level random delivery (benor_tally3.hip): the same per-wave
-// LDS (a phase hands on its class sizes only; "?" is held by no node after round 1).
-int tally3_blocks_per_cu(const KParams &p);       // resident workgroups per CU (registers, LDS); 0 = unknown
+int tally3_blocks_per_cu(const KParams &p);       // benor_tally3.hip: three-valued
 hipError_t launch_tally3(const KParams &p, int grid_blocks, hipStream_t stream);
-
-// Count-level random delivery with crashes during the run (benor_tally_crash.hip):
-// per-wave LDS of a batch launch (four ballot planes, one staged row, the schedule
-// list and, for a random schedule whose row region is too small for them, a pass
-// of stream-7 words); a per-node-state launch adds two planes by itself.
-uint32_t crash_wave_bytes(uint32_t W, uint32_t cap, uint32_t ncr, bool random);
-uint32_t crash_state_bytes(uint32_t W);
-int crash_blocks_per_cu(const KParams &p);        // resident workgroups per CU (registers, LDS); 0 = unknown
+int crash_blocks_per_cu(const KParams &p);        // benor_tally_crash.hip: with crashes during the run
 hipError_t launch_tally_crash(const KParams &p, int grid_blocks, hipStream_t stream);
-
-// ... and with partial broadcasts (benor_tally_partial.hip): the same layout plus the
-// step's crasher list (cut and vote class per entry).
-uint32_t partial_wave_bytes(uint32_t W, uint32_t cap, uint32_t ncr, bool random);
-int partial_blocks_per_cu(const KParams &p);      // resident workgroups per CU (registers, LDS); 0 = unknown
+int partial_blocks_per_cu(const KParams &p);      // benor_tally_partial.hip: ... and partial broadcasts
 hipError_t launch_tally_partial(const KParams &p, int grid_blocks, hipStream_t stream);
-
-// ... and with broadcasts that reach a random subset (benor_tally_subset.hip): the same
-// layout, the list holding compact index and vote class per entry.
-uint32_t subset_wave_bytes(uint32_t W, uint32_t cap, uint32_t ncr, bool random);
-int subset_blocks_per_cu(const KParams &p);       // resident workgroups per CU (registers, LDS); 0 = unknown
+int subset_blocks_per_cu(const KParams &p);       // benor_tally_subset.hip: ... that reach a random subset
 hipError_t launch_tally_subset(const KParams &p, int grid_blocks, hipStream_t stream);
-
-// Count-level random delivery with Byzantine senders (benor_tally_byz.hip): per-wave LDS
-// of a batch launch (four ballot planes and one staged row; a per-node-state launch adds
-// a decided plane by itself), and whether the workgroup keeps the b Binomial thresholds
-// in LDS behind the waves' regions (byz_thr_in_lds: when that costs no resident workgroup).
-uint32_t byz_wave_bytes(uint32_t W, uint32_t cap);
-uint32_t byz_state_bytes(uint32_t W);
+// benor_tally_byz.hip: with Byzantine senders; whether the workgroup keeps the b Binomial thresholds
+// in LDS behind the waves' regions (byz_thr_in_lds: when that costs no resident workgroup)
 bool byz_thr_in_lds(uint32_t lds_bytes, uint32_t b);
 bool byz_heard(const KParams &p);                 // BO_BYZ_BALANCE, BO_BYZ_SPLIT: the kernel without thresholds
-int byz_blocks_per_cu(const KParams &p);          // resident workgroups per CU (registers, LDS); 0 = unknown
+int byz_blocks_per_cu(const KParams &p);
 hipError_t launch_tally_byz(const KParams &p, int grid_blocks, hipStream_t stream);
 
 // Event level for kMaxEventN < N <= BO_MAX_N (benor_event_big.hip): one wave per trial.

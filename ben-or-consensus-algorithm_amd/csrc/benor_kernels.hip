@@ -36,6 +36,7 @@
 #include <stdlib.h>
 
 #include "benor_device.h"
+#include "benor_tally_common.h"
 
 #include <cstring>
 
@@ -643,62 +644,31 @@ void plan_geometry(KParams &p) {
     p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
     return;
   }
-  if (p.mode == BO_MODE_RANDOM_TALLY || p.mode == BO_MODE_RANDOM_TALLY3) {
-    // count-level random delivery (benor_tally.hip); three-valued: benor_tally3.hip, the same LDS layout
+  if (p.mode == BO_MODE_RANDOM_TALLY || p.mode == BO_MODE_RANDOM_TALLY3 || p.mode == BO_MODE_CRASH_TALLY ||
+      p.mode == BO_MODE_CRASH_PARTIAL || p.mode == BO_MODE_CRASH_SUBSET || p.mode == BO_MODE_BYZ_TALLY) {
+    // The count-level kernels (benor_tally*.hip; layouts: benor_tally_common.h).  The row region is the
+    // widest row of HG(m, ., q): no pool of the crash family exceeds m0, and the Byzantine kernels run on
+    // mode 4's table.
     p.G = 1;
     p.nblocks = W;
-    p.variant = p.mode == BO_MODE_RANDOM_TALLY ? 9u : 10u;
-    const uint32_t e = p.m - p.q;
-    p.tally_cap = p.q <= e ? p.q : e;               // the widest row of HG(m, ., q)
-    p.wave_bytes = (tally_wave_bytes(W, p.tally_cap) + 15u) & ~15u;   // x ballots + one staged row
-    p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
-    return;
-  }
-  if (p.mode == BO_MODE_CRASH_TALLY) {
-    // ... with crashes during the run (benor_tally_crash.hip): the row region is the m0 table's widest row
-    p.G = 1;
-    p.nblocks = W;
-    p.variant = 11u;
     const uint32_t e = p.m - p.q;
     p.tally_cap = p.q <= e ? p.q : e;
-    p.wave_bytes = (crash_wave_bytes(W, p.tally_cap, p.cr_n, p.cr_random != 0u) + 15u) & ~15u;
+    const bool random = p.cr_random != 0u;
+    uint32_t bytes;
+    switch (p.mode) {
+      case BO_MODE_RANDOM_TALLY: p.variant = 9u, bytes = tally_wave_bytes(W, p.tally_cap); break;
+      case BO_MODE_RANDOM_TALLY3: p.variant = 10u, bytes = tally_wave_bytes(W, p.tally_cap); break;
+      case BO_MODE_CRASH_TALLY: p.variant = 11u, bytes = crash_wave_bytes(W, p.tally_cap, p.cr_n, random, false); break;
+      case BO_MODE_CRASH_PARTIAL: p.variant = 12u, bytes = crash_wave_bytes(W, p.tally_cap, p.cr_n, random, true); break;
+      case BO_MODE_CRASH_SUBSET: p.variant = 13u, bytes = crash_wave_bytes(W, p.tally_cap, p.cr_n, random, true); break;
+      default: p.variant = 14u, bytes = byz_wave_bytes(W, p.tally_cap); break;
+    }
+    p.wave_bytes = (bytes + 15u) & ~15u;
     p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
-    return;
-  }
-  if (p.mode == BO_MODE_CRASH_PARTIAL) {
-    // ... and partial broadcasts (benor_tally_partial.hip): no pool exceeds m0, so the same row region
-    p.G = 1;
-    p.nblocks = W;
-    p.variant = 12u;
-    const uint32_t e = p.m - p.q;
-    p.tally_cap = p.q <= e ? p.q : e;
-    p.wave_bytes = (partial_wave_bytes(W, p.tally_cap, p.cr_n, p.cr_random != 0u) + 15u) & ~15u;
-    p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
-    return;
-  }
-  if (p.mode == BO_MODE_CRASH_SUBSET) {
-    // ... or broadcasts that reach a random subset (benor_tally_subset.hip): the same pools, the same row region
-    p.G = 1;
-    p.nblocks = W;
-    p.variant = 13u;
-    const uint32_t e = p.m - p.q;
-    p.tally_cap = p.q <= e ? p.q : e;
-    p.wave_bytes = (subset_wave_bytes(W, p.tally_cap, p.cr_n, p.cr_random != 0u) + 15u) & ~15u;
-    p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
-    return;
-  }
-  if (p.mode == BO_MODE_BYZ_TALLY) {
-    // three-valued count-level random delivery with Byzantine senders (benor_tally_byz.hip): mode 4's
-    // table and row region; the Binomial thresholds ride in LDS when that costs no resident workgroup
-    p.G = 1;
-    p.nblocks = W;
-    p.variant = 14u;
-    const uint32_t e = p.m - p.q;
-    p.tally_cap = p.q <= e ? p.q : e;
-    p.wave_bytes = (byz_wave_bytes(W, p.tally_cap) + 15u) & ~15u;
-    p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
-    p.byz_lds = !byz_heard(p) && byz_thr_in_lds(p.lds_bytes, p.byz_n) ? 1u : 0u;   // (the inbox-reading strategies have none)
-    if (p.byz_lds) p.lds_bytes += 8u * p.byz_n;
+    if (p.variant == 14u) {   // the Binomial thresholds ride in LDS when that costs no resident workgroup
+      p.byz_lds = !byz_heard(p) && byz_thr_in_lds(p.lds_bytes, p.byz_n) ? 1u : 0u;   // (the inbox-reading strategies have none)
+      if (p.byz_lds) p.lds_bytes += 8u * p.byz_n;
+    }
     return;
   }
   if (p.m <= kMaxLaneM) {                           // lane kernel: one trial per lane
@@ -927,6 +897,18 @@ uint32_t mfma_chunk(const KParams &p, int device) {
   return c;
 }
 
+// Resident workgroups per CU of the count-level kernel of variant 9..14 (0 = unknown).
+static int count_level_blocks_per_cu(const KParams &p) {
+  switch (p.variant) {
+    case 9: return tally_blocks_per_cu(p);
+    case 10: return tally3_blocks_per_cu(p);
+    case 11: return crash_blocks_per_cu(p);
+    case 12: return partial_blocks_per_cu(p);
+    case 13: return subset_blocks_per_cu(p);
+    default: return byz_blocks_per_cu(p);
+  }
+}
+
 int lockstep_grid(const KParams &p, int device) {
   int cus = 256;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
@@ -986,28 +968,8 @@ int lockstep_grid(const KParams &p, int device) {
     const uint64_t lds_fit = lds_groups_per_cu(lds);
     if (lds_fit < per_cu) per_cu = lds_fit ? lds_fit : 1;
   }
-  if (p.variant == 9) {                      // count-level random delivery: its unrolled forms are register-bound
-    const uint64_t fit = (uint64_t)tally_blocks_per_cu(p);
-    if (fit >= 1u && fit < per_cu) per_cu = fit;
-  }
-  if (p.variant == 10) {                     // its three-valued form: one kernel for every W
-    const uint64_t fit = (uint64_t)tally3_blocks_per_cu(p);
-    if (fit >= 1u && fit < per_cu) per_cu = fit;
-  }
-  if (p.variant == 11) {                     // ... and its form with crashes during the run
-    const uint64_t fit = (uint64_t)crash_blocks_per_cu(p);
-    if (fit >= 1u && fit < per_cu) per_cu = fit;
-  }
-  if (p.variant == 12) {                     // ... and with partial broadcasts
-    const uint64_t fit = (uint64_t)partial_blocks_per_cu(p);
-    if (fit >= 1u && fit < per_cu) per_cu = fit;
-  }
-  if (p.variant == 13) {                     // ... that reach a random subset
-    const uint64_t fit = (uint64_t)subset_blocks_per_cu(p);
-    if (fit >= 1u && fit < per_cu) per_cu = fit;
-  }
-  if (p.variant == 14) {                     // ... and its form with Byzantine senders
-    const uint64_t fit = (uint64_t)byz_blocks_per_cu(p);
+  if (p.variant >= 9 && p.variant <= 14) {   // the count-level kernels are register-bound (benor_tally.hip: per unroll)
+    const uint64_t fit = (uint64_t)count_level_blocks_per_cu(p);
     if (fit >= 1u && fit < per_cu) per_cu = fit;
   }
   // Lane kernel: a short launch spread over every wave slot (~2 trials per

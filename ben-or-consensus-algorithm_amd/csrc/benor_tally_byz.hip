@@ -18,11 +18,11 @@
 // kernel of this file, benor_tally_heard_kernel (further down).
 //
 // One wave = one trial, lane l of receiver group j = compact index 64 j + l over
-// the m live nodes, as in benor_tally_crash.hip, whose helpers this kernel runs
-// on.  Its alive plane is here the honest plane HP, constant per plan: class
-// sizes are popcounts of the x and proposal planes ANDed with it, a group without
-// an honest lane draws nothing, and a Byzantine lane never writes a plane bit.  A
-// step is one of two kinds, wave-uniformly:
+// the m live nodes, as in benor_tally_crash.hip, on the same helpers
+// (benor_tally_common.h).  Its alive plane is here the honest plane HP,
+// constant per plan: class sizes are popcounts of the x and proposal planes ANDed
+// with it, a group without an honest lane draws nothing, and a Byzantine lane
+// never writes a plane bit.  A step is one of two kinds, wave-uniformly:
 //   * every receiver hears the same Byzantine messages (OPPOSE off a tie, byz_one 0
 //     or UINT32_MAX): the phase is set up once with its row staged in LDS and the
 //     honest lanes draw from it (phase_setup and draw3, mode 4's step with shifted
@@ -30,7 +30,7 @@
 //   * each receiver has a B1 of its own: one stream-10 block per lane next to the
 //     stream-5 block, a binary search of the Binomial thresholds, and one per-lane
 //     draw from the lane's own row of the (m, q) table in global memory
-//     (benor_tally_subset.hip's draw3_own with one table and no directory).
+//     (draw3_lane, as benor_tally_subset.hip, with one table and no directory).
 //     Neighbouring lanes' B1 differ by O(sqrt b), so the rows they touch lie close.
 // The thresholds, 8 b <= 32 KiB shared by every trial, are copied into LDS once
 // per workgroup, behind the four waves' regions, when that costs no resident
@@ -42,7 +42,7 @@
 // with the honest nodes in the place of the alive ones; a Byzantine node's state is
 // not written (the host reports it).  No floating point runs on the device, and no
 // launch leaves overflow or deferral state.
-#include "benor_tally_crash.h"
+#include "benor_tally_common.h"
 
 namespace benor {
 
@@ -51,87 +51,20 @@ namespace {
 constexpr uint32_t kByzCertain = 0xFFFFFFFFu;      // KParams::byz_one: every Byzantine message carries 1
 constexpr uint32_t kByzWgPerCu = 6u;               // resident workgroups the registers allow (__launch_bounds__ below)
 
-// #{ j < n : thr[j] <= u } in global memory: row_count's search from the largest power of
-// two not above n (a probe at or beyond n fails).
-__device__ __forceinline__ uint32_t count_global(const unsigned long long *__restrict__ thr, uint32_t n, uint64_t u) {
-  uint32_t pos = 0u;
-  for (uint32_t st = 1u << (31u - (uint32_t)__builtin_clz(n | 1u)); st != 0u; st >>= 1) {
-    const uint32_t i = pos + st - 1u;
-    if (i < n && thr[i] <= u) pos += st;
-  }
-  return pos;
-}
-
-// draw3 for a lane with class sizes of its own among the m senders: phase_setup's class
-// choice, row_count and draw3's walk with every quantity per lane, the row searched where
-// it lies in global memory (the plan's one table).  K0 + K1 <= m; a lane that is not
-// `active` loads nothing and its result is not used.
-__device__ __forceinline__ void draw3_lane(const KParams &p, uint32_t K0, uint32_t K1, uint32_t k0, uint32_t k1,
-                                           uint32_t tlo, uint32_t thi, uint32_t c, uint32_t r, uint32_t phase,
-                                           uint64_t u, bool active, uint32_t &c0, uint32_t &c1) {
-  const uint32_t m = p.m, q = p.q, Kq = m - K0 - K1;
-  uint32_t sel, KS, KA;
-  if (Kq <= K0 && Kq <= K1) sel = 0u, KS = Kq, KA = K1;
-  else if (K0 <= K1) sel = 1u, KS = K0, KA = K1;
-  else sel = 2u, KS = K1, KA = K0;
-  uint32_t cA = KA + q > m ? KA + q - m : 0u;
-  if (active && KA != 0u && KA != m && m != q) {   // else the row is a point
-    const uint32_t o = p.tally_off[KA];
-    uint32_t n = p.tally_off[KA + 1u] - o;
-    if (n > p.tally_cap) n = p.tally_cap;
-    cA += count_global(p.tally_thr + o, n, u);
-  }
-  if (!active) KS = 0u;
-  uint32_t cS = 0u;
-  if (m == q) {
-    cS = KS;                                       // every sender is in the inbox
-  } else {
-    const uint32_t slots = q - cA;                 // inbox slots left to the senders outside A
-    const uint32_t dtop = m - KA;                  // ... of which there are this many (>= slots, >= KS)
-    const uint32_t c3 = (r - 1u) | (phase << 16) | (kStreamWalk << 24);
-    uint32_t i = 0;
-    const auto word = [&](uint32_t w) {
-      if (i < KS) {
-        const uint32_t d = dtop - i;               // member i's denominator, >= 1
-        const uint64_t mm = (uint64_t)w * d;
-        const uint32_t l = (uint32_t)mm;
-        bool ok = true;
-        if (l < d) ok = l >= (0u - d) % d;
-        if (ok) {
-          if ((uint32_t)(mm >> 32) < slots - cS) ++cS;
-          ++i;
-        }
-      }
-    };
-    for (uint32_t blk = 0; __any(i < KS); ++blk) {
-      const uint4 b = philox4x32_10(k0, k1, make_uint4(tlo, thi, c | (blk << 12), c3));
-      word(b.x), word(b.y), word(b.z), word(b.w);
-    }
-  }
-  const uint32_t cT = q - cA - cS;
-  c1 = sel == 2u ? cS : cA;
-  c0 = sel == 0u ? cT : (sel == 1u ? cS : cA);
-}
-
 // (six waves per SIMD: one more than benor_tally_crash.hip, there is no schedule and no alive plane to maintain)
 __global__ void __launch_bounds__(256, 6) benor_tally_byz_kernel(KParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wv = threadIdx.x >> 6;
   const uint32_t m = p.m, F = p.F, W = p.W, q = p.q, nb = p.byz_n;
-  const uint32_t WP = (W + 1u) & ~1u;
 
   uint32_t *lhist = reinterpret_cast<uint32_t *>(smem);
   const bool states = p.node_out != nullptr;       // a state launch: a DEC plane of its own
-  uint64_t *HP = reinterpret_cast<uint64_t *>(smem + p.hist_bytes + wv * p.wave_bytes);   // [W] honest (constant)
-  uint64_t *X1 = HP + WP;                                                                 // [W] x = 1
-  uint64_t *P1 = X1 + WP, *P0 = P1 + WP;                                                  // [W] proposals 1, 0
-  uint64_t *X0 = P0;                                                                      // [W] x = 0 (round 1)
-  uint64_t *DEC = P0 + WP;                                                                // [W] decided (state launch)
-  uint64_t *row = HP + (states ? 5u : 4u) * WP;                                           // [tally_cap] thresholds
+  const Planes S(smem + p.hist_bytes + wv * p.wave_bytes, byz_layout(W, p.tally_cap, states));
+  uint64_t *const HP = S.AL, *const X1 = S.X1, *const P1 = S.P1, *const P0 = S.P0, *const X0 = S.X0, *const row = S.row;
   uint64_t *BT = reinterpret_cast<uint64_t *>(smem + p.hist_bytes + kWavesPerBlock * p.wave_bytes);   // [b] (byz_lds)
   const bool in_lds = p.byz_lds != 0u;
-  const uint32_t bsteps = 32u - (uint32_t)__builtin_clz(nb | 1u);
+  const uint32_t bsteps = search_steps(nb);
 
   for (uint32_t i = threadIdx.x; i < p.hist_len; i += blockDim.x) lhist[i] = 0u;
   if (in_lds)
@@ -143,10 +76,7 @@ __global__ void __launch_bounds__(256, 6) benor_tally_byz_kernel(KParams p) {
   for (uint32_t j = 0; j < W; ++j) h += (uint32_t)__builtin_popcountll(HP[j]);
   h = uni(h);
 
-  Table tb;                                        // the plan's one table
-  tb.m = m;
-  tb.off = p.tally_off;
-  tb.thr = p.tally_thr;
+  const Table tb{m, p.tally_off, p.tally_thr};     // the plan's one table
 
   const uint32_t k0 = (uint32_t)p.seed, k1 = (uint32_t)(p.seed >> 32);
   const uint64_t waves_total = (uint64_t)gridDim.x * kWavesPerBlock;
@@ -162,36 +92,18 @@ __global__ void __launch_bounds__(256, 6) benor_tally_byz_kernel(KParams p) {
     B1u = p.byz_one == kByzCertain ? nb : 0u;
     return p.byz_one != 0u && p.byz_one != kByzCertain;
   };
+  // A lane with a B1 of its own searches its row of the one table where it lies in global memory.
+  const auto one_table = [&](uint32_t) { return tb; };
   // Receiver c's B1 from its stream-10 uniform.
   const auto lies = [&](uint64_t u) {
-    return in_lds ? row_count(BT, nb, bsteps, u) : count_global(p.byz_thr, nb, u);
+    return in_lds ? count_le(BT, nb, bsteps, u) : count_le<false>(p.byz_thr, nb, bsteps, u);
   };
 
   for (uint64_t t = (uint64_t)blockIdx.x * kWavesPerBlock + wv; t < p.trial_count; t += waves_total) {
     const uint64_t trial = p.trial_begin + t;
     const uint32_t tlo = uni((uint32_t)trial), thi = uni((uint32_t)(trial >> 32));
     __builtin_amdgcn_wave_barrier();               // the previous trial's state reads are done
-    if (p.init_mode == BO_INIT_RANDOM) {           // /start (node.ts:167-188): stream 1, as every batch mode
-      const uint32_t nph = (W + 1u) >> 1;
-      if (lane < nph) {
-        uint4 r;
-        if (m <= 32u) r = make_uint4(init_word_small(k0, k1, trial), 0u, 0u, 0u);   // shared block (m <= 32)
-        else r = philox4x32_10(k0, k1, make_uint4(tlo, thi, lane, kStreamInit << 24));
-        const uint32_t w0 = 2u * lane, w1 = w0 + 1u;
-        const uint64_t g0 = group_mask(w0, m), a0 = ((uint64_t)r.y << 32 | r.x) & g0;
-        X1[w0] = a0, X0[w0] = g0 & ~a0;
-        if (w1 < W) {
-          const uint64_t g1 = group_mask(w1, m), a1 = ((uint64_t)r.w << 32 | r.z) & g1;
-          X1[w1] = a1, X0[w1] = g1 & ~a1;
-        }
-      }
-    } else {
-      for (uint32_t w = lane; w < W; w += 64u) {
-        const uint4 rc = p.init_plane[w];
-        X0[w] = (uint64_t)rc.y << 32 | rc.x;
-        X1[w] = (uint64_t)rc.w << 32 | rc.z;
-      }
-    }
+    trial_start<true>(X1, X0, p, k0, k1, trial, tlo, thi, lane);
     __builtin_amdgcn_wave_barrier();
 
     uint64_t dec = 0ull;                           // bit j: node 64 j + lane has decided (sticky)
@@ -208,8 +120,7 @@ __global__ void __launch_bounds__(256, 6) benor_tally_byz_kernel(KParams p) {
       H1 = uni(H1);
       H0 = r == 1u ? uni(H0) : h - H1;             // after a P-phase every honest x is binary
       bool own = per_lane_step(H0, H1);
-      PhaseC ph;
-      ph.sel = 0u, ph.KA = 0u, ph.KS = 0u, ph.lo = 0u, ph.n = 0u, ph.steps = 0u;
+      PhaseC ph = phase_none();
       if (!own) ph = phase_setup(row, p, tb, H0 + nb - B1u, H1 + B1u, h - H0 - H1, lane);
       else __builtin_amdgcn_wave_barrier();        // the class sizes are read before P0 takes X0's words
       for (uint32_t j = 0; j < W; ++j) {
@@ -226,7 +137,8 @@ __global__ void __launch_bounds__(256, 6) benor_tally_byz_kernel(KParams p) {
           } else {
             const uint4 l = philox4x32_10(k0, k1, make_uint4(tlo, thi, c, (r - 1u) | (kStreamLie << 24)));
             const uint32_t B1 = lies((uint64_t)l.y << 32 | l.x);
-            draw3_lane(p, H0 + nb - B1, H1 + B1, k0, k1, tlo, thi, c, r, 0u, u, (hp >> lane) & 1ull, c0, c1);
+            draw3_lane(one_table, p.tally_cap, 0u, m, q, H0 + nb - B1, H1 + B1, k0, k1, tlo, thi, c, r, 0u, u,
+                       (hp >> lane) & 1ull, c0, c1);
           }
           p0 = ballot(c0 > c1) & hp;
           p1 = ballot(c1 > c0) & hp;
@@ -257,19 +169,12 @@ __global__ void __launch_bounds__(256, 6) benor_tally_byz_kernel(KParams p) {
         } else {
           const uint4 l = philox4x32_10(k0, k1, make_uint4(tlo, thi, c, (r - 1u) | (kStreamLie << 24)));
           const uint32_t B1 = lies((uint64_t)l.w << 32 | l.z);
-          draw3_lane(p, H0 + nb - B1, H1 + B1, k0, k1, tlo, thi, c, r, 1u, u, mine, c0, c1);
+          draw3_lane(one_table, p.tally_cap, 0u, m, q, H0 + nb - B1, H1 + B1, k0, k1, tlo, thi, c, r, 1u, u, mine, c0,
+                     c1);
         }
-        const bool d0l = c0 > F, d1l = !d0l && c1 > F;
-        const uint64_t d0 = ballot(d0l) & hp;
-        const uint64_t d1 = ballot(d1l) & hp;
-        const uint64_t rest = hp & ~(d0 | d1);
-        uint64_t x1 = d1;
-        if (rest) {
-          x1 |= ballot(c1 > c0) & rest;
-          const uint64_t tie = ballot(c1 == c0) & rest;                  // an empty tally included
-          if (tie) x1 |= coin_ballot(k0, k1, tlo, thi, j, r, tie);
-        }
-        if (mine && (d0l || d1l)) dec |= 1ull << j;                      // sticky
+        bool decided;
+        const uint64_t x1 = p_rule(c0, c1, F, hp, k0, k1, tlo, thi, j, r, decided);
+        if (mine && decided) dec |= 1ull << j;     // sticky
         undecided = undecided || (mine && !((dec >> j) & 1ull));
         if (lane == 0) X1[j] = (X1[j] & ~hp) | x1;                       // a Byzantine node's bit is never written
       }
@@ -281,30 +186,8 @@ __global__ void __launch_bounds__(256, 6) benor_tally_byz_kernel(KParams p) {
     uint32_t K = 0;                                // the honest nodes with x = 1
     for (uint32_t j = 0; j < W; ++j) K += (uint32_t)__builtin_popcountll(X1[j] & HP[j]);
     K = uni(K);
-    const uint32_t v = (K != 0u && K != h) ? 2u : (K != 0u ? 1u : 0u);
-    if (lane == 0) {
-      atomicAdd(&lhist[all_dec ? (R * 3u + v) : v], 1u);
-      if (all_dec && v == 2u) atomicAdd(&lhist[p.hist_len - 1u], 1u);
-      if (p.rounds_out) *p.rounds_out = all_dec ? R : 0u;
-    }
-    if (states) {
-      for (uint32_t j = 0; j < W; ++j) {
-        const uint64_t d = ballot((dec >> j) & 1ull);
-        if (lane == 0) DEC[j] = d;
-      }
-      __builtin_amdgcn_wave_barrier();
-      for (uint32_t c = lane; c < m; c += 64u) {
-        const uint32_t j = c >> 6;
-        if (!((HP[j] >> lane) & 1ull)) continue;   // Byzantine: alive, no protocol state (the host's entry stays)
-        bo_node_state ns;
-        ns.killed = 0;
-        ns.x = (int8_t)((X1[j] >> lane) & 1ull);
-        ns.decided = (int8_t)((DEC[j] >> lane) & 1ull);
-        ns.pad = 0;
-        ns.k = (int32_t)R + 1;
-        p.node_out[p.live_ids[c]] = ns;
-      }
-    }
+    trial_end(lhist, p, K, h, false, all_dec, R, lane);
+    if (states) write_states<false>(p, HP, X1, X0, S.DEC, nullptr, 0u, dec, R, lane);
   }
 
   __syncthreads();
@@ -332,22 +215,10 @@ __device__ __forceinline__ uint32_t heard_byz(uint32_t Hq, uint32_t nb, uint32_t
   const uint32_t dtop = Hq + nb;                   // >= rest, >= KW
   const uint32_t c3 = (r - 1u) | (phase << 16) | (kStreamHeard << 24);
   uint32_t i = 0, cS = 0;
-  const auto word = [&](uint32_t w) {
-    if (i < KW) {
-      const uint32_t d = dtop - i;                 // member i's denominator, >= 1
-      const uint64_t mm = (uint64_t)w * d;
-      const uint32_t l = (uint32_t)mm;
-      bool ok = true;
-      if (l < d) ok = l >= (0u - d) % d;
-      if (ok) {
-        if ((uint32_t)(mm >> 32) < rest - cS) ++cS;
-        ++i;
-      }
-    }
-  };
   for (uint32_t blk = 0; __any(i < KW && cS < rest); ++blk) {
     const uint4 b = philox4x32_10(k0, k1, make_uint4(tlo, thi, c | (blk << 12), c3));
-    word(b.x), word(b.y), word(b.z), word(b.w);
+    walk_word(b.x, KW, dtop, rest, i, cS), walk_word(b.y, KW, dtop, rest, i, cS);
+    walk_word(b.z, KW, dtop, rest, i, cS), walk_word(b.w, KW, dtop, rest, i, cS);
   }
   return walk_byz ? cS : rest - cS;
 }
@@ -369,16 +240,11 @@ __global__ void __launch_bounds__(256, 6) benor_tally_heard_kernel(KParams p) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wv = threadIdx.x >> 6;
   const uint32_t m = p.m, F = p.F, W = p.W, q = p.q, nb = p.byz_n, strategy = p.byz_strategy;
-  const uint32_t WP = (W + 1u) & ~1u;
 
   uint32_t *lhist = reinterpret_cast<uint32_t *>(smem);
   const bool states = p.node_out != nullptr;       // a state launch: a DEC plane of its own
-  uint64_t *HP = reinterpret_cast<uint64_t *>(smem + p.hist_bytes + wv * p.wave_bytes);   // [W] honest (constant)
-  uint64_t *X1 = HP + WP;                                                                 // [W] x = 1
-  uint64_t *P1 = X1 + WP, *P0 = P1 + WP;                                                  // [W] proposals 1, 0
-  uint64_t *X0 = P0;                                                                      // [W] x = 0 (round 1)
-  uint64_t *DEC = P0 + WP;                                                                // [W] decided (state launch)
-  uint64_t *row = HP + (states ? 5u : 4u) * WP;                                           // [tally_cap] thresholds
+  const Planes S(smem + p.hist_bytes + wv * p.wave_bytes, byz_layout(W, p.tally_cap, states));
+  uint64_t *const HP = S.AL, *const X1 = S.X1, *const P1 = S.P1, *const P0 = S.P0, *const X0 = S.X0, *const row = S.row;
 
   for (uint32_t i = threadIdx.x; i < p.hist_len; i += blockDim.x) lhist[i] = 0u;
   for (uint32_t w = lane; w < W; w += 64u) HP[w] = p.byz_plane[w];
@@ -388,10 +254,7 @@ __global__ void __launch_bounds__(256, 6) benor_tally_heard_kernel(KParams p) {
   for (uint32_t j = 0; j < W; ++j) h += (uint32_t)__builtin_popcountll(HP[j]);
   h = uni(h);
 
-  Table tb;                                        // the plan's one table
-  tb.m = m;
-  tb.off = p.tally_off;
-  tb.thr = p.tally_thr;
+  const Table tb{m, p.tally_off, p.tally_thr};     // the plan's one table
 
   const uint32_t k0 = (uint32_t)p.seed, k1 = (uint32_t)(p.seed >> 32);
   const uint64_t waves_total = (uint64_t)gridDim.x * kWavesPerBlock;
@@ -400,27 +263,7 @@ __global__ void __launch_bounds__(256, 6) benor_tally_heard_kernel(KParams p) {
     const uint64_t trial = p.trial_begin + t;
     const uint32_t tlo = uni((uint32_t)trial), thi = uni((uint32_t)(trial >> 32));
     __builtin_amdgcn_wave_barrier();               // the previous trial's state reads are done
-    if (p.init_mode == BO_INIT_RANDOM) {           // /start (node.ts:167-188): stream 1, as every batch mode
-      const uint32_t nph = (W + 1u) >> 1;
-      if (lane < nph) {
-        uint4 r;
-        if (m <= 32u) r = make_uint4(init_word_small(k0, k1, trial), 0u, 0u, 0u);   // shared block (m <= 32)
-        else r = philox4x32_10(k0, k1, make_uint4(tlo, thi, lane, kStreamInit << 24));
-        const uint32_t w0 = 2u * lane, w1 = w0 + 1u;
-        const uint64_t g0 = group_mask(w0, m), a0 = ((uint64_t)r.y << 32 | r.x) & g0;
-        X1[w0] = a0, X0[w0] = g0 & ~a0;
-        if (w1 < W) {
-          const uint64_t g1 = group_mask(w1, m), a1 = ((uint64_t)r.w << 32 | r.z) & g1;
-          X1[w1] = a1, X0[w1] = g1 & ~a1;
-        }
-      }
-    } else {
-      for (uint32_t w = lane; w < W; w += 64u) {
-        const uint4 rc = p.init_plane[w];
-        X0[w] = (uint64_t)rc.y << 32 | rc.x;
-        X1[w] = (uint64_t)rc.w << 32 | rc.z;
-      }
-    }
+    trial_start<true>(X1, X0, p, k0, k1, trial, tlo, thi, lane);
     __builtin_amdgcn_wave_barrier();
 
     uint64_t dec = 0ull;                           // bit j: node 64 j + lane has decided (sticky)
@@ -479,17 +322,9 @@ __global__ void __launch_bounds__(256, 6) benor_tally_heard_kernel(KParams p) {
         const uint32_t nB = Hq != 0u ? heard_byz(Hq, nb, rest, k0, k1, tlo, thi, c, r, 1u) : rest;
         const uint32_t l1 = heard_lies(strategy, c, h0, h1, nB);
         const uint32_t c0 = h0 + nB - l1, c1 = h1 + l1;
-        const bool d0l = c0 > F, d1l = !d0l && c1 > F;
-        const uint64_t d0 = ballot(d0l) & hp;
-        const uint64_t d1 = ballot(d1l) & hp;
-        const uint64_t left = hp & ~(d0 | d1);
-        uint64_t x1 = d1;
-        if (left) {
-          x1 |= ballot(c1 > c0) & left;
-          const uint64_t tie = ballot(c1 == c0) & left;                  // an empty tally included
-          if (tie) x1 |= coin_ballot(k0, k1, tlo, thi, j, r, tie);
-        }
-        if (mine && (d0l || d1l)) dec |= 1ull << j;                      // sticky
+        bool decided;
+        const uint64_t x1 = p_rule(c0, c1, F, hp, k0, k1, tlo, thi, j, r, decided);
+        if (mine && decided) dec |= 1ull << j;     // sticky
         undecided = undecided || (mine && !((dec >> j) & 1ull));
         if (lane == 0) X1[j] = (X1[j] & ~hp) | x1;                       // a Byzantine node's bit is never written
       }
@@ -501,30 +336,8 @@ __global__ void __launch_bounds__(256, 6) benor_tally_heard_kernel(KParams p) {
     uint32_t K = 0;                                // the honest nodes with x = 1
     for (uint32_t j = 0; j < W; ++j) K += (uint32_t)__builtin_popcountll(X1[j] & HP[j]);
     K = uni(K);
-    const uint32_t v = (K != 0u && K != h) ? 2u : (K != 0u ? 1u : 0u);
-    if (lane == 0) {
-      atomicAdd(&lhist[all_dec ? (R * 3u + v) : v], 1u);
-      if (all_dec && v == 2u) atomicAdd(&lhist[p.hist_len - 1u], 1u);
-      if (p.rounds_out) *p.rounds_out = all_dec ? R : 0u;
-    }
-    if (states) {
-      for (uint32_t j = 0; j < W; ++j) {
-        const uint64_t d = ballot((dec >> j) & 1ull);
-        if (lane == 0) DEC[j] = d;
-      }
-      __builtin_amdgcn_wave_barrier();
-      for (uint32_t c = lane; c < m; c += 64u) {
-        const uint32_t j = c >> 6;
-        if (!((HP[j] >> lane) & 1ull)) continue;   // Byzantine: alive, no protocol state (the host's entry stays)
-        bo_node_state ns;
-        ns.killed = 0;
-        ns.x = (int8_t)((X1[j] >> lane) & 1ull);
-        ns.decided = (int8_t)((DEC[j] >> lane) & 1ull);
-        ns.pad = 0;
-        ns.k = (int32_t)R + 1;
-        p.node_out[p.live_ids[c]] = ns;
-      }
-    }
+    trial_end(lhist, p, K, h, false, all_dec, R, lane);
+    if (states) write_states<false>(p, HP, X1, X0, S.DEC, nullptr, 0u, dec, R, lane);
   }
 
   __syncthreads();
@@ -536,15 +349,6 @@ __global__ void __launch_bounds__(256, 6) benor_tally_heard_kernel(KParams p) {
 // The strategies whose liars see the receiver's inbox run benor_tally_heard_kernel.
 bool byz_heard(const KParams &p) { return p.byz_strategy == BO_BYZ_BALANCE || p.byz_strategy == BO_BYZ_SPLIT; }
 
-// A batch launch's per-wave LDS: four planes and the row region.
-uint32_t byz_wave_bytes(uint32_t W, uint32_t cap) {
-  const uint32_t WP = (W + 1u) & ~1u, capE = (cap + 1u) & ~1u;
-  return (4u * WP + capE) * 8u;
-}
-
-// ... and what a per-node-state launch adds to it: the DEC plane.
-uint32_t byz_state_bytes(uint32_t W) { return ((W + 1u) & ~1u) * 8u; }
-
 // The b Binomial thresholds go into LDS, once per workgroup, when a CU then holds as many
 // workgroups as without them: the fewer of what `lds_bytes` (histogram and the four waves'
 // regions) allows and the six that the registers allow.
@@ -555,31 +359,17 @@ bool byz_thr_in_lds(uint32_t lds_bytes, uint32_t b) {
 
 // Workgroups of the kernel that one CU holds at once (registers and LDS; 0 = unknown).
 int byz_blocks_per_cu(const KParams &p) {
-  int n = 0;
-  const auto kernel = byz_heard(p) ? benor_tally_heard_kernel : benor_tally_byz_kernel;
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 64 * kWavesPerBlock, p.lds_bytes);
-  return e == hipSuccess ? n : 0;
+  return blocks_per_cu(byz_heard(p) ? benor_tally_heard_kernel : benor_tally_byz_kernel, p);
 }
 
 hipError_t launch_tally_byz(const KParams &plan, int grid, hipStream_t s) {
-  KParams p = plan;
-  if (p.node_out) {                                // a state launch (one trial): one more plane per wave
-    p.wave_bytes += byz_state_bytes(p.W);
-    p.lds_bytes += kWavesPerBlock * byz_state_bytes(p.W);
-  }
+  const KParams p = state_launch(plan, byz_state_bytes(plan.W));
   const bool heard = byz_heard(p);                 // BO_BYZ_BALANCE, BO_BYZ_SPLIT: no thresholds, none in LDS
   if (!p.tally_off || !p.tally_thr || !p.byz_plane || (heard ? p.byz_lds != 0u : !p.byz_thr) || p.W > kMaxW ||
       p.byz_n == 0u || p.byz_n > p.m - p.q || plan.wave_bytes < byz_wave_bytes(p.W, p.tally_cap) ||
       plan.lds_bytes < p.hist_bytes + kWavesPerBlock * plan.wave_bytes + (p.byz_lds ? 8u * p.byz_n : 0u))
     return hipErrorInvalidValue;
-  const auto kernel = heard ? benor_tally_heard_kernel : benor_tally_byz_kernel;
-  if (p.lds_bytes > 64u * 1024u) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * kWavesPerBlock), p.lds_bytes, s, p);
-  return hipGetLastError();
+  return launch_lds(heard ? benor_tally_heard_kernel : benor_tally_byz_kernel, p, grid, s);
 }
 
 }  // namespace benor

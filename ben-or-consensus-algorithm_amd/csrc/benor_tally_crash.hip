@@ -5,7 +5,7 @@
 // may crash at a step boundary (step 2(r - 1) = the R-phase of round r, step
 // 2(r - 1) + 1 = its P-phase).  At step s the senders and the receivers are the
 // alive set A_s, m_s = |A_s| >= q, the class sizes are counted over A_s, and a
-// receiver's (c0, c1) is benor_tally3.hip's draw3 with m = m_s: one count from
+// receiver's (c0, c1) is benor_tally_common.h's draw3 with m = m_s: one count from
 // row K_A of the HG(m_s, ., q) table, the smallest class walked from stream 6.
 // So the plan holds one table per reachable live count, found through a small
 // directory indexed by the number of crashes so far (CrashDir), and m_s, the
@@ -26,7 +26,7 @@
 // index), step clamped to 2^20 - 1 (no run reaches step 2 BO_MAX_K): the plan's
 // for an explicit schedule, drawn per trial by Floyd's algorithm from Philox
 // stream 7 for a random one.  No floating point runs on the device.
-#include "benor_tally_crash.h"
+#include "benor_tally_common.h"
 
 namespace benor {
 
@@ -36,22 +36,14 @@ __global__ void __launch_bounds__(256) benor_tally_crash_kernel(KParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wv = threadIdx.x >> 6;
-  const uint32_t m0 = p.m, F = p.F, W = p.W, q = p.q, ncr = p.cr_n;
-  const uint32_t WP = (W + 1u) & ~1u;
+  const uint32_t F = p.F, W = p.W, q = p.q, ncr = p.cr_n;
 
   uint32_t *lhist = reinterpret_cast<uint32_t *>(smem);
   const bool states = p.node_out != nullptr;       // a state launch: X0 and DEC planes of their own
-  const uint32_t capE = (p.tally_cap + 1u) & ~1u;
-  uint64_t *AL = reinterpret_cast<uint64_t *>(smem + p.hist_bytes + wv * p.wave_bytes);   // [W] alive
-  uint64_t *X1 = AL + WP;                                                                 // [W] x = 1
-  uint64_t *P1 = X1 + WP, *P0 = P1 + WP;                                                  // [W] proposals 1, 0
-  uint64_t *X0 = states ? P0 + WP : P0;                                                   // [W] x = 0 (round 1)
-  uint64_t *DEC = X0 + WP;                                                                // [W] decided (state launch)
-  uint64_t *row = AL + (states ? 6u : 4u) * WP;                                           // [tally_cap] thresholds
-  // [256] stream-7 words: in the row region when it is large enough (no row is staged while a schedule is drawn)
-  uint32_t *WB = reinterpret_cast<uint32_t *>(2u * capE >= kSchedWords ? row : row + capE);
-  uint32_t *SC = reinterpret_cast<uint32_t *>(row + capE) +
-                 (p.cr_random && 2u * capE < kSchedWords ? kSchedWords : 0u);             // [ncr] the schedule
+  const Planes S(smem + p.hist_bytes + wv * p.wave_bytes,
+                 crash_layout(W, p.tally_cap, ncr, p.cr_random != 0u, states, false));
+  uint64_t *const AL = S.AL, *const X1 = S.X1, *const P1 = S.P1, *const P0 = S.P0, *const X0 = S.X0, *const row = S.row;
+  uint32_t *const SC = S.SC;
 
   for (uint32_t i = threadIdx.x; i < p.hist_len; i += blockDim.x) lhist[i] = 0u;
   __syncthreads();
@@ -66,33 +58,7 @@ __global__ void __launch_bounds__(256) benor_tally_crash_kernel(KParams p) {
     const uint64_t trial = p.trial_begin + t;
     const uint32_t tlo = uni((uint32_t)trial), thi = uni((uint32_t)(trial >> 32));
     __builtin_amdgcn_wave_barrier();               // the previous trial's state reads are done
-    if (lane < W) {
-      AL[lane] = group_mask(lane, m0);
-      P1[lane] = 0ull;                             // the schedule draw's chosen set
-    }
-    if (p.init_mode == BO_INIT_RANDOM) {           // /start (node.ts:167-188): stream 1, as every batch mode
-      const uint32_t nph = (W + 1u) >> 1;
-      if (lane < nph) {
-        uint4 r;
-        if (m0 <= 32u) r = make_uint4(init_word_small(k0, k1, trial), 0u, 0u, 0u);   // shared block (m <= 32)
-        else r = philox4x32_10(k0, k1, make_uint4(tlo, thi, lane, kStreamInit << 24));
-        const uint32_t w0 = 2u * lane, w1 = w0 + 1u;
-        const uint64_t g0 = group_mask(w0, m0), a0 = ((uint64_t)r.y << 32 | r.x) & g0;
-        X1[w0] = a0, X0[w0] = g0 & ~a0;
-        if (w1 < W) {
-          const uint64_t g1 = group_mask(w1, m0), a1 = ((uint64_t)r.w << 32 | r.z) & g1;
-          X1[w1] = a1, X0[w1] = g1 & ~a1;
-        }
-      }
-    } else {
-      for (uint32_t w = lane; w < W; w += 64u) {
-        const uint4 rc = p.init_plane[w];
-        X0[w] = (uint64_t)rc.y << 32 | rc.x;
-        X1[w] = (uint64_t)rc.w << 32 | rc.z;
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (p.cr_random) draw_schedule(SC, WB, P1, p, k0, k1, tlo, thi, lane);
+    crash_trial_start(S, p, k0, k1, trial, tlo, thi, lane);
 
     // The crashes of step s, then the step's live count and its table.
     Table tb;
@@ -109,10 +75,7 @@ __global__ void __launch_bounds__(256) benor_tally_crash_kernel(KParams p) {
       uint32_t ms = 0;
       for (uint32_t j = 0; j < W; ++j) ms += (uint32_t)__builtin_popcountll(AL[j]);
       ms = uni(ms);
-      const CrashDir de = p.cr_dir[m0 - ms];       // m0 - ms <= ncr crashes so far
-      tb.m = ms;
-      tb.off = p.tally_off + uni(de.off_base);
-      tb.thr = p.tally_thr + uni64(de.thr_base);
+      tb = dir_table(p, ms);
       return ms;
     };
 
@@ -166,18 +129,10 @@ __global__ void __launch_bounds__(256) benor_tally_crash_kernel(KParams p) {
         const uint4 b = philox4x32_10(k0, k1, make_uint4(tlo, thi, c, (r - 1u) | (kStreamTally << 24)));
         uint32_t c0, c1;
         draw3(row, ph, ms, q, k0, k1, tlo, thi, c, r, 1u, (uint64_t)b.w << 32 | b.z, c0, c1);
-        const bool d0l = c0 > F, d1l = !d0l && c1 > F;
-        const uint64_t d0 = ballot(d0l) & al;
-        const uint64_t d1 = ballot(d1l) & al;
-        const uint64_t rest = al & ~(d0 | d1);
-        uint64_t x1 = d1;
-        if (rest) {
-          x1 |= ballot(c1 > c0) & rest;
-          const uint64_t tie = ballot(c1 == c0) & rest;              // an empty tally included
-          if (tie) x1 |= coin_ballot(k0, k1, tlo, thi, j, r, tie);
-        }
+        bool decided;
+        const uint64_t x1 = p_rule(c0, c1, F, al, k0, k1, tlo, thi, j, r, decided);
         const bool mine = (al >> lane) & 1ull;     // this lane's node is alive
-        if (mine && (d0l || d1l)) dec |= 1ull << j;                  // sticky
+        if (mine && decided) dec |= 1ull << j;     // sticky
         if (lane == 0) {                           // the bits of crashed nodes stay as of their crash
           X1[j] = (X1[j] & ~al) | x1;
           if (states) X0[j] = (X0[j] & ~al) | (al & ~x1);
@@ -188,50 +143,7 @@ __global__ void __launch_bounds__(256) benor_tally_crash_kernel(KParams p) {
       all_dec = !__any(undecided);                 // over the alive nodes
       if (all_dec) break;
     }
-    __builtin_amdgcn_wave_barrier();
-    uint32_t K = 0, ms = 0;                        // the nodes alive at the end, and those with x = 1
-    for (uint32_t j = 0; j < W; ++j) {
-      const uint64_t al = AL[j];
-      ms += (uint32_t)__builtin_popcountll(al);
-      K += (uint32_t)__builtin_popcountll(X1[j] & al);
-    }
-    K = uni(K), ms = uni(ms);
-    const uint32_t v = none ? 2u : ((K != 0u && K != ms) ? 2u : (K != 0u ? 1u : 0u));
-    if (none) all_dec = false;                     // nobody left: bin[2], rounds 0
-    if (lane == 0) {
-      atomicAdd(&lhist[all_dec ? (R * 3u + v) : v], 1u);
-      if (all_dec && v == 2u) atomicAdd(&lhist[p.hist_len - 1u], 1u);
-      if (p.rounds_out) *p.rounds_out = all_dec ? R : 0u;
-    }
-    if (states) {
-      for (uint32_t j = 0; j < W; ++j) {
-        const uint64_t d = ballot((dec >> j) & 1ull);
-        if (lane == 0) DEC[j] = d;
-      }
-      __builtin_amdgcn_wave_barrier();
-      for (uint32_t c = lane; c < m0; c += 64u) {
-        const uint32_t j = c >> 6;
-        if (!((AL[j] >> lane) & 1ull)) continue;
-        bo_node_state ns;
-        ns.killed = 0;
-        ns.x = (int8_t)((X1[j] >> lane) & 1ull);
-        ns.decided = (int8_t)((DEC[j] >> lane) & 1ull);
-        ns.pad = 0;
-        ns.k = (int32_t)R + 1;
-        p.node_out[p.live_ids[c]] = ns;
-      }
-      for (uint32_t i = lane; i < ncr; i += 64u) {   // crashed: x and decided as of the crash, k its round
-        const uint32_t e = SC[i], c = e & 0xFFFu, j = c >> 6, b = c & 63u;
-        if ((AL[j] >> b) & 1ull) continue;           // its step was never reached
-        bo_node_state ns;
-        ns.killed = 1;
-        ns.x = (int8_t)(((X1[j] >> b) & 1ull) ? 1 : (((X0[j] >> b) & 1ull) ? 0 : 2));
-        ns.decided = (int8_t)((DEC[j] >> b) & 1ull);
-        ns.pad = 0;
-        ns.k = (int32_t)(e >> 13) + 1;
-        p.node_out[p.live_ids[c]] = ns;
-      }
-    }
+    crash_trial_end(S, lhist, p, none, all_dec, R, dec, lane);
   }
 
   __syncthreads();
@@ -240,42 +152,17 @@ __global__ void __launch_bounds__(256) benor_tally_crash_kernel(KParams p) {
 
 }  // namespace
 
-// A batch launch's per-wave LDS: four planes, the row region, the schedule's
-// stream-7 words where the row region is too small for them, the schedule.
-uint32_t crash_wave_bytes(uint32_t W, uint32_t cap, uint32_t ncr, bool random) {
-  const uint32_t WP = (W + 1u) & ~1u, capE = (cap + 1u) & ~1u;
-  return (4u * WP + capE) * 8u + (random && 2u * capE < kSchedWords ? kSchedWords * 4u : 0u) + ((ncr + 3u) & ~3u) * 4u;
-}
-
-// ... and what a per-node-state launch adds to it: the X0 and DEC planes.
-uint32_t crash_state_bytes(uint32_t W) { return 2u * ((W + 1u) & ~1u) * 8u; }
-
 // Workgroups of the kernel that one CU holds at once (registers and LDS; 0 = unknown).
-int crash_blocks_per_cu(const KParams &p) {
-  int n = 0;
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, benor_tally_crash_kernel, 64 * kWavesPerBlock,
-                                                                    p.lds_bytes);
-  return e == hipSuccess ? n : 0;
-}
+int crash_blocks_per_cu(const KParams &p) { return blocks_per_cu(benor_tally_crash_kernel, p); }
 
 hipError_t launch_tally_crash(const KParams &plan, int grid, hipStream_t s) {
-  KParams p = plan;
-  if (p.node_out) {                                // a state launch (one trial): two more planes per wave
-    p.wave_bytes += crash_state_bytes(p.W);
-    p.lds_bytes += kWavesPerBlock * crash_state_bytes(p.W);
-  }
+  const KParams p = state_launch(plan, crash_state_bytes(plan.W));
   // (an explicit schedule whose steps all lie beyond 2 k_max leaves an empty list)
   if (!p.tally_off || !p.tally_thr || !p.cr_dir || p.W > kMaxW || p.cr_n > p.m ||
       (!p.cr_random && p.cr_n != 0u && !p.cr_list) || (p.cr_random && (p.cr_n == 0u || p.crash_window == 0u)) ||
-      plan.wave_bytes < crash_wave_bytes(p.W, p.tally_cap, p.cr_n, p.cr_random != 0u))
+      plan.wave_bytes < crash_wave_bytes(p.W, p.tally_cap, p.cr_n, p.cr_random != 0u, false))
     return hipErrorInvalidValue;
-  if (p.lds_bytes > 64u * 1024u) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&benor_tally_crash_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(benor_tally_crash_kernel, dim3(grid), dim3(64 * kWavesPerBlock), p.lds_bytes, s, p);
-  return hipGetLastError();
+  return launch_lds(benor_tally_crash_kernel, p, grid, s);
 }
 
 }  // namespace benor

@@ -14,7 +14,7 @@
 // The cuts of a step split the compact indices into at most |C_s| + 1 contiguous
 // segments inside which H_c, and so the pool size, the table and the three class
 // sizes, are the same for every receiver.  So the kernel keeps
-// benor_tally_crash.hip's wave-uniform machinery -- phase_setup, the row staged in
+// benor_tally_common.h's wave-uniform machinery -- phase_setup, the row staged in
 // LDS, draw3 -- and runs it once per segment instead of once per step: the next
 // boundary is the smallest cut above the current position (a wave reduction over
 // the step's crasher list), the groups that overlap the segment are drawn with the
@@ -31,7 +31,7 @@
 // from the frozen planes before the step overwrites anything (X1, and X0 in round
 // 1 -- later every alive x is binary -- at an R-step, P1 / P0 at a P-step).  No
 // floating point runs on the device.
-#include "benor_tally_crash.h"
+#include "benor_tally_common.h"
 
 namespace benor {
 
@@ -79,22 +79,13 @@ __global__ void __launch_bounds__(256, 5) benor_tally_partial_kernel(KParams p) 
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wv = threadIdx.x >> 6;
   const uint32_t m0 = p.m, F = p.F, W = p.W, q = p.q, ncr = p.cr_n;
-  const uint32_t WP = (W + 1u) & ~1u;
 
   uint32_t *lhist = reinterpret_cast<uint32_t *>(smem);
   const bool states = p.node_out != nullptr;       // a state launch: X0 and DEC planes of their own
-  const uint32_t capE = (p.tally_cap + 1u) & ~1u;
-  uint64_t *AL = reinterpret_cast<uint64_t *>(smem + p.hist_bytes + wv * p.wave_bytes);   // [W] alive
-  uint64_t *X1 = AL + WP;                                                                 // [W] x = 1
-  uint64_t *P1 = X1 + WP, *P0 = P1 + WP;                                                  // [W] proposals 1, 0
-  uint64_t *X0 = states ? P0 + WP : P0;                                                   // [W] x = 0 (round 1)
-  uint64_t *DEC = X0 + WP;                                                                // [W] decided (state launch)
-  uint64_t *row = AL + (states ? 6u : 4u) * WP;                                           // [tally_cap] thresholds
-  // [256] stream-7 words: in the row region when it is large enough (no row is staged while a schedule is drawn)
-  uint32_t *WB = reinterpret_cast<uint32_t *>(2u * capE >= kSchedWords ? row : row + capE);
-  uint32_t *SC = reinterpret_cast<uint32_t *>(row + capE) +
-                 (p.cr_random && 2u * capE < kSchedWords ? kSchedWords : 0u);             // [ncr] the schedule
-  uint32_t *CL = SC + ((ncr + 3u) & ~3u);                                                 // [ncr] the step's crashers
+  const Planes S(smem + p.hist_bytes + wv * p.wave_bytes,
+                 crash_layout(W, p.tally_cap, ncr, p.cr_random != 0u, states, true));
+  uint64_t *const AL = S.AL, *const X1 = S.X1, *const P1 = S.P1, *const P0 = S.P0, *const X0 = S.X0, *const row = S.row;
+  uint32_t *const SC = S.SC, *const CL = S.CL;
 
   for (uint32_t i = threadIdx.x; i < p.hist_len; i += blockDim.x) lhist[i] = 0u;
   __syncthreads();
@@ -109,33 +100,7 @@ __global__ void __launch_bounds__(256, 5) benor_tally_partial_kernel(KParams p) 
     const uint64_t trial = p.trial_begin + t;
     const uint32_t tlo = uni((uint32_t)trial), thi = uni((uint32_t)(trial >> 32));
     __builtin_amdgcn_wave_barrier();               // the previous trial's state reads are done
-    if (lane < W) {
-      AL[lane] = group_mask(lane, m0);
-      P1[lane] = 0ull;                             // the schedule draw's chosen set
-    }
-    if (p.init_mode == BO_INIT_RANDOM) {           // /start (node.ts:167-188): stream 1, as every batch mode
-      const uint32_t nph = (W + 1u) >> 1;
-      if (lane < nph) {
-        uint4 r;
-        if (m0 <= 32u) r = make_uint4(init_word_small(k0, k1, trial), 0u, 0u, 0u);   // shared block (m <= 32)
-        else r = philox4x32_10(k0, k1, make_uint4(tlo, thi, lane, kStreamInit << 24));
-        const uint32_t w0 = 2u * lane, w1 = w0 + 1u;
-        const uint64_t g0 = group_mask(w0, m0), a0 = ((uint64_t)r.y << 32 | r.x) & g0;
-        X1[w0] = a0, X0[w0] = g0 & ~a0;
-        if (w1 < W) {
-          const uint64_t g1 = group_mask(w1, m0), a1 = ((uint64_t)r.w << 32 | r.z) & g1;
-          X1[w1] = a1, X0[w1] = g1 & ~a1;
-        }
-      }
-    } else {
-      for (uint32_t w = lane; w < W; w += 64u) {
-        const uint4 rc = p.init_plane[w];
-        X0[w] = (uint64_t)rc.y << 32 | rc.x;
-        X1[w] = (uint64_t)rc.w << 32 | rc.z;
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (p.cr_random) draw_schedule(SC, WB, P1, p, k0, k1, tlo, thi, lane);
+    crash_trial_start(S, p, k0, k1, trial, tlo, thi, lane);
 
     // The crashers of step s (phase 0: an R-step of round r, 1: a P-step) go into CL
     // with their cut and the class of their last message, and leave the alive set;
@@ -180,15 +145,6 @@ __global__ void __launch_bounds__(256, 5) benor_tally_partial_kernel(KParams p) 
       for (uint32_t j = 0; j < W; ++j) ms += (uint32_t)__builtin_popcountll(AL[j]);
       return uni(ms);
     };
-    // The table of a pool of m nodes: m0 - m <= ncr crashes so far.
-    const auto table_of = [&](uint32_t m) {
-      const CrashDir de = p.cr_dir[m0 - m];
-      Table tb;
-      tb.m = m;
-      tb.off = p.tally_off + uni(de.off_base);
-      tb.thr = p.tally_thr + uni64(de.thr_base);
-      return tb;
-    };
     // The lanes of group j inside the segment [pos, end), end > 64 j, pos < 64 j + 64.
     const auto segment_mask = [](uint32_t j, uint32_t pos, uint32_t end) {
       const uint32_t lo = j * 64u;
@@ -216,7 +172,7 @@ __global__ void __launch_bounds__(256, 5) benor_tally_partial_kernel(KParams p) 
       for (uint32_t pos = 0u; pos < m0;) {
         const Segment sg = next_segment(CL, ncs, pos, m0, lane);
         const uint32_t mp = ms + sg.j;             // the segment's pool
-        const Table tb = table_of(mp);
+        const Table tb = dir_table(p, mp);
         const PhaseC ph = phase_setup(row, p, tb, K0 + sg.d0, K1 + sg.d1, mp - K0 - K1 - sg.d0 - sg.d1, lane);
         for (uint32_t j = pos >> 6; j <= (sg.end - 1u) >> 6; ++j) {
           const uint64_t al = uni64(AL[j]) & segment_mask(j, pos, sg.end);
@@ -252,7 +208,7 @@ __global__ void __launch_bounds__(256, 5) benor_tally_partial_kernel(KParams p) 
       for (uint32_t pos = 0u; pos < m0;) {
         const Segment sg = next_segment(CL, ncs, pos, m0, lane);
         const uint32_t mp = ms + sg.j;
-        const Table tb = table_of(mp);
+        const Table tb = dir_table(p, mp);
         const PhaseC ph = phase_setup(row, p, tb, K0 + sg.d0, K1 + sg.d1, mp - K0 - K1 - sg.d0 - sg.d1, lane);
         for (uint32_t j = pos >> 6; j <= (sg.end - 1u) >> 6; ++j) {
           const uint64_t al = uni64(AL[j]) & segment_mask(j, pos, sg.end);
@@ -261,18 +217,10 @@ __global__ void __launch_bounds__(256, 5) benor_tally_partial_kernel(KParams p) 
           const uint4 b = philox4x32_10(k0, k1, make_uint4(tlo, thi, c, (r - 1u) | (kStreamTally << 24)));
           uint32_t c0, c1;
           draw3(row, ph, mp, q, k0, k1, tlo, thi, c, r, 1u, (uint64_t)b.w << 32 | b.z, c0, c1);
-          const bool d0l = c0 > F, d1l = !d0l && c1 > F;
-          const uint64_t d0 = ballot(d0l) & al;
-          const uint64_t d1 = ballot(d1l) & al;
-          const uint64_t rest = al & ~(d0 | d1);
-          uint64_t x1 = d1;
-          if (rest) {
-            x1 |= ballot(c1 > c0) & rest;
-            const uint64_t tie = ballot(c1 == c0) & rest;              // an empty tally included
-            if (tie) x1 |= coin_ballot(k0, k1, tlo, thi, j, r, tie);
-          }
+          bool decided;
+          const uint64_t x1 = p_rule(c0, c1, F, al, k0, k1, tlo, thi, j, r, decided);
           const bool mine = (al >> lane) & 1ull;   // this lane's node is alive and in the segment
-          if (mine && (d0l || d1l)) dec |= 1ull << j;                  // sticky
+          if (mine && decided) dec |= 1ull << j;   // sticky
           if (lane == 0) {                         // the bits of crashed nodes stay as of their crash
             X1[j] = (X1[j] & ~al) | x1;
             if (states) X0[j] = (X0[j] & ~al) | (al & ~x1);
@@ -285,50 +233,7 @@ __global__ void __launch_bounds__(256, 5) benor_tally_partial_kernel(KParams p) 
       all_dec = !__any(undecided);                 // over the alive nodes
       if (all_dec) break;
     }
-    __builtin_amdgcn_wave_barrier();
-    uint32_t K = 0, ms = 0;                        // the nodes alive at the end, and those with x = 1
-    for (uint32_t j = 0; j < W; ++j) {
-      const uint64_t al = AL[j];
-      ms += (uint32_t)__builtin_popcountll(al);
-      K += (uint32_t)__builtin_popcountll(X1[j] & al);
-    }
-    K = uni(K), ms = uni(ms);
-    const uint32_t v = none ? 2u : ((K != 0u && K != ms) ? 2u : (K != 0u ? 1u : 0u));
-    if (none) all_dec = false;                     // nobody left: bin[2], rounds 0
-    if (lane == 0) {
-      atomicAdd(&lhist[all_dec ? (R * 3u + v) : v], 1u);
-      if (all_dec && v == 2u) atomicAdd(&lhist[p.hist_len - 1u], 1u);
-      if (p.rounds_out) *p.rounds_out = all_dec ? R : 0u;
-    }
-    if (states) {
-      for (uint32_t j = 0; j < W; ++j) {
-        const uint64_t d = ballot((dec >> j) & 1ull);
-        if (lane == 0) DEC[j] = d;
-      }
-      __builtin_amdgcn_wave_barrier();
-      for (uint32_t c = lane; c < m0; c += 64u) {
-        const uint32_t j = c >> 6;
-        if (!((AL[j] >> lane) & 1ull)) continue;
-        bo_node_state ns;
-        ns.killed = 0;
-        ns.x = (int8_t)((X1[j] >> lane) & 1ull);
-        ns.decided = (int8_t)((DEC[j] >> lane) & 1ull);
-        ns.pad = 0;
-        ns.k = (int32_t)R + 1;
-        p.node_out[p.live_ids[c]] = ns;
-      }
-      for (uint32_t i = lane; i < ncr; i += 64u) {   // crashed: x and decided as of the crash, k its round
-        const uint32_t e = SC[i], c = e & 0xFFFu, j = c >> 6, b = c & 63u;
-        if ((AL[j] >> b) & 1ull) continue;           // its step was never reached
-        bo_node_state ns;
-        ns.killed = 1;
-        ns.x = (int8_t)(((X1[j] >> b) & 1ull) ? 1 : (((X0[j] >> b) & 1ull) ? 0 : 2));
-        ns.decided = (int8_t)((DEC[j] >> b) & 1ull);
-        ns.pad = 0;
-        ns.k = (int32_t)(e >> 13) + 1;
-        p.node_out[p.live_ids[c]] = ns;
-      }
-    }
+    crash_trial_end(S, lhist, p, none, all_dec, R, dec, lane);
   }
 
   __syncthreads();
@@ -337,40 +242,18 @@ __global__ void __launch_bounds__(256, 5) benor_tally_partial_kernel(KParams p) 
 
 }  // namespace
 
-// A batch launch's per-wave LDS: benor_tally_crash.hip's (four planes, the row
-// region, the stream-7 words where the row region is too small for them, the
-// schedule) and the step's crasher list.
-uint32_t partial_wave_bytes(uint32_t W, uint32_t cap, uint32_t ncr, bool random) {
-  return crash_wave_bytes(W, cap, ncr, random) + ((ncr + 3u) & ~3u) * 4u;
-}
-
 // Workgroups of the kernel that one CU holds at once (registers and LDS; 0 = unknown).
-int partial_blocks_per_cu(const KParams &p) {
-  int n = 0;
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, benor_tally_partial_kernel, 64 * kWavesPerBlock,
-                                                                    p.lds_bytes);
-  return e == hipSuccess ? n : 0;
-}
+int partial_blocks_per_cu(const KParams &p) { return blocks_per_cu(benor_tally_partial_kernel, p); }
 
 hipError_t launch_tally_partial(const KParams &plan, int grid, hipStream_t s) {
-  KParams p = plan;
-  if (p.node_out) {                                // a state launch (one trial): two more planes per wave
-    p.wave_bytes += crash_state_bytes(p.W);
-    p.lds_bytes += kWavesPerBlock * crash_state_bytes(p.W);
-  }
+  const KParams p = state_launch(plan, crash_state_bytes(plan.W));
   // (an explicit schedule whose steps all lie beyond 2 k_max leaves an empty list)
   if (!p.tally_off || !p.tally_thr || !p.cr_dir || p.W > kMaxW || p.cr_n > p.m ||
       (!p.cr_random && p.cr_n != 0u && !p.cr_list) || (p.cr_random && (p.cr_n == 0u || p.crash_window == 0u)) ||
       (p.cr_cut != kCutRandom && p.cr_cut > p.m) ||
-      plan.wave_bytes < partial_wave_bytes(p.W, p.tally_cap, p.cr_n, p.cr_random != 0u))
+      plan.wave_bytes < crash_wave_bytes(p.W, p.tally_cap, p.cr_n, p.cr_random != 0u, true))
     return hipErrorInvalidValue;
-  if (p.lds_bytes > 64u * 1024u) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&benor_tally_partial_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(benor_tally_partial_kernel, dim3(grid), dim3(64 * kWavesPerBlock), p.lds_bytes, s, p);
-  return hipGetLastError();
+  return launch_lds(benor_tally_partial_kernel, p, grid, s);
 }
 
 }  // namespace benor

@@ -23,11 +23,11 @@
 //      list);
 //   2. the draw: the step has a base profile, the one every lane has when the
 //      reach pass is skipped and the empty one otherwise.  Its phase is set up
-//      once per step with the row staged in LDS (benor_tally_crash.hip's
+//      once per step with the row staged in LDS (benor_tally_common.h's
 //      wave-uniform phase_setup and draw3: a step without a reaching crasher is
 //      that kernel's step), and the lanes with that profile draw from it.  The
 //      other lanes, each with a pool of its own, draw in one more pass from their
-//      own rows in global memory (draw3_own: the same class choice, count and walk
+//      own rows in global memory (draw3_lane: the same class choice, count and walk
 //      with every quantity per lane).  The first form of this kernel staged a row
 //      per distinct profile of the group instead and ran draw3 once per profile;
 //      that cost 3.5-14.5 times mode 6's random cuts.
@@ -42,7 +42,7 @@
 // from the frozen planes before the step overwrites anything (X1, and X0 in round
 // 1 -- later every alive x is binary -- at an R-step, P1 / P0 at a P-step).  No
 // floating point runs on the device.
-#include "benor_tally_crash.h"
+#include "benor_tally_common.h"
 
 namespace benor {
 
@@ -50,89 +50,26 @@ namespace {
 
 constexpr uint32_t kReachAll = 0xFFFFFFFFu;        // KParams::cr_reach: every crasher reaches every receiver
 
-// draw3 for a lane whose pool is its own: phase_setup's class choice, row_count and
-// draw3's walk with every quantity per lane, the row searched where it lies in
-// global memory.  m <= m0 is the lane's pool size, (K0, K1) its class sizes; a
-// lane that is not `active` loads nothing and its result is not used.  The search
-// is row_count's for any power of two `top` above the row's width (a probe at or
-// beyond the width fails as row_count's does).
-__device__ __forceinline__ void draw3_own(const KParams &p, uint32_t m, uint32_t K0, uint32_t K1, uint32_t k0,
-                                          uint32_t k1, uint32_t tlo, uint32_t thi, uint32_t c, uint32_t r,
-                                          uint32_t phase, uint64_t u, bool active, uint32_t &c0, uint32_t &c1) {
-  const uint32_t q = p.q, Kq = m - K0 - K1;
-  uint32_t sel, KS, KA;
-  if (Kq <= K0 && Kq <= K1) sel = 0u, KS = Kq, KA = K1;
-  else if (K0 <= K1) sel = 1u, KS = K0, KA = K1;
-  else sel = 2u, KS = K1, KA = K0;
-  uint32_t cA = KA + q > m ? KA + q - m : 0u;
-  if (active && KA != 0u && KA != m && m != q) {   // else the row is a point
-    const CrashDir de = p.cr_dir[p.m - m];
-    const uint32_t *off = p.tally_off + de.off_base;
-    const uint32_t o = off[KA];
-    uint32_t n = off[KA + 1u] - o;
-    if (n > p.tally_cap) n = p.tally_cap;
-    const unsigned long long *src = p.tally_thr + de.thr_base + o;
-    uint32_t pos = 0u;
-    for (uint32_t st = 1u << (31u - (uint32_t)__builtin_clz(p.tally_cap | 1u)); st != 0u; st >>= 1) {
-      const uint32_t i = pos + st - 1u;
-      if (i < n && src[i] <= u) pos += st;
-    }
-    cA += pos;
-  }
-  if (!active) KS = 0u;
-  uint32_t cS = 0u;
-  if (m == q) {
-    cS = KS;                                       // every alive sender is in the inbox
-  } else {
-    const uint32_t slots = q - cA;                 // inbox slots left to the senders outside A
-    const uint32_t dtop = m - KA;                  // ... of which there are this many (>= slots, >= KS)
-    const uint32_t c3 = (r - 1u) | (phase << 16) | (kStreamWalk << 24);
-    uint32_t i = 0;
-    const auto word = [&](uint32_t w) {
-      if (i < KS) {
-        const uint32_t d = dtop - i;               // member i's denominator, >= 1
-        const uint64_t mm = (uint64_t)w * d;
-        const uint32_t l = (uint32_t)mm;
-        bool ok = true;
-        if (l < d) ok = l >= (0u - d) % d;
-        if (ok) {
-          if ((uint32_t)(mm >> 32) < slots - cS) ++cS;
-          ++i;
-        }
-      }
-    };
-    for (uint32_t blk = 0; __any(i < KS); ++blk) {
-      const uint4 b = philox4x32_10(k0, k1, make_uint4(tlo, thi, c | (blk << 12), c3));
-      word(b.x), word(b.y), word(b.z), word(b.w);
-    }
-  }
-  const uint32_t cT = q - cA - cS;
-  c1 = sel == 2u ? cS : cA;
-  c0 = sel == 0u ? cT : (sel == 1u ? cS : cA);
-}
-
 // (five waves per SIMD, benor_tally_crash.hip's occupancy)
 __global__ void __launch_bounds__(256, 5) benor_tally_subset_kernel(KParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wv = threadIdx.x >> 6;
   const uint32_t m0 = p.m, F = p.F, W = p.W, q = p.q, ncr = p.cr_n, reach = p.cr_reach;
-  const uint32_t WP = (W + 1u) & ~1u;
 
   uint32_t *lhist = reinterpret_cast<uint32_t *>(smem);
   const bool states = p.node_out != nullptr;       // a state launch: X0 and DEC planes of their own
-  const uint32_t capE = (p.tally_cap + 1u) & ~1u;
-  uint64_t *AL = reinterpret_cast<uint64_t *>(smem + p.hist_bytes + wv * p.wave_bytes);   // [W] alive
-  uint64_t *X1 = AL + WP;                                                                 // [W] x = 1
-  uint64_t *P1 = X1 + WP, *P0 = P1 + WP;                                                  // [W] proposals 1, 0
-  uint64_t *X0 = states ? P0 + WP : P0;                                                   // [W] x = 0 (round 1)
-  uint64_t *DEC = X0 + WP;                                                                // [W] decided (state launch)
-  uint64_t *row = AL + (states ? 6u : 4u) * WP;                                           // [tally_cap] thresholds
-  // [256] stream-7 words: in the row region when it is large enough (no row is staged while a schedule is drawn)
-  uint32_t *WB = reinterpret_cast<uint32_t *>(2u * capE >= kSchedWords ? row : row + capE);
-  uint32_t *SC = reinterpret_cast<uint32_t *>(row + capE) +
-                 (p.cr_random && 2u * capE < kSchedWords ? kSchedWords : 0u);             // [ncr] the schedule
-  uint32_t *CL = SC + ((ncr + 3u) & ~3u);                                                 // [ncr] the step's crashers
+  const Planes S(smem + p.hist_bytes + wv * p.wave_bytes,
+                 crash_layout(W, p.tally_cap, ncr, p.cr_random != 0u, states, true));
+  uint64_t *const AL = S.AL, *const X1 = S.X1, *const P1 = S.P1, *const P0 = S.P0, *const X0 = S.X0, *const row = S.row;
+  uint32_t *const SC = S.SC, *const CL = S.CL;
+  // A lane with a pool of its own searches its row where it lies in global memory, through the
+  // directory; the halving starts from the plan's cap, which bounds every row (a wave-uniform loop).
+  const uint32_t own_steps = search_steps(p.tally_cap);
+  const auto own_table = [&](uint32_t m) {
+    const CrashDir de = p.cr_dir[m0 - m];
+    return Table{m, p.tally_off + de.off_base, p.tally_thr + de.thr_base};
+  };
 
   for (uint32_t i = threadIdx.x; i < p.hist_len; i += blockDim.x) lhist[i] = 0u;
   __syncthreads();
@@ -147,33 +84,7 @@ __global__ void __launch_bounds__(256, 5) benor_tally_subset_kernel(KParams p) {
     const uint64_t trial = p.trial_begin + t;
     const uint32_t tlo = uni((uint32_t)trial), thi = uni((uint32_t)(trial >> 32));
     __builtin_amdgcn_wave_barrier();               // the previous trial's state reads are done
-    if (lane < W) {
-      AL[lane] = group_mask(lane, m0);
-      P1[lane] = 0ull;                             // the schedule draw's chosen set
-    }
-    if (p.init_mode == BO_INIT_RANDOM) {           // /start (node.ts:167-188): stream 1, as every batch mode
-      const uint32_t nph = (W + 1u) >> 1;
-      if (lane < nph) {
-        uint4 r;
-        if (m0 <= 32u) r = make_uint4(init_word_small(k0, k1, trial), 0u, 0u, 0u);   // shared block (m <= 32)
-        else r = philox4x32_10(k0, k1, make_uint4(tlo, thi, lane, kStreamInit << 24));
-        const uint32_t w0 = 2u * lane, w1 = w0 + 1u;
-        const uint64_t g0 = group_mask(w0, m0), a0 = ((uint64_t)r.y << 32 | r.x) & g0;
-        X1[w0] = a0, X0[w0] = g0 & ~a0;
-        if (w1 < W) {
-          const uint64_t g1 = group_mask(w1, m0), a1 = ((uint64_t)r.w << 32 | r.z) & g1;
-          X1[w1] = a1, X0[w1] = g1 & ~a1;
-        }
-      }
-    } else {
-      for (uint32_t w = lane; w < W; w += 64u) {
-        const uint4 rc = p.init_plane[w];
-        X0[w] = (uint64_t)rc.y << 32 | rc.x;
-        X1[w] = (uint64_t)rc.w << 32 | rc.z;
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (p.cr_random) draw_schedule(SC, WB, P1, p, k0, k1, tlo, thi, lane);
+    crash_trial_start(S, p, k0, k1, trial, tlo, thi, lane);
 
     // The crashers of step s (phase 0: an R-step of round r, 1: a P-step) go into CL
     // with the class of their last message, and leave the alive set; then the step's
@@ -205,15 +116,6 @@ __global__ void __launch_bounds__(256, 5) benor_tally_subset_kernel(KParams p) {
       uint32_t ms = 0;
       for (uint32_t j = 0; j < W; ++j) ms += (uint32_t)__builtin_popcountll(AL[j]);
       return uni(ms);
-    };
-    // The table of a pool of m nodes: m0 - m <= ncr crashes so far.
-    const auto table_of = [&](uint32_t m) {
-      const CrashDir de = p.cr_dir[m0 - m];
-      Table tb;
-      tb.m = m;
-      tb.off = p.tally_off + uni(de.off_base);
-      tb.thr = p.tally_thr + uni64(de.thr_base);
-      return tb;
     };
     // The profile of receiver 64 j + lane at this step: pf = |H_c| | (members of H_c that vote 0) << 16,
     // pd1 = members that vote 1.
@@ -249,8 +151,7 @@ __global__ void __launch_bounds__(256, 5) benor_tally_subset_kernel(KParams p) {
     // per step, by the first group with a lane that has it.
     bool varied = false, staged = false;
     uint32_t bf = 0u, bd1 = 0u, mp = 0u;
-    PhaseC ph;
-    ph.sel = 0u, ph.KA = 0u, ph.KS = 0u, ph.lo = 0u, ph.n = 0u, ph.steps = 0u;
+    PhaseC ph = phase_none();
     const auto base_profile = [&]() {
       const bool all = ncs != 0u && reach == kReachAll;
       varied = ncs != 0u && reach != 0u && reach != kReachAll;
@@ -261,7 +162,7 @@ __global__ void __launch_bounds__(256, 5) benor_tally_subset_kernel(KParams p) {
       if (staged) return;
       const uint32_t hj = bf & 0xFFFFu, d0 = bf >> 16;
       mp = ms + hj;                                // the base profile's pool
-      const Table tb = table_of(mp);
+      const Table tb = dir_table(p, mp);
       ph = phase_setup(row, p, tb, K0 + d0, K1 + bd1, mp - K0 - K1 - d0 - bd1, lane);
       staged = true;
     };
@@ -304,7 +205,8 @@ __global__ void __launch_bounds__(256, 5) benor_tally_subset_kernel(KParams p) {
           if (own) {
             const bool mine = (own >> lane) & 1ull;
             uint32_t o0, o1;
-            draw3_own(p, ms + (pf & 0xFFFFu), K0 + (pf >> 16), K1 + pd1, k0, k1, tlo, thi, c, r, 0u, u, mine, o0, o1);
+            draw3_lane(own_table, p.tally_cap, own_steps, ms + (pf & 0xFFFFu), q, K0 + (pf >> 16), K1 + pd1, k0, k1, tlo, thi, c, r,
+                       0u, u, mine, o0, o1);
             if (mine) c0 = o0, c1 = o1;
           }
           p0 = ballot(c0 > c1) & al;
@@ -345,21 +247,14 @@ __global__ void __launch_bounds__(256, 5) benor_tally_subset_kernel(KParams p) {
         if (own) {
           const bool mo = (own >> lane) & 1ull;
           uint32_t o0, o1;
-          draw3_own(p, ms + (pf & 0xFFFFu), K0 + (pf >> 16), K1 + pd1, k0, k1, tlo, thi, c, r, 1u, u, mo, o0, o1);
+          draw3_lane(own_table, p.tally_cap, own_steps, ms + (pf & 0xFFFFu), q, K0 + (pf >> 16), K1 + pd1, k0, k1, tlo, thi, c, r,
+                     1u, u, mo, o0, o1);
           if (mo) c0 = o0, c1 = o1;
         }
-        const bool d0l = c0 > F, d1l = !d0l && c1 > F;
-        const uint64_t d0 = ballot(d0l) & al;
-        const uint64_t d1 = ballot(d1l) & al;
-        const uint64_t rest = al & ~(d0 | d1);
-        uint64_t x1 = d1;
-        if (rest) {
-          x1 |= ballot(c1 > c0) & rest;
-          const uint64_t tie = ballot(c1 == c0) & rest;                  // an empty tally included
-          if (tie) x1 |= coin_ballot(k0, k1, tlo, thi, j, r, tie);
-        }
+        bool decided;
+        const uint64_t x1 = p_rule(c0, c1, F, al, k0, k1, tlo, thi, j, r, decided);
         const bool mine = (al >> lane) & 1ull;     // this lane's node is alive
-        if (mine && (d0l || d1l)) dec |= 1ull << j;                      // sticky
+        if (mine && decided) dec |= 1ull << j;     // sticky
         undecided = undecided || (mine && !((dec >> j) & 1ull));
         if (lane == 0) {                           // the bits of crashed nodes stay as of their crash
           X1[j] = (X1[j] & ~al) | x1;
@@ -370,50 +265,7 @@ __global__ void __launch_bounds__(256, 5) benor_tally_subset_kernel(KParams p) {
       all_dec = !__any(undecided);                 // over the alive nodes
       if (all_dec) break;
     }
-    __builtin_amdgcn_wave_barrier();
-    uint32_t K = 0, ms = 0;                        // the nodes alive at the end, and those with x = 1
-    for (uint32_t j = 0; j < W; ++j) {
-      const uint64_t al = AL[j];
-      ms += (uint32_t)__builtin_popcountll(al);
-      K += (uint32_t)__builtin_popcountll(X1[j] & al);
-    }
-    K = uni(K), ms = uni(ms);
-    const uint32_t v = none ? 2u : ((K != 0u && K != ms) ? 2u : (K != 0u ? 1u : 0u));
-    if (none) all_dec = false;                     // nobody left: bin[2], rounds 0
-    if (lane == 0) {
-      atomicAdd(&lhist[all_dec ? (R * 3u + v) : v], 1u);
-      if (all_dec && v == 2u) atomicAdd(&lhist[p.hist_len - 1u], 1u);
-      if (p.rounds_out) *p.rounds_out = all_dec ? R : 0u;
-    }
-    if (states) {
-      for (uint32_t j = 0; j < W; ++j) {
-        const uint64_t d = ballot((dec >> j) & 1ull);
-        if (lane == 0) DEC[j] = d;
-      }
-      __builtin_amdgcn_wave_barrier();
-      for (uint32_t c = lane; c < m0; c += 64u) {
-        const uint32_t j = c >> 6;
-        if (!((AL[j] >> lane) & 1ull)) continue;
-        bo_node_state ns;
-        ns.killed = 0;
-        ns.x = (int8_t)((X1[j] >> lane) & 1ull);
-        ns.decided = (int8_t)((DEC[j] >> lane) & 1ull);
-        ns.pad = 0;
-        ns.k = (int32_t)R + 1;
-        p.node_out[p.live_ids[c]] = ns;
-      }
-      for (uint32_t i = lane; i < ncr; i += 64u) {   // crashed: x and decided as of the crash, k its round
-        const uint32_t e = SC[i], c = e & 0xFFFu, j = c >> 6, b = c & 63u;
-        if ((AL[j] >> b) & 1ull) continue;           // its step was never reached
-        bo_node_state ns;
-        ns.killed = 1;
-        ns.x = (int8_t)(((X1[j] >> b) & 1ull) ? 1 : (((X0[j] >> b) & 1ull) ? 0 : 2));
-        ns.decided = (int8_t)((DEC[j] >> b) & 1ull);
-        ns.pad = 0;
-        ns.k = (int32_t)(e >> 13) + 1;
-        p.node_out[p.live_ids[c]] = ns;
-      }
-    }
+    crash_trial_end(S, lhist, p, none, all_dec, R, dec, lane);
   }
 
   __syncthreads();
@@ -422,39 +274,17 @@ __global__ void __launch_bounds__(256, 5) benor_tally_subset_kernel(KParams p) {
 
 }  // namespace
 
-// A batch launch's per-wave LDS: benor_tally_crash.hip's (four planes, the row
-// region, the stream-7 words where the row region is too small for them, the
-// schedule) and the step's crasher list.
-uint32_t subset_wave_bytes(uint32_t W, uint32_t cap, uint32_t ncr, bool random) {
-  return crash_wave_bytes(W, cap, ncr, random) + ((ncr + 3u) & ~3u) * 4u;
-}
-
 // Workgroups of the kernel that one CU holds at once (registers and LDS; 0 = unknown).
-int subset_blocks_per_cu(const KParams &p) {
-  int n = 0;
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, benor_tally_subset_kernel, 64 * kWavesPerBlock,
-                                                                    p.lds_bytes);
-  return e == hipSuccess ? n : 0;
-}
+int subset_blocks_per_cu(const KParams &p) { return blocks_per_cu(benor_tally_subset_kernel, p); }
 
 hipError_t launch_tally_subset(const KParams &plan, int grid, hipStream_t s) {
-  KParams p = plan;
-  if (p.node_out) {                                // a state launch (one trial): two more planes per wave
-    p.wave_bytes += crash_state_bytes(p.W);
-    p.lds_bytes += kWavesPerBlock * crash_state_bytes(p.W);
-  }
+  const KParams p = state_launch(plan, crash_state_bytes(plan.W));
   // (an explicit schedule whose steps all lie beyond 2 k_max leaves an empty list)
   if (!p.tally_off || !p.tally_thr || !p.cr_dir || p.W > kMaxW || p.cr_n > p.m ||
       (!p.cr_random && p.cr_n != 0u && !p.cr_list) || (p.cr_random && (p.cr_n == 0u || p.crash_window == 0u)) ||
-      plan.wave_bytes < subset_wave_bytes(p.W, p.tally_cap, p.cr_n, p.cr_random != 0u))
+      plan.wave_bytes < crash_wave_bytes(p.W, p.tally_cap, p.cr_n, p.cr_random != 0u, true))
     return hipErrorInvalidValue;
-  if (p.lds_bytes > 64u * 1024u) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&benor_tally_subset_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(benor_tally_subset_kernel, dim3(grid), dim3(64 * kWavesPerBlock), p.lds_bytes, s, p);
-  return hipGetLastError();
+  return launch_lds(benor_tally_subset_kernel, p, grid, s);
 }
 
 }  // namespace benor

@@ -78,6 +78,13 @@ def test_bit_exact_random_schedule_two_groups():
     check_exact(130, 46, first(1, 130), 100, crash_count=10, crash_window=8)
 
 
+def test_bit_exact_random_schedule_words_in_the_row_region():
+    """(400, 133): W = 7 and a row cap of 133, so a pass of stream-7 words fits the row region and
+    the schedule is drawn there, in the batch launch and in the state launches (at N = 10 and 130
+    above the words have a region of their own)."""
+    check_exact(400, 133, first(0, 400), 300, crash_count=8, crash_window=4)
+
+
 def test_fixed_init_with_question_marks():
     init = [Q, 1, 0, 1, Q, 0, 1, 0, 1, 0, 1, 0]
     check_exact(12, 4, first(0, 12), 1000, init=init, crash_at=at(12, {0: 0, 6: 1}))   # a "?" holder goes at step 0
