@@ -49,6 +49,10 @@ BO_MODE_BYZ_TALLY = 8          # mode 4 with Byzantine senders: byzantine[i] mar
                                # lies, it never receives); byz_one / 2^32 is the probability that a Byzantine message
                                # carries 1, byz_strategy BYZ_RANDOM (independently per receiver), BYZ_OPPOSE, or one of
                                # the two that read the receiver's inbox and ignore byz_one, BYZ_BALANCE and BYZ_SPLIT
+BO_MODE_BYZ_RULE_B = 9         # mode 8 under Ben-Or's Byzantine-tolerant rule (Protocol B, F as its t): propose v iff
+                               # 2 c_v > N + F; adopt the strict majority v iff c_v > F and decide iff 2 c_v > N + F,
+                               # else the coin.  Everything else, byzantine / byz_one / byz_strategy included, is mode
+                               # 8's; b = 0 runs this mode's kernel (it is not mode 4's plan)
 BYZ_RANDOM = 0                 # byz_strategy: each Byzantine message is 1 with probability byz_one / 2^32 (equivocation)
 BYZ_OPPOSE = 1                 # ... every one carries the value fewer honest senders hold (byz_one's step on a tie)
 BYZ_BALANCE = 3                # ... the Byzantine messages a receiver drew make its two tallies as equal as they can
@@ -74,6 +78,7 @@ BO_KERNEL_TALLY_CRASH = 11
 BO_KERNEL_TALLY_PARTIAL = 12
 BO_KERNEL_TALLY_SUBSET = 13
 BO_KERNEL_TALLY_BYZ = 14
+BO_KERNEL_TALLY_BYZ_B = 15
 KERNEL_NAMES = {BO_KERNEL_NONE: "none", BO_KERNEL_BLOCKED: "blocked popcount", BO_KERNEL_W: "W popcount",
                 BO_KERNEL_RANDOM: "random delivery", BO_KERNEL_EVENT: "event level", BO_KERNEL_LANE: "lane",
                 BO_KERNEL_MFMA: "matrix core (e2m1 MFMA)", BO_KERNEL_MFMA_SMALL: "packed matrix core (e2m1 MFMA, m <= 32)",
@@ -85,7 +90,9 @@ KERNEL_NAMES = {BO_KERNEL_NONE: "none", BO_KERNEL_BLOCKED: "blocked popcount", B
                 BO_KERNEL_TALLY_SUBSET: "count-level random delivery with crashes whose last broadcast reaches a random "
                                         "subset (a reach pass per group, per-lane draws for the receivers it reaches)",
                 BO_KERNEL_TALLY_BYZ: "count-level random delivery with Byzantine senders (an honest plane, wave-uniform "
-                                     "steps from a staged row, per-lane Binomial lies and draws otherwise)"}
+                                     "steps from a staged row, per-lane Binomial lies and draws otherwise)",
+                BO_KERNEL_TALLY_BYZ_B: "count-level random delivery with Byzantine senders under Ben-Or's Byzantine-"
+                                       "tolerant rule (the same two trial loops with thresholds at (N + F) / 2 and F + 1)"}
 BO_MAX_N = 4096
 BO_MAX_K = 1024
 
@@ -485,11 +492,11 @@ def reach_word(p: float) -> int:
 
 
 def _byz_words(mode, crash_cut, crash_count, byzantine, byz_one, byz_strategy):
-    """Mode 8 reads the crash_cut word as byz_one and the crash_count word as byz_strategy."""
+    """Modes 8 and 9 read the crash_cut word as byz_one and the crash_count word as byz_strategy."""
     if byzantine is None and byz_one is None and byz_strategy is None:
         return crash_cut, crash_count
-    if mode != BO_MODE_BYZ_TALLY:
-        raise ValueError("byzantine, byz_one and byz_strategy need mode=BO_MODE_BYZ_TALLY")
+    if mode not in (BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B):
+        raise ValueError("byzantine, byz_one and byz_strategy need mode=BO_MODE_BYZ_TALLY or BO_MODE_BYZ_RULE_B")
     if crash_cut or crash_count:
         raise ValueError("byz_one / byz_strategy name the configuration words of crash_cut / crash_count: give one")
     byz_one = 0 if byz_one is None else byz_one
@@ -499,9 +506,9 @@ def _byz_words(mode, crash_cut, crash_count, byzantine, byz_one, byz_strategy):
 
 
 def _faulty_array(N, faulty, byzantine, mode):
-    """The faulty bytes: 1 for a faulty node, and in mode 8 2 for a Byzantine one (an int entry of
+    """The faulty bytes: 1 for a faulty node, and in modes 8 and 9 2 for a Byzantine one (an int entry of
     `faulty` goes through as it is there, so that the library's validation can be reached)."""
-    raw = mode == BO_MODE_BYZ_TALLY
+    raw = mode in (BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B)
     fl = [v if raw and type(v) is int else (1 if v else 0) for v in faulty]
     if byzantine is not None:
         if len(byzantine) != len(fl):

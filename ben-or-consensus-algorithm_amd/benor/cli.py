@@ -13,6 +13,8 @@
                                                                           # ... or reaching each receiver with probability 1/2
     python -m benor.cli trials --N 1024 --F 340 --mode byz --crashed 0 --byzantine 100 --byz-one 0.5 --byz-strategy random
                                                                           # 100 Byzantine senders, a fair coin per receiver and step
+    python -m benor.cli trials --N 1024 --F 204 --mode byzb --crashed 0 --byzantine 16 --byz-strategy split
+                                                                          # ... under Ben-Or's Byzantine-tolerant rule (N > 5F)
     python -m benor.cli sweep --N 64,128,...,4096 --steps 32 --trials 2**30 --out sweep.csv
                                                                           # C5 phase diagram
     python -m benor.cli sweep --cells 4096:0,4096:1984 --per-cell 4793490  # two cells of it
@@ -92,7 +94,8 @@ def cmd_trials(a) -> int:
     mode = {"lockstep": benor.BO_MODE_LOCKSTEP, "random": benor.BO_MODE_RANDOM_DELIVERY,
             "tally": benor.BO_MODE_RANDOM_TALLY, "tally3": benor.BO_MODE_RANDOM_TALLY3,
             "crash": benor.BO_MODE_CRASH_TALLY, "partial": benor.BO_MODE_CRASH_PARTIAL,
-            "subset": benor.BO_MODE_CRASH_SUBSET, "byz": benor.BO_MODE_BYZ_TALLY}[a.mode]
+            "subset": benor.BO_MODE_CRASH_SUBSET, "byz": benor.BO_MODE_BYZ_TALLY,
+            "byzb": benor.BO_MODE_BYZ_RULE_B}[a.mode]
     crashed = a.F if a.crashed is None else a.crashed            # the first f nodes (start.ts:7-18 placement)
     sched = {}
     if a.mode in ("crash", "partial", "subset"):                  # crashes during the run, in steps
@@ -122,7 +125,7 @@ def cmd_trials(a) -> int:
         sched["crash_reach"] = benor.reach_word(a.crash_reach)
     elif a.crash_reach is not None:
         raise SystemExit("--crash-reach needs --mode subset")
-    if a.mode == "byz":                                           # Byzantine senders
+    if a.mode in ("byz", "byzb"):                                 # Byzantine senders (byzb: §4.3.9)
         if not 0.0 <= a.byz_one <= 1.0:
             raise SystemExit("--byz-one is a probability in [0, 1]")
         if not 0 <= a.byzantine <= a.N - crashed:
@@ -132,7 +135,7 @@ def cmd_trials(a) -> int:
                  "byz_strategy": {"random": benor.BYZ_RANDOM, "oppose": benor.BYZ_OPPOSE, "balance": benor.BYZ_BALANCE,
                                   "split": benor.BYZ_SPLIT}[a.byz_strategy]}
     elif a.byzantine:
-        raise SystemExit("--byzantine needs --mode byz")
+        raise SystemExit("--byzantine needs --mode byz or --mode byzb")
     plan = benor.TrialsPlan(a.N, a.F, [i < crashed for i in range(a.N)], seed=a.seed, k_max=a.k_max, mode=mode,
                             **sched)
     t0 = time.perf_counter()
@@ -148,7 +151,7 @@ def cmd_trials(a) -> int:
         row.update(crash_cut=a.crash_cut)
     if a.mode == "subset":
         row.update(crash_reach=a.crash_reach, crash_reach_word=sched["crash_reach"])
-    if a.mode == "byz":
+    if a.mode in ("byz", "byzb"):
         row.update(byzantine=a.byzantine, byz_one=a.byz_one, byz_one_word=sched["byz_one"], byz_strategy=a.byz_strategy,
                    kernel=benor.KERNEL_NAMES[plan.kernel])
     row["seconds"] = dt
@@ -286,13 +289,13 @@ def main(argv=None) -> int:
     t.add_argument("--begin", type=int, default=0)
     t.add_argument("--seed", type=int, default=0x243F6A8885A308D3)
     t.add_argument("--k-max", type=int, default=16)
-    t.add_argument("--mode", choices=["lockstep", "random", "tally", "tally3", "crash", "partial", "subset", "byz"],
+    t.add_argument("--mode", choices=["lockstep", "random", "tally", "tally3", "crash", "partial", "subset", "byz", "byzb"],
                    default="lockstep",
                    help="delivery model: lockstep, random (mask-level), tally (count-level random delivery: odd "
                         "quorum, no '?'), tally3 (count-level, any quorum), crash (tally3 with crashes during the run), "
                         "partial (crash with the crasher's last broadcast reaching a prefix of the receivers) or "
                         "subset (... reaching each receiver independently with probability --crash-reach); byz (tally3 "
-                        "with --byzantine senders that lie)")
+                        "with --byzantine senders that lie); byzb (byz under Ben-Or's Byzantine-tolerant rule, F as its t)")
     t.add_argument("--crashed", type=int, default=None,
                    help="crash the first f nodes (default F; random, tally, tally3 and crash take f <= F)")
     t.add_argument("--crash-count", type=int, default=0,

@@ -71,6 +71,7 @@ struct KParams {
                             // 12: ... whose last broadcast reaches a prefix of the receivers (benor_tally_partial.hip),
                             // 13: ... or a random subset of them, receiver by receiver (benor_tally_subset.hip),
                             // 14: three-valued count-level random delivery with Byzantine senders (benor_tally_byz.hip)
+                            // 15: ... under Ben-Or's Byzantine-tolerant rule (the same file's loops, Protocol B's rule)
   uint32_t base_variant;    // variant 7: the popcount kernel (1 W, 0 blocked) that serves the state
   uint32_t base_G;          //   launches and the deferred trials, and its G
   uint32_t mode;            // BO_MODE_LOCKSTEP / BO_MODE_RANDOM_DELIVERY / BO_MODE_EVENT / BO_MODE_RANDOM_TALLY /
@@ -78,7 +79,7 @@ struct KParams {
                             // mode 3's scope holds BO_MODE_RANDOM_TALLY here: it is that mode's plan; a
                             // BO_MODE_CRASH_TALLY, BO_MODE_CRASH_PARTIAL or BO_MODE_CRASH_SUBSET plan with an empty
                             // schedule is BO_MODE_RANDOM_TALLY3's, and so is a BO_MODE_BYZ_TALLY plan without a
-                            // Byzantine node)
+                            // Byzantine node; a BO_MODE_BYZ_RULE_B plan keeps its mode at b = 0)
   uint32_t q;               // quorum N - F (messages each receiver tallies per phase)
   uint32_t k_max;
   uint32_t init_mode;       // BO_INIT_RANDOM / BO_INIT_FIXED
@@ -178,12 +179,13 @@ struct KParams {
     uint32_t cr_cut;
     uint32_t cr_reach;
   };
-  // count-level random delivery with Byzantine senders (variant 14): m counts the live nodes, honest
+  // count-level random delivery with Byzantine senders (variants 14 and 15): m counts the live nodes, honest
   // and Byzantine; byz_plane[W] holds the honest nodes' bits (the receivers), byz_n = b > 0 is the
   // number of Byzantine senders, byz_thr[b] the thresholds of Binomial(b, byz_one / 2^32)
   // (bo_byz_cdf; device), searched in LDS (byz_lds, a copy per workgroup behind the waves' regions)
   // or where they lie in global memory.  tally_off / tally_thr hold the one table of (m, q).
-  // BO_BYZ_BALANCE and BO_BYZ_SPLIT read no thresholds: byz_thr is unused and byz_lds is 0
+  // BO_BYZ_BALANCE and BO_BYZ_SPLIT read no thresholds: byz_thr is unused and byz_lds is 0; so it is
+  // in a variant-15 plan with byz_n = 0 (byz_thr NULL), which variant 14 does not have
   const unsigned long long *byz_plane;
   const unsigned long long *byz_thr;
   uint32_t byz_n, byz_strategy, byz_one, byz_lds;
@@ -245,7 +247,7 @@ hipError_t launch_tally_subset(const KParams &p, int grid_blocks, hipStream_t st
 // benor_tally_byz.hip: with Byzantine senders; whether the workgroup keeps the b Binomial thresholds
 // in LDS behind the waves' regions (byz_thr_in_lds: when that costs no resident workgroup)
 bool byz_thr_in_lds(uint32_t lds_bytes, uint32_t b);
-bool byz_heard(const KParams &p);                 // BO_BYZ_BALANCE, BO_BYZ_SPLIT: the kernel without thresholds
+bool byz_heard(const KParams &p);                 // BO_BYZ_BALANCE, BO_BYZ_SPLIT with byz_n > 0: the kernel without thresholds
 int byz_blocks_per_cu(const KParams &p);
 hipError_t launch_tally_byz(const KParams &p, int grid_blocks, hipStream_t stream);
 

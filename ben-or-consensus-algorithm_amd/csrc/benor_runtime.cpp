@@ -568,9 +568,11 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   if (cfg->k_max < 1 || cfg->k_max > BO_MAX_K) return fail(BO_ERR_INVALID_ARGUMENT, "k_max must be in [1, 1024]");
   if (cfg->mode != BO_MODE_LOCKSTEP && cfg->mode != BO_MODE_RANDOM_DELIVERY && cfg->mode != BO_MODE_EVENT &&
       cfg->mode != BO_MODE_RANDOM_TALLY && cfg->mode != BO_MODE_RANDOM_TALLY3 && cfg->mode != BO_MODE_CRASH_TALLY &&
-      cfg->mode != BO_MODE_CRASH_PARTIAL && cfg->mode != BO_MODE_CRASH_SUBSET && cfg->mode != BO_MODE_BYZ_TALLY)
+      cfg->mode != BO_MODE_CRASH_PARTIAL && cfg->mode != BO_MODE_CRASH_SUBSET && cfg->mode != BO_MODE_BYZ_TALLY &&
+      cfg->mode != BO_MODE_BYZ_RULE_B)
     return fail(BO_ERR_UNSUPPORTED, "unknown delivery mode");
-  const bool byz_mode = cfg->mode == BO_MODE_BYZ_TALLY;
+  const bool rule_b = cfg->mode == BO_MODE_BYZ_RULE_B;   // BO_MODE_BYZ_TALLY's configuration and validation, another rule
+  const bool byz_mode = cfg->mode == BO_MODE_BYZ_TALLY || rule_b;
   const bool crash_mode = cfg->mode == BO_MODE_CRASH_TALLY || cfg->mode == BO_MODE_CRASH_PARTIAL ||
                           cfg->mode == BO_MODE_CRASH_SUBSET;
   const bool random_mode = cfg->mode == BO_MODE_RANDOM_DELIVERY || cfg->mode == BO_MODE_RANDOM_TALLY ||
@@ -579,12 +581,13 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
     return fail(BO_ERR_INVALID_ARGUMENT, "unknown init_mode");
   if (!cfg->faulty) return fail(BO_ERR_INVALID_ARGUMENT, "faulty is NULL");
   if (cfg->init_mode == BO_INIT_FIXED && !cfg->init) return fail(BO_ERR_INVALID_ARGUMENT, "init is NULL");
-  // BO_MODE_BYZ_TALLY alone reads the value of a faulty entry: 1 crashed from the start, 2
-  // Byzantine (live: it sends); every other mode reads non-zero as faulty.
+  // BO_MODE_BYZ_TALLY and BO_MODE_BYZ_RULE_B alone read the value of a faulty entry: 1 crashed from
+  // the start, 2 Byzantine (live: it sends); every other mode reads non-zero as faulty.
   if (byz_mode) {
     for (uint32_t i = 0; i < cfg->N; ++i)
       if (cfg->faulty[i] > 2u)
-        return fail(BO_ERR_INVALID_ARGUMENT, "BO_MODE_BYZ_TALLY: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)");
+        return fail(BO_ERR_INVALID_ARGUMENT, rule_b ? "BO_MODE_BYZ_RULE_B: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)"
+                                                    : "BO_MODE_BYZ_TALLY: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)");
     if (cfg->byz_strategy != BO_BYZ_RANDOM && cfg->byz_strategy != BO_BYZ_OPPOSE && cfg->byz_strategy != BO_BYZ_BALANCE &&
         cfg->byz_strategy != BO_BYZ_SPLIT)
       return fail(BO_ERR_INVALID_ARGUMENT,
@@ -603,7 +606,8 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   if (random_mode && f > cfg->F)
     return fail(BO_ERR_FAULTY_COUNT, "random delivery needs at most F crash-faulty nodes");
   if (f + nbyz > cfg->F)
-    return fail(BO_ERR_FAULTY_COUNT, "BO_MODE_BYZ_TALLY needs at most F nodes crashed or Byzantine");
+    return fail(BO_ERR_FAULTY_COUNT, rule_b ? "BO_MODE_BYZ_RULE_B needs at most F nodes crashed or Byzantine"
+                                            : "BO_MODE_BYZ_TALLY needs at most F nodes crashed or Byzantine");
   live.clear();
   for (uint32_t i = 0; i < cfg->N; ++i)
     if (!crashed(i)) live.push_back(i);
@@ -640,7 +644,7 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   kp.seed = cfg->seed;
   kp.mode = cfg->mode;
   kp.q = cfg->N - cfg->F;
-  kp.crash_count = byz_mode ? 0u : cfg->crash_count;   // (BO_MODE_BYZ_TALLY reads the word as byz_strategy)
+  kp.crash_count = byz_mode ? 0u : cfg->crash_count;   // (BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B: the word is byz_strategy)
   kp.crash_window = cfg->crash_window;
   if (cfg->mode == BO_MODE_EVENT && !cfg->crash_at && cfg->crash_count > 0 && cfg->crash_window > 0)
     kp.ev_rstops = std::min<uint32_t>(cfg->crash_count, m);   // per-trial random /stop schedule
@@ -677,9 +681,10 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   // (its kernel, its results bit for bit); outside, benor_tally3.hip.
   // A BO_MODE_CRASH_TALLY plan with an empty schedule is the three-valued mode's plan.
   if (crash_mode && n_crash == 0) kp.mode = BO_MODE_RANDOM_TALLY3;
-  // ... and so is a BO_MODE_BYZ_TALLY plan without a Byzantine node, at every byz_one and strategy.
-  if (byz_mode && nbyz == 0) kp.mode = BO_MODE_RANDOM_TALLY3;
-  if (kp.mode == BO_MODE_BYZ_TALLY) {
+  // ... and so is a BO_MODE_BYZ_TALLY plan without a Byzantine node, at every byz_one and strategy
+  // (BO_MODE_BYZ_RULE_B keeps its plan: the rule differs).
+  if (cfg->mode == BO_MODE_BYZ_TALLY && nbyz == 0) kp.mode = BO_MODE_RANDOM_TALLY3;
+  if (kp.mode == BO_MODE_BYZ_TALLY || kp.mode == BO_MODE_BYZ_RULE_B) {
     kp.byz_n = nbyz;
     kp.byz_strategy = cfg->byz_strategy;
     kp.byz_one = cfg->byz_one;
@@ -860,8 +865,8 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
       kp.init_x = pl->d_init_x;
       kp.crash_at = pl->d_crash;
       kp.scratch = pl->d_scratch;
-    } else if (kp.variant == 9 || kp.variant == 10 || kp.variant == 14) {
-      // BO_MODE_RANDOM_TALLY, BO_MODE_RANDOM_TALLY3, BO_MODE_BYZ_TALLY:
+    } else if (kp.variant == 9 || kp.variant == 10 || kp.variant == 14 || kp.variant == 15) {
+      // BO_MODE_RANDOM_TALLY, BO_MODE_RANDOM_TALLY3, BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B:
       // the whole table HG(m, K, q), K = 0..m: at most ~3.7 * 10^6 thresholds (30 MB) at m = 4096
       std::vector<uint32_t> off(m + 2u, 0u);
       std::vector<uint64_t> thr;
@@ -874,10 +879,11 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
       const size_t off_bytes = (sizeof(uint32_t) * off.size() + 7u) & ~size_t(7);
       const size_t thr_bytes = sizeof(uint64_t) * std::max<size_t>(thr.size(), 1u);
       // ... and, with Byzantine senders, the Binomial thresholds and the honest plane behind it
+      const bool byz = kp.variant == 14 || kp.variant == 15;
       std::vector<uint64_t> lie;
-      if (kp.variant == 14 && !benor::byz_heard(kp)) byz_row(kp.byz_n, kp.byz_one, lie);   // (BALANCE, SPLIT: no thresholds)
+      if (byz && !benor::byz_heard(kp)) byz_row(kp.byz_n, kp.byz_one, lie);   // (BALANCE, SPLIT, b = 0: no thresholds)
       const size_t lie_bytes = sizeof(uint64_t) * lie.size();
-      const size_t plane_bytes = kp.variant == 14 ? sizeof(uint64_t) * crash.honest.size() : 0u;
+      const size_t plane_bytes = byz ? sizeof(uint64_t) * crash.honest.size() : 0u;
       e = hipMalloc(&pl->d_tally, off_bytes + thr_bytes + lie_bytes + plane_bytes);
       if (e == hipSuccess) e = hipMemcpy(pl->d_tally, off.data(), sizeof(uint32_t) * off.size(), hipMemcpyHostToDevice);
       if (e == hipSuccess && !thr.empty())
@@ -890,8 +896,8 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
       if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "tally table upload"); }
       kp.tally_off = reinterpret_cast<const uint32_t *>(pl->d_tally);
       kp.tally_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + off_bytes);
-      if (kp.variant == 14) {
-        kp.byz_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + off_bytes + thr_bytes);
+      if (byz) {
+        if (lie_bytes) kp.byz_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + off_bytes + thr_bytes);
         kp.byz_plane = reinterpret_cast<const unsigned long long *>(pl->d_tally + off_bytes + thr_bytes + lie_bytes);
       }
     } else if (kp.variant == 11 || kp.variant == 12 || kp.variant == 13) {
@@ -978,7 +984,7 @@ uint64_t bo_plan_popc_words_per_node_round(const bo_plan *pl) {
   if (pl->kp.mode != BO_MODE_RANDOM_DELIVERY && pl->kp.mode != BO_MODE_RANDOM_TALLY &&
       pl->kp.mode != BO_MODE_RANDOM_TALLY3 && pl->kp.mode != BO_MODE_CRASH_TALLY &&
       pl->kp.mode != BO_MODE_CRASH_PARTIAL && pl->kp.mode != BO_MODE_CRASH_SUBSET &&
-      pl->kp.mode != BO_MODE_BYZ_TALLY)
+      pl->kp.mode != BO_MODE_BYZ_TALLY && pl->kp.mode != BO_MODE_BYZ_RULE_B)
     counts = ((pl->kp.m - pl->kp.init_q) & 1u) ? 2ull : 3ull;
   return counts * ((pl->kp.m + 31ull) / 32ull);
 }
@@ -1308,8 +1314,8 @@ void initial_states(const bo_trials_cfg *cfg, std::vector<bo_node_state> &st) {
   st.resize(cfg->N);
   for (uint32_t i = 0; i < cfg->N; ++i) {
     const bool f = cfg->faulty[i] != 0;
-    // (BO_MODE_BYZ_TALLY: a Byzantine node is alive and has no protocol state; no kernel writes its entry)
-    const bool byz = cfg->mode == BO_MODE_BYZ_TALLY && cfg->faulty[i] == 2u;
+    // (BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B: a Byzantine node is alive and has no protocol state; no kernel writes its entry)
+    const bool byz = (cfg->mode == BO_MODE_BYZ_TALLY || cfg->mode == BO_MODE_BYZ_RULE_B) && cfg->faulty[i] == 2u;
     st[i].killed = f && !byz ? 1 : 0;
     st[i].x = f ? -1 : (cfg->init_mode == BO_INIT_FIXED ? cfg->init[i] : -1);
     st[i].decided = f ? -1 : 0;

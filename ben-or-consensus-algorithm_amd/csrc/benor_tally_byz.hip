@@ -1,5 +1,10 @@
 // benor_tally_byz.hip -- three-valued count-level random delivery with Byzantine
-// senders (BO_MODE_BYZ_TALLY with b > 0 Byzantine nodes).
+// senders (BO_MODE_BYZ_TALLY with b > 0 Byzantine nodes), and the same
+// under Ben-Or's Byzantine-tolerant rule (BO_MODE_BYZ_RULE_B, b >= 0).
+//
+// Four entries from two trial loops, each a template over the rule applied to a
+// receiver's counts (RuleRef, RuleB below): variant 14 runs <RuleRef>, variant 15
+// <RuleB>.  Everything else in this comment holds for both.
 //
 // The model is benor_tally3.hip's with b of the m live nodes Byzantine: they send
 // at every step and lie, they never receive.  The h = m - b honest nodes run the
@@ -15,7 +20,7 @@
 //   BO_BYZ_OPPOSE: 0 if H1 > H0, b if H0 > H1, for every receiver; BO_BYZ_RANDOM's
 //     step on H0 == H1.
 // BO_BYZ_BALANCE and BO_BYZ_SPLIT, whose liars see the receiver's inbox, run a second
-// kernel of this file, benor_tally_heard_kernel (further down).
+// loop of this file, benor_tally_heard_kernel (further down).
 //
 // One wave = one trial, lane l of receiver group j = compact index 64 j + l over
 // the m live nodes, as in benor_tally_crash.hip, on the same helpers
@@ -51,12 +56,46 @@ namespace {
 constexpr uint32_t kByzCertain = 0xFFFFFFFFu;      // KParams::byz_one: every Byzantine message carries 1
 constexpr uint32_t kByzWgPerCu = 6u;               // resident workgroups the registers allow (__launch_bounds__ below)
 
+// The rule a receiver applies to its counts (c0, c1), the one thing in which BO_MODE_BYZ_TALLY and
+// BO_MODE_BYZ_RULE_B differ: the R-phase's proposal ballots of a group and the P-phase rule.
+// kNoLiar: the mode runs its kernel without a Byzantine node too (byz_n = 0: every step wave-uniform
+// with B1 = 0, no threshold read).
+struct RuleRef {                                   // the reference's crash-tolerant rule (node.ts:46-158)
+  static constexpr bool kNoLiar = false;           // (b = 0 is mode 4's plan)
+  static __device__ __forceinline__ void r(uint32_t c0, uint32_t c1, uint32_t, uint32_t, uint64_t hp, uint64_t &p0,
+                                           uint64_t &p1) {
+    p0 = ballot(c0 > c1) & hp;
+    p1 = ballot(c1 > c0) & hp;
+  }
+  static __device__ __forceinline__ uint64_t p(uint32_t c0, uint32_t c1, uint32_t, uint32_t F, uint64_t hp, uint32_t k0,
+                                               uint32_t k1, uint32_t tlo, uint32_t thi, uint32_t j, uint32_t r,
+                                               bool &decided) {
+    return p_rule(c0, c1, F, hp, k0, k1, tlo, thi, j, r, decided);
+  }
+};
+struct RuleB {                                     // Ben-Or's Protocol B, t = F
+  static constexpr bool kNoLiar = true;
+  static __device__ __forceinline__ void r(uint32_t c0, uint32_t c1, uint32_t N, uint32_t F, uint64_t hp, uint64_t &p0,
+                                           uint64_t &p1) {
+    r_rule_b(c0, c1, N, F, hp, p0, p1);
+  }
+  static __device__ __forceinline__ uint64_t p(uint32_t c0, uint32_t c1, uint32_t N, uint32_t F, uint64_t hp, uint32_t k0,
+                                               uint32_t k1, uint32_t tlo, uint32_t thi, uint32_t j, uint32_t r,
+                                               bool &decided) {
+    return p_rule_b(c0, c1, N, F, hp, k0, k1, tlo, thi, j, r, decided);
+  }
+};
+
+// The oblivious strategies (BO_BYZ_RANDOM, BO_BYZ_OPPOSE), for either rule: benor_tally_byz_kernel<RuleRef> is
+// variant 14's entry, <RuleB> variant 15's.  The entries themselves are the templates: a rule-templated
+// device function called from two plain entries compiles variant 14 with six more SGPR spills.
 // (six waves per SIMD: one more than benor_tally_crash.hip, there is no schedule and no alive plane to maintain)
+template <class Rule>
 __global__ void __launch_bounds__(256, 6) benor_tally_byz_kernel(KParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wv = threadIdx.x >> 6;
-  const uint32_t m = p.m, F = p.F, W = p.W, q = p.q, nb = p.byz_n;
+  const uint32_t N = p.N, m = p.m, F = p.F, W = p.W, q = p.q, nb = p.byz_n;
 
   uint32_t *lhist = reinterpret_cast<uint32_t *>(smem);
   const bool states = p.node_out != nullptr;       // a state launch: a DEC plane of its own
@@ -90,6 +129,8 @@ __global__ void __launch_bounds__(256, 6) benor_tally_byz_kernel(KParams p) {
       return false;
     }
     B1u = p.byz_one == kByzCertain ? nb : 0u;
+    if constexpr (Rule::kNoLiar)
+      if (nb == 0u) return false;                  // no Byzantine node: byz_thr is not there to search
     return p.byz_one != 0u && p.byz_one != kByzCertain;
   };
   // A lane with a B1 of its own searches its row of the one table where it lies in global memory.
@@ -140,8 +181,7 @@ __global__ void __launch_bounds__(256, 6) benor_tally_byz_kernel(KParams p) {
             draw3_lane(one_table, p.tally_cap, 0u, m, q, H0 + nb - B1, H1 + B1, k0, k1, tlo, thi, c, r, 0u, u,
                        (hp >> lane) & 1ull, c0, c1);
           }
-          p0 = ballot(c0 > c1) & hp;
-          p1 = ballot(c1 > c0) & hp;
+          Rule::r(c0, c1, N, F, hp, p0, p1);
         }
         if (lane == 0) P0[j] = p0, P1[j] = p1;
       }
@@ -173,7 +213,7 @@ __global__ void __launch_bounds__(256, 6) benor_tally_byz_kernel(KParams p) {
                      c1);
         }
         bool decided;
-        const uint64_t x1 = p_rule(c0, c1, F, hp, k0, k1, tlo, thi, j, r, decided);
+        const uint64_t x1 = Rule::p(c0, c1, N, F, hp, k0, k1, tlo, thi, j, r, decided);
         if (mine && decided) dec |= 1ull << j;     // sticky
         undecided = undecided || (mine && !((dec >> j) & 1ull));
         if (lane == 0) X1[j] = (X1[j] & ~hp) | x1;                       // a Byzantine node's bit is never written
@@ -234,12 +274,13 @@ __device__ __forceinline__ uint32_t heard_lies(uint32_t strategy, uint32_t c, ui
 }
 
 // benor_tally_byz_kernel's trial loop with every step of the first kind: no Binomial
-// thresholds (byz_thr and byz_lds are not read), no per-lane row.
+// thresholds (byz_thr and byz_lds are not read), no per-lane row.  byz_n > 0 (launch_tally_byz).
+template <class Rule>
 __global__ void __launch_bounds__(256, 6) benor_tally_heard_kernel(KParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wv = threadIdx.x >> 6;
-  const uint32_t m = p.m, F = p.F, W = p.W, q = p.q, nb = p.byz_n, strategy = p.byz_strategy;
+  const uint32_t N = p.N, m = p.m, F = p.F, W = p.W, q = p.q, nb = p.byz_n, strategy = p.byz_strategy;
 
   uint32_t *lhist = reinterpret_cast<uint32_t *>(smem);
   const bool states = p.node_out != nullptr;       // a state launch: a DEC plane of its own
@@ -294,8 +335,7 @@ __global__ void __launch_bounds__(256, 6) benor_tally_heard_kernel(KParams p) {
           const uint32_t nB = Hq != 0u ? heard_byz(Hq, nb, rest, k0, k1, tlo, thi, c, r, 0u) : rest;
           const uint32_t l1 = heard_lies(strategy, c, h0, h1, nB);
           const uint32_t c0 = h0 + nB - l1, c1 = h1 + l1;
-          p0 = ballot(c0 > c1) & hp;
-          p1 = ballot(c1 > c0) & hp;
+          Rule::r(c0, c1, N, F, hp, p0, p1);
         }
         if (lane == 0) P0[j] = p0, P1[j] = p1;
       }
@@ -323,7 +363,7 @@ __global__ void __launch_bounds__(256, 6) benor_tally_heard_kernel(KParams p) {
         const uint32_t l1 = heard_lies(strategy, c, h0, h1, nB);
         const uint32_t c0 = h0 + nB - l1, c1 = h1 + l1;
         bool decided;
-        const uint64_t x1 = p_rule(c0, c1, F, hp, k0, k1, tlo, thi, j, r, decided);
+        const uint64_t x1 = Rule::p(c0, c1, N, F, hp, k0, k1, tlo, thi, j, r, decided);
         if (mine && decided) dec |= 1ull << j;     // sticky
         undecided = undecided || (mine && !((dec >> j) & 1ull));
         if (lane == 0) X1[j] = (X1[j] & ~hp) | x1;                       // a Byzantine node's bit is never written
@@ -346,8 +386,11 @@ __global__ void __launch_bounds__(256, 6) benor_tally_heard_kernel(KParams p) {
 
 }  // namespace
 
-// The strategies whose liars see the receiver's inbox run benor_tally_heard_kernel.
-bool byz_heard(const KParams &p) { return p.byz_strategy == BO_BYZ_BALANCE || p.byz_strategy == BO_BYZ_SPLIT; }
+// The strategies whose liars see the receiver's inbox run the heard entry of the plan's rule; a
+// BO_MODE_BYZ_RULE_B plan without a Byzantine node has no inbox to read and runs the other one.
+bool byz_heard(const KParams &p) {
+  return p.byz_n != 0u && (p.byz_strategy == BO_BYZ_BALANCE || p.byz_strategy == BO_BYZ_SPLIT);
+}
 
 // The b Binomial thresholds go into LDS, once per workgroup, when a CU then holds as many
 // workgroups as without them: the fewer of what `lds_bytes` (histogram and the four waves'
@@ -359,17 +402,22 @@ bool byz_thr_in_lds(uint32_t lds_bytes, uint32_t b) {
 
 // Workgroups of the kernel that one CU holds at once (registers and LDS; 0 = unknown).
 int byz_blocks_per_cu(const KParams &p) {
-  return blocks_per_cu(byz_heard(p) ? benor_tally_heard_kernel : benor_tally_byz_kernel, p);
+  if (p.variant == 15u) return blocks_per_cu(byz_heard(p) ? benor_tally_heard_kernel<RuleB> : benor_tally_byz_kernel<RuleB>, p);
+  return blocks_per_cu(byz_heard(p) ? benor_tally_heard_kernel<RuleRef> : benor_tally_byz_kernel<RuleRef>, p);
 }
 
+// Variants 14 and 15.  Variant 15 alone runs without a Byzantine node (byz_n = 0: no thresholds, none in LDS).
 hipError_t launch_tally_byz(const KParams &plan, int grid, hipStream_t s) {
   const KParams p = state_launch(plan, byz_state_bytes(plan.W));
+  const bool rule_b = p.variant == 15u;
   const bool heard = byz_heard(p);                 // BO_BYZ_BALANCE, BO_BYZ_SPLIT: no thresholds, none in LDS
-  if (!p.tally_off || !p.tally_thr || !p.byz_plane || (heard ? p.byz_lds != 0u : !p.byz_thr) || p.W > kMaxW ||
-      p.byz_n == 0u || p.byz_n > p.m - p.q || plan.wave_bytes < byz_wave_bytes(p.W, p.tally_cap) ||
+  const bool no_thr = heard || p.byz_n == 0u;
+  if (!p.tally_off || !p.tally_thr || !p.byz_plane || (no_thr ? p.byz_lds != 0u : !p.byz_thr) || p.W > kMaxW ||
+      (p.byz_n == 0u && !rule_b) || p.byz_n > p.m - p.q || plan.wave_bytes < byz_wave_bytes(p.W, p.tally_cap) ||
       plan.lds_bytes < p.hist_bytes + kWavesPerBlock * plan.wave_bytes + (p.byz_lds ? 8u * p.byz_n : 0u))
     return hipErrorInvalidValue;
-  return launch_lds(heard ? benor_tally_heard_kernel : benor_tally_byz_kernel, p, grid, s);
+  if (rule_b) return launch_lds(heard ? benor_tally_heard_kernel<RuleB> : benor_tally_byz_kernel<RuleB>, p, grid, s);
+  return launch_lds(heard ? benor_tally_heard_kernel<RuleRef> : benor_tally_byz_kernel<RuleRef>, p, grid, s);
 }
 
 }  // namespace benor

@@ -4,8 +4,8 @@
 // here once: the per-wave LDS layouts, the threshold search, the three-class draw
 // in its wave-uniform and its per-lane form, the stream-6 walk whose word order is
 // the bit-exact contract with the oracle, a trial's start and end, the P-phase
-// rule, the per-node-state write-out, the random schedule, and the host's
-// occupancy query and launch.
+// rule (and both phases of Ben-Or's Byzantine-tolerant rule), the per-node-state
+// write-out, the random schedule, and the host's occupancy query and launch.
 //
 // The first part, the layouts, is plain C++ that also compiles on the host without
 // HIP (tests/tally_layout_check.cpp sweeps it); the rest is device code.
@@ -379,6 +379,31 @@ __device__ __forceinline__ uint64_t p_rule(uint32_t c0, uint32_t c1, uint32_t F,
     if (tie) x1 |= coin_ballot(k0, k1, tlo, thi, j, r, tie);
   }
   decided = d0l || d1l;
+  return x1;
+}
+
+// ---- Ben-Or's Byzantine-tolerant rule (Protocol B, N > 5t with t = F; BO_MODE_BYZ_RULE_B)
+// The R-phase: propose v iff more than (N + F) / 2 of the messages heard carry v, else
+// "?" (neither ballot).  Both cannot hold: c0 + c1 <= N - F.
+__device__ __forceinline__ void r_rule_b(uint32_t c0, uint32_t c1, uint32_t N, uint32_t F, uint64_t mask, uint64_t &p0,
+                                         uint64_t &p1) {
+  p0 = ballot(2u * c0 > N + F) & mask;
+  p1 = ballot(2u * c1 > N + F) & mask;
+}
+
+// The P-phase, p_rule's interface: v = the value with the strictly larger count (none on
+// c0 == c1, an empty tally included); with c_v > F the node adopts v, and decides iff
+// 2 c_v > N + F; otherwise x is the node's coin (coin_ballot, the coin stream of every batch
+// mode).  Ballots and integer compares only; counts are at most N <= 4096.
+__device__ __forceinline__ uint64_t p_rule_b(uint32_t c0, uint32_t c1, uint32_t N, uint32_t F, uint64_t mask, uint32_t k0,
+                                             uint32_t k1, uint32_t tlo, uint32_t thi, uint32_t j, uint32_t r,
+                                             bool &decided) {
+  const uint32_t cv = c1 > c0 ? c1 : c0;
+  const bool adopt = c0 != c1 && cv > F;
+  const uint64_t coin = mask & ~ballot(adopt);
+  uint64_t x1 = ballot(adopt && c1 > c0) & mask;
+  if (coin) x1 |= coin_ballot(k0, k1, tlo, thi, j, r, coin);
+  decided = adopt && 2u * cv > N + F;
   return x1;
 }
 

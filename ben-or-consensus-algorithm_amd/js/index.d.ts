@@ -96,8 +96,11 @@ export interface TrialsConfig {
    *    receiver independently with probability crashReach / 2^32; crashReach = 0 is mode 5 and REACH_ALL is
    *    mode 6 with a full cut, bit for bit),
    *  8 mode 4 with Byzantine senders (MODE_BYZ_TALLY: the nodes of byzantineList send at every step and lie,
-   *    they never receive; crashed + Byzantine <= F; without a Byzantine node it is mode 4 bit for bit) */
-  mode?: 0 | 1 | 2 | 3 | 4 | 5 | 6 | 7 | 8;
+   *    they never receive; crashed + Byzantine <= F; without a Byzantine node it is mode 4 bit for bit),
+   *  9 mode 8 under Ben-Or's Byzantine-tolerant rule (MODE_BYZ_RULE_B: Protocol B with F as its t -- propose v
+   *    iff 2 c_v > N + F, adopt the strict majority v iff c_v > F and decide iff 2 c_v > N + F, else the coin;
+   *    byzantineList, byzOne and byzStrategy as in mode 8; without a Byzantine node it still runs this rule) */
+  mode?: 0 | 1 | 2 | 3 | 4 | 5 | 6 | 7 | 8 | 9;
   /** event mode: deliveries after which node i is stopped (null = never);
    *  MODE_CRASH_TALLY, MODE_CRASH_PARTIAL, MODE_CRASH_SUBSET: the step at which node i crashes (null = never) */
   crashAt?: (number | null)[];
@@ -111,12 +114,12 @@ export interface TrialsConfig {
   /** MODE_CRASH_SUBSET: the probability, in units of 2^-32, that a crasher's last message reaches a receiver
    *  (0 .. REACH_ALL = 2^32 - 1: certainly); it fills the word that crashCut fills, so give one of the two */
   crashReach?: number;
-  /** MODE_BYZ_TALLY: true marks node i Byzantine (a node of faultyList is crashed and may not be in both) */
+  /** MODE_BYZ_TALLY, MODE_BYZ_RULE_B: true marks node i Byzantine (a node of faultyList is crashed and may not be in both) */
   byzantineList?: boolean[];
-  /** MODE_BYZ_TALLY: the probability, in units of 2^-32, that a Byzantine message carries 1, independently per
+  /** MODE_BYZ_TALLY, MODE_BYZ_RULE_B: the probability, in units of 2^-32, that a Byzantine message carries 1, independently per
    *  trial, sender, receiver, round and phase (0 .. 2^32 - 1: certainly); it fills the word that crashCut fills */
   byzOne?: number;
-  /** MODE_BYZ_TALLY: BYZ_RANDOM (default; each message by byzOne), BYZ_OPPOSE (every message carries the value
+  /** MODE_BYZ_TALLY, MODE_BYZ_RULE_B: BYZ_RANDOM (default; each message by byzOne), BYZ_OPPOSE (every message carries the value
    *  fewer honest senders hold at the step, byzOne's step on a tie), BYZ_BALANCE (the Byzantine messages in a
    *  receiver's inbox make its two tallies as equal as they can) or BYZ_SPLIT (they say 1 to a receiver of odd
    *  compact index, 0 to one of even index); the last two do not read byzOne.  It fills the word that crashCount
@@ -138,6 +141,7 @@ export declare const MODE_CRASH_SUBSET: 7;
 /** TrialsConfig.crashReach: every crasher reaches every receiver (include/benor.h, crash_reach = UINT32_MAX). */
 export declare const REACH_ALL: 4294967295;
 export declare const MODE_BYZ_TALLY: 8;
+export declare const MODE_BYZ_RULE_B: 9;
 /** TrialsConfig.byzStrategy (include/benor.h BO_BYZ_RANDOM, BO_BYZ_OPPOSE, BO_BYZ_BALANCE, BO_BYZ_SPLIT). */
 export declare const BYZ_RANDOM: 0;
 export declare const BYZ_OPPOSE: 1;

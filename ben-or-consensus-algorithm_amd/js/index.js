@@ -20,8 +20,9 @@ const MODE_LOCKSTEP = 0, MODE_RANDOM_DELIVERY = 1, MODE_EVENT = 2, MODE_RANDOM_T
   MODE_CRASH_TALLY = 5,
   MODE_CRASH_PARTIAL = 6,
   MODE_CRASH_SUBSET = 7,
-  MODE_BYZ_TALLY = 8;
-// runTrials cfg.byzStrategy (MODE_BYZ_TALLY): BO_BYZ_RANDOM, BO_BYZ_OPPOSE, BO_BYZ_BALANCE, BO_BYZ_SPLIT
+  MODE_BYZ_TALLY = 8,
+  MODE_BYZ_RULE_B = 9;
+// runTrials cfg.byzStrategy (MODE_BYZ_TALLY, MODE_BYZ_RULE_B): BO_BYZ_RANDOM, BO_BYZ_OPPOSE, BO_BYZ_BALANCE, BO_BYZ_SPLIT
 const BYZ_RANDOM = 0, BYZ_OPPOSE = 1, BYZ_BALANCE = 3, BYZ_SPLIT = 4;   // (2 is no strategy)
 // runTrials cfg.crashCut (MODE_CRASH_PARTIAL): a cut per trial and crasher (BO_CUT_RANDOM)
 const CUT_RANDOM = 0xFFFFFFFF;
@@ -222,5 +223,5 @@ module.exports = {
   getNodeState, getNodesState, getNodeStatus, reachedFinality, runTrials, delay,
   waitConsensus, liveStopEvents, getNodesStateAt,
   MODE_LOCKSTEP, MODE_RANDOM_DELIVERY, MODE_EVENT, MODE_RANDOM_TALLY, MODE_RANDOM_TALLY3, MODE_CRASH_TALLY,
-  MODE_CRASH_PARTIAL, CUT_RANDOM, MODE_CRASH_SUBSET, REACH_ALL, MODE_BYZ_TALLY, BYZ_RANDOM, BYZ_OPPOSE, BYZ_BALANCE, BYZ_SPLIT,
+  MODE_CRASH_PARTIAL, CUT_RANDOM, MODE_CRASH_SUBSET, REACH_ALL, MODE_BYZ_TALLY, MODE_BYZ_RULE_B, BYZ_RANDOM, BYZ_OPPOSE, BYZ_BALANCE, BYZ_SPLIT,
 };

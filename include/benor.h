@@ -220,6 +220,29 @@ enum {
  * and its results bit for bit.  Not modelled: Byzantine nodes together with
  * crashes during the run, lies that say "?", explicit lie masks.  Batch API only
  * (no network API, no `sweep`). */
+/* BYZ_RULE_B is BYZ_TALLY with the other rule of the same paper:
+ * Ben-Or's Byzantine-tolerant Protocol B, stated for N > 5t, with F as its t.
+ * Who is Byzantine (faulty[i] == 2) and f + b <= F, compact indices, senders and
+ * receivers, the four strategies with their draws (streams 5, 6, 10 and 11),
+ * byz_one and byz_strategy in the same union words, the coin stream, halting over
+ * the honest nodes, the histogram layout and the per-node states are BYZ_TALLY's,
+ * word for word, and so is every validation error.  Only the rule applied to a
+ * receiver's counts (c0, c1) at a step differs:
+ *   R-phase: propose 0 if 2 c0 > N + F, else 1 if 2 c1 > N + F, else "?" (both
+ *     cannot hold: c0 + c1 <= N - F).
+ *   P-phase: v = the value with the strictly larger count (none on c0 == c1, an
+ *     empty tally included).  If v exists and c_v > F: x = v, and the node has
+ *     decided iff 2 c_v > N + F (sticky; x is recomputed every round).  Otherwise
+ *     x is the node's coin (RANDOM_TALLY3's coin stream).
+ * F is not checked against N > 5F: outside the bound the mode measures what the
+ * rule does there (N <= 3F never proposes, every trial ends in bin 0..2).  For
+ * N > 5F the histogram's last bin and every bin R*3 + 2 stay 0, and a unanimous
+ * honest start v lands in bin[1*3 + v], under every strategy.  b = 0 is valid and
+ * is NOT RANDOM_TALLY3's plan, the rule differs: it runs this mode's kernel with
+ * every step wave-uniform and no stream-10 or stream-11 word, the same results
+ * at every byz_one and strategy (f = F then gives m == q).  Not modelled: what
+ * BYZ_TALLY does not model, other rules (Protocol A, Bracha), a common coin.
+ * Batch API only (no network API, no `sweep`). */
 enum {
   BO_MODE_LOCKSTEP = 0,
   BO_MODE_RANDOM_DELIVERY = 1,
@@ -229,10 +252,11 @@ enum {
   BO_MODE_CRASH_TALLY = 5,
   BO_MODE_CRASH_PARTIAL = 6,
   BO_MODE_CRASH_SUBSET = 7,
-  BO_MODE_BYZ_TALLY = 8
+  BO_MODE_BYZ_TALLY = 8,
+  BO_MODE_BYZ_RULE_B = 9
 };
 
-/* BO_MODE_BYZ_TALLY, byz_strategy. */
+/* BO_MODE_BYZ_TALLY and BO_MODE_BYZ_RULE_B, byz_strategy. */
 /* (2 is not a strategy: it stays BO_ERR_INVALID_ARGUMENT, as it was before BALANCE and SPLIT existed) */
 enum { BO_BYZ_RANDOM = 0, BO_BYZ_OPPOSE = 1, BO_BYZ_BALANCE = 3, BO_BYZ_SPLIT = 4 };
 
@@ -379,12 +403,12 @@ typedef struct bo_trials_cfg {
         uint32_t crash_cut;   /* CRASH_PARTIAL: every crasher's cut, 0..m0, or BO_CUT_RANDOM */
         uint32_t crash_reach; /* CRASH_SUBSET: the probability, in units of 2^-32, that a crasher's last message
                                  reaches a receiver (0: never, UINT32_MAX: certainly); every value is valid */
-        uint32_t byz_one;     /* BYZ_TALLY: the probability, in units of 2^-32, that a Byzantine message carries 1
+        uint32_t byz_one;     /* BYZ_TALLY, BYZ_RULE_B: the probability, in units of 2^-32, that a Byzantine message carries 1
                                  (0: never, UINT32_MAX: certainly); every value is valid */
     };                        /* the other modes ignore it */
     uint64_t seed;            /* Philox4x32-10 key */
     const uint8_t *faulty;    /* host [N]; non-zero = faulty: exactly F set (LOCKSTEP, EVENT), at most F (RANDOM_DELIVERY, RANDOM_TALLY, RANDOM_TALLY3, CRASH_TALLY, CRASH_PARTIAL, CRASH_SUBSET);
-                                 BYZ_TALLY alone reads the value: 1 crashed from the start, 2 Byzantine, together at most F */
+                                 BYZ_TALLY and BYZ_RULE_B alone read the value: 1 crashed from the start, 2 Byzantine, together at most F */
     const int8_t *init;       /* host [N]; used when init_mode == BO_INIT_FIXED */
     /* EVENT mode: GET /stop schedule.  crash_at[i] = number of deliveries
      * after which node i is stopped (UINT32_MAX = never), or, when crash_at is
@@ -394,12 +418,12 @@ typedef struct bo_trials_cfg {
      * at which node i crashes (UINT32_MAX = never; entries of faulty nodes are
      * ignored), or, when crash_at is NULL, crash_count distinct initially-live
      * nodes at uniform steps in [0, crash_window), drawn per trial.
-     * The other modes ignore the three fields, except that BYZ_TALLY reads the
-     * crash_count word as byz_strategy. */
+     * The other modes ignore the three fields, except that BYZ_TALLY and BYZ_RULE_B
+     * read the crash_count word as byz_strategy. */
     const uint32_t *crash_at; /* host [N] or NULL */
     union {                   /* one word, the layout of the struct is that of ABI version 8 */
         uint32_t crash_count;
-        uint32_t byz_strategy; /* BYZ_TALLY: a BO_BYZ_* strategy */
+        uint32_t byz_strategy; /* BYZ_TALLY, BYZ_RULE_B: a BO_BYZ_* strategy */
     };
     uint32_t crash_window;
 } bo_trials_cfg;
@@ -443,9 +467,9 @@ int bo_plan_check(bo_plan *plan);
  * (c0 = M - c1); the P-phase counts c1 when M is odd (no tie, so no "?"
  * proposal: c0 = m - c1) and c0, c1 otherwise -- 2 or 3 x ceil(m/32).
  * RANDOM_DELIVERY: both values in both phases, 4 x ceil(m/32).  RANDOM_TALLY,
- * RANDOM_TALLY3, CRASH_TALLY, CRASH_PARTIAL, CRASH_SUBSET and BYZ_TALLY answer RANDOM_DELIVERY's
+ * RANDOM_TALLY3, CRASH_TALLY, CRASH_PARTIAL, CRASH_SUBSET, BYZ_TALLY and BYZ_RULE_B answer RANDOM_DELIVERY's
  * unit, the work they stand in for (the crash modes with m = the initially-live count,
- * BYZ_TALLY with m = the live nodes, honest and Byzantine, as bo_plan_live_nodes reports it). */
+ * BYZ_TALLY and BYZ_RULE_B with m = the live nodes, honest and Byzantine, as bo_plan_live_nodes reports it). */
 uint64_t bo_plan_popc_words_per_node_round(const bo_plan *plan);
 uint32_t bo_plan_live_nodes(const bo_plan *plan);
 
@@ -484,13 +508,16 @@ enum {
                               TALLY_CRASH's wave-uniform draw for the lanes that hear none of them and one
                               per-lane draw, each lane searching the row of its own pool in global memory,
                               for the others; one table per pool size */
-  BO_KERNEL_TALLY_BYZ = 14  /* BO_MODE_BYZ_TALLY with b > 0 Byzantine nodes: TALLY3's draw among all m live
+  BO_KERNEL_TALLY_BYZ = 14, /* BO_MODE_BYZ_TALLY with b > 0 Byzantine nodes: TALLY3's draw among all m live
                               senders for the honest receivers (a constant honest plane in place of the alive
                               plane); a step whose Byzantine messages are the same for every receiver is
                               wave-uniform with its row staged in LDS, otherwise every lane draws its own
                               Binomial count of lying 1s (Philox stream 10) and searches the row of its own
                               class sizes in global memory; one table, (m, q) (b = 0 runs RANDOM_TALLY3's
                               kernel choice) */
+  BO_KERNEL_TALLY_BYZ_B = 15 /* BO_MODE_BYZ_RULE_B with an honest node, b = 0 included: TALLY_BYZ's two trial loops
+                              instantiated with Protocol B's rule (thresholds at (N + F) / 2 and F + 1); the same
+                              LDS layout, launch bounds, grid and state launch */
 };
 
 /* The kernel family bo_plan_launch runs for this plan.  (The per-node-state

@@ -14,7 +14,7 @@ median and minimum ms per launch and the variant's median / first variant's.
 
 A shape may carry a fourth field f < F (the first f nodes crashed, the rest of
 F the random-delivery slack: BO_MODE_RANDOM_DELIVERY).  A variant may also name
-the delivery mode with the pseudo-variable `mode` (lockstep, random, tally, tally3, crash, partial, subset or byz),
+the delivery mode with the pseudo-variable `mode` (lockstep, random, tally, tally3, crash, partial, subset, byz or byzb),
 so the mask-level and the count-level random-delivery modes are timed
 alternately on one plan each:
 
@@ -52,6 +52,13 @@ and not `byz_one`); next to mode:tally3 it times what the liars cost:
         "t3=mode:tally3;half=mode:byz,byzantine:100,byz_one:0.5;all=mode:byz,byzantine:100,byz_one:all;opp=mode:byz,byzantine:100,byz_one:0.5,byz_strategy:oppose"
     python tools/ab_inproc.py --rounds 7 --reps 5 --shapes "1024,340,100000,0" --variants \
         "t3=mode:tally3;half=mode:byz,byzantine:100,byz_one:0.5;bal=mode:byz,byzantine:100,byz_strategy:balance;split=mode:byz,byzantine:100,byz_strategy:split"
+
+`mode:byzb` (BO_MODE_BYZ_RULE_B, Ben-Or's Byzantine-tolerant rule) takes mode:byz's three variables;
+next to mode:byz on the same liars it times the two rules, whose rounds per trial differ by design
+(compare node_rounds_per_s, the figure per unit of work):
+
+    python tools/ab_inproc.py --rounds 7 --reps 5 --shapes "1024,204,100000,0" --variants \
+        "m8=mode:byz,byzantine:16,byz_strategy:split;m9=mode:byzb,byzantine:16,byz_strategy:split"
 
 Every line also reports
 the live node-rounds per second its launches represent (bench.py node_rounds)
@@ -107,13 +114,14 @@ def main():
     mode_ids = {"lockstep": benor.BO_MODE_LOCKSTEP, "random": benor.BO_MODE_RANDOM_DELIVERY,
                 "tally": benor.BO_MODE_RANDOM_TALLY, "tally3": benor.BO_MODE_RANDOM_TALLY3,
                 "crash": benor.BO_MODE_CRASH_TALLY, "partial": benor.BO_MODE_CRASH_PARTIAL,
-                "subset": benor.BO_MODE_CRASH_SUBSET, "byz": benor.BO_MODE_BYZ_TALLY}
+                "subset": benor.BO_MODE_CRASH_SUBSET, "byz": benor.BO_MODE_BYZ_TALLY,
+                "byzb": benor.BO_MODE_BYZ_RULE_B}
     bad = sorted({v for v in modes.values() if v is not None and v not in mode_ids})
     if bad:
         ap.error(f"mode must be one of {sorted(mode_ids)}: {bad}")
     byz_keys = ("byzantine", "byz_one", "byz_strategy")
-    if any(any(k in sc for k in byz_keys) != (modes[name] == "byz") for name, sc in scheds.items()):
-        ap.error("byzantine / byz_one / byz_strategy go with mode:byz, and it with them")
+    if any(any(k in sc for k in byz_keys) != (modes[name] in ("byz", "byzb")) for name, sc in scheds.items()):
+        ap.error("byzantine / byz_one / byz_strategy go with mode:byz or mode:byzb, and they with them")
     if any(any(k not in byz_keys for k in sc) and modes[name] not in ("crash", "partial", "subset")
            for name, sc in scheds.items()):
         ap.error("crash_count / crash_window / crash_at need mode:crash, mode:partial or mode:subset")
@@ -124,7 +132,7 @@ def main():
 
     def schedule(name, N, f):
         sc, kw = dict(scheds[name]), {}
-        if modes[name] == "byz":
+        if modes[name] in ("byz", "byzb"):
             b, one = int(sc.get("byzantine", 0)), sc.get("byz_one", "0.5")
             return {"byzantine": [f <= i < f + b for i in range(N)],
                     "byz_one": 0xFFFFFFFF if one == "all" else benor.reach_word(float(one)) if "." in one else int(one),
