@@ -105,6 +105,7 @@ KNOBS = {
     "BENOR_EVENT_LANES_PER_CU": "tuning", "BENOR_TEST_DEFER_SEG_CAP": "test", "BENOR_TIMELINE": "diagnostic",
     "BENOR_EVENT_FORM": "validation", "BENOR_LIVE_WAVES": "tuning", "BENOR_EVENT_STATS": "diagnostic",
     "BENOR_MFMA_PAIR": "validation", "BENOR_MFMA_DYNAMIC": "validation", "BENOR_MFMA_CHUNK": "tuning",
+    "BENOR_MFMA_STRIP": "validation",
 }
 
 BASE_NODE_PORT = 3000          # src/config.ts:1 (kept for the HTTP-shaped helpers)

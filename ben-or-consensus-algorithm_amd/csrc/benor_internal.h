@@ -7,6 +7,7 @@
 
 #include "benor.h"
 #include "benor_mfma_sched.h"
+#include "benor_mfma_strip.h"
 
 namespace benor {
 
@@ -222,6 +223,16 @@ constexpr uint64_t kDeferChunk = 1ull << 22;   // trials per matrix-core launch 
 const char *knob(const char *name);
 uint32_t knob_u32(const char *name, uint32_t dflt);
 bool knob_is(const char *name, const char *value);
+
+// The paired KIND 0 matrix-core kernel takes its strip form (benor_mfma.h
+// STRIP) on this plan: W >= 5 and at most 16 live rows in the last 32-row
+// receiver tile, from W = 7 on by the planner's rule (stripf::kPlannedMinW).
+// BENOR_MFMA_STRIP (validation): "0" keeps the 32-row form everywhere, "1"
+// takes the strip at W = 5 and 6 too and changes nothing on other shapes.
+inline bool mfma_strip_form(const KParams &p) {
+  if (p.variant != 7u || p.G != 0u || p.W > 16u || !stripf::eligible(p.W, p.m) || knob_is("BENOR_MFMA_PAIR", "0")) return false;
+  return knob_is("BENOR_MFMA_STRIP", "1") || (stripf::planned(p.W, p.m) && !knob_is("BENOR_MFMA_STRIP", "0"));
+}
 
 // Pick the tally block size G and fill nblocks / LDS sizes.
 void plan_geometry(KParams &p);

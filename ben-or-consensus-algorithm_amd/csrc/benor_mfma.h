@@ -106,17 +106,43 @@
 //    (0.968, ranges 21.94-22.34 and 21.33-21.49), N=1000/F=333 0.973, N=1023/F=0
 //    0.987; static at 3 or 9 workgroups per CU is slower than at 8 (1.036,
 //    1.007), and C = 4, 8, 16 are within 0.7 % of each other.
+//  * Strip (paired form, at most 16 live rows in the last 32-row tile; by the
+//    planner from W = 7, at W = 5, 6 behind BENOR_MFMA_STRIP=1;
+//    benor_mfma_strip.h, tests/strip_layout_check.cpp): that tile pays W + KP
+//    whole products for <= 16 receivers.  It runs instead in the 16-row shape
+//    v_mfma_scale_f32_16x16x128_f8f6f4 (16 receivers x 16 trials x 128 senders,
+//    7.11 ns per SIMD against the 32-row shape's 14.13 under the same load,
+//    tools/mfma32_probe shape: half the cost at the same clock), once per trial
+//    half, after the other tiles of the phase: 2 ceil(W / 2) + 2 ceil(KP / 2)
+//    half products.  The operand is the 32-row one after v_permlane16_swap_b32
+//    on two K chunks' registers, in place, and one swap per packed word brings
+//    the results back.  Padded rows are the one place where products can go:
+//    no receiver exists there, and every real receiver still gets its own
+//    count.  Headline: 462 + 24 products per group for 484, 167 VGPRs (three
+//    waves per SIMD as before; the live-row masks sit in SGPRs and the Philox
+//    block numbers are recomputed per group for that).  In one process against
+//    BENOR_MFMA_STRIP=0, median of 7 rounds (profiles/r18_mfma_strip_ab.jsonl):
+//    headline 21.35 -> 21.12 ms (0.989, ranges 21.22-21.53 and 20.92-21.16),
+//    N=1003/F=0 0.990, each range wholly below the other form's, as at W = 7,
+//    8, 9, 10, 13 (0.980 .. 0.993, profiles/r18_mfma_strip_ab_w.jsonl); W = 5
+//    and 6 gain 0.984 and 0.989 in the median with overlapping ranges, so the
+//    planner leaves them on the 32-row form; shapes with more live rows
+//    (N=1000/F=333, N=700/F=233, N=273/F=0) unchanged.  bench.py against the parent commit, alternated on one box
+//    (profiles/r18_bench_parent_strip.jsonl): 21.42 / 21.38 -> 21.11 / 21.16 ms
+//    per step.
 #pragma once
 
 #include "benor_device.h"
 #include "benor_mfma_pair.h"
 #include "benor_mfma_sched.h"
+#include "benor_mfma_strip.h"
 
 namespace benor {
 
 typedef int mf_v4i __attribute__((ext_vector_type(4)));
 typedef int mf_v8i __attribute__((ext_vector_type(8)));
 typedef float mf_v16f __attribute__((ext_vector_type(16)));
+typedef float mf_v4f __attribute__((ext_vector_type(4)));
 
 // s_getreg operands (id | (size - 1) << 11, offset 0): the whole HW_ID
 // (SE_ID 15:13, SH_ID 12, CU_ID 11:8) and XCC_ID (3:0) registers.
@@ -129,6 +155,41 @@ __device__ __forceinline__ mf_v16f mfma_count(mf_v4i a, mf_v4i b, mf_v16f c) {
   const mf_v8i a8 = __builtin_shufflevector(a, a, 0, 1, 2, 3, -1, -1, -1, -1);   // fp4 reads the low 4 VGPRs
   const mf_v8i b8 = __builtin_shufflevector(b, b, 0, 1, 2, 3, -1, -1, -1, -1);
   return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, c, 4, 4, 0, 127 + SA, 0, 127);
+}
+
+// The 16-row shape of the same product: 16 receivers x 16 trials x 128
+// senders.  Lane l brings column l & 15 and K block l >> 4 (32 e2m1 nibbles
+// in 4 VGPRs); result register j of lane l is row 4 (l >> 4) + j of that column.
+__device__ __forceinline__ mf_v4f mfma_count16(mf_v4i a, mf_v4i b, mf_v4f c) {
+  const mf_v8i a8 = __builtin_shufflevector(a, a, 0, 1, 2, 3, -1, -1, -1, -1);
+  const mf_v8i b8 = __builtin_shufflevector(b, b, 0, 1, 2, 3, -1, -1, -1, -1);
+  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a8, b8, c, 4, 4, 0, 127, 0, 127);
+}
+
+// v_permlane16_swap_b32 on one register pair: the odd 16-lane rows of a trade
+// places with the even rows of b.  Of two registers in the 32-trial layout
+// (rows 0 / 2 = trials 0..15, rows 1 / 3 = trials 16..31) a becomes trials
+// 0..15 in all four rows and b trials 16..31; applied again it is undone, so
+// of two registers in the 16-trial layouts (a: trials 0..15, b: 16..31) each
+// lane of both ends up with values of its own 32-layout trial.
+__device__ __forceinline__ void row_swap(uint32_t &a, uint32_t &b) {
+  const auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
+  a = r[0];
+  b = r[1];
+}
+
+// The strip's B operands for K chunks c, c + 1 of the 32-trial layout
+// (c + 1 == n: against zeros): 128 distinct senders of trials 0..15 in lo,
+// of trials 16..31 in hi.  In place: x[c], x[c + 1] are dead afterwards.
+template <int N>
+__device__ __forceinline__ void strip_operands(mf_v4i (&x)[N], int c, mf_v4i &lo, mf_v4i &hi) {
+#pragma unroll
+  for (int v = 0; v < 4; ++v) {
+    uint32_t a = (uint32_t)x[c][v], b = c + 1 < N ? (uint32_t)x[c + 1][v] : 0u;
+    row_swap(a, b);
+    lo[v] = (int)a;
+    hi[v] = (int)b;
+  }
 }
 
 // Sign bits of four f32 results as bytes (0xff where negative): v_perm_b32
@@ -198,10 +259,13 @@ __device__ __forceinline__ mf_v4i expand_votes(uint32_t w) {
 
 // Paired form: four results (two receivers each, benor_mfma_pair.h) -> one
 // B-operand dword of the P-phase, eight e2m1 nibbles.
-__device__ __forceinline__ uint32_t pack_pair4(const mf_v16f &acc, int base) {
-  const uint32_t x = __builtin_amdgcn_perm(__float_as_uint(acc[base + 1]), __float_as_uint(acc[base + 0]), pairf::kSelX);
-  const uint32_t y = __builtin_amdgcn_perm(__float_as_uint(acc[base + 3]), __float_as_uint(acc[base + 2]), pairf::kSelY);
+__device__ __forceinline__ uint32_t pack_pair4(float u0, float u1, float u2, float u3) {
+  const uint32_t x = __builtin_amdgcn_perm(__float_as_uint(u1), __float_as_uint(u0), pairf::kSelX);
+  const uint32_t y = __builtin_amdgcn_perm(__float_as_uint(u3), __float_as_uint(u2), pairf::kSelY);
   return (x & pairf::kMaskX) | (y & pairf::kMaskY);
+}
+__device__ __forceinline__ uint32_t pack_pair4(const mf_v16f &acc, int base) {
+  return pack_pair4(acc[base + 0], acc[base + 1], acc[base + 2], acc[base + 3]);
 }
 
 // The claim words of the dynamic form as benor_mfma_sched.h's atomics policy
@@ -231,11 +295,25 @@ struct ClaimWords {
 // PAIR (KIND 0 only): two receiver tiles per accumulator instead of one.
 // DYN (the paired form only): the waves claim chunks of p.mfma_chunk groups
 // from the plan's claim words (benor_mfma_sched.h) instead of striding.
-template <int W, bool HALF, int KIND, bool PAIR = false, bool DYN = false>
+// STRIP (the paired form, W >= 5, a last tile of <= 16 live rows): that tile
+// runs in the 16-row shape, 16 receivers x 16 trials x 128 senders at half a
+// 32-row product's cycles, after the other tiles of each phase, when the
+// phase's operand is otherwise dead: v_permlane16_swap_b32 on two K chunks'
+// registers turns them in place into one 128-sender operand per trial half
+// (row_swap), so the tile costs 2 ceil(W / 2) + 2 ceil(KP / 2) half products
+// instead of W + KP whole ones.  Its eight results per lane are thresholded
+// as a lone low field, and one more swap per packed word brings them back to
+// the lane of their 32-layout trial: the proposals into free nibbles of the
+// last P-phase chunk, the decisions into s_or / s_and.
+// tests/strip_layout_check.cpp models the lanes and the swaps.
+template <int W, bool HALF, int KIND, bool PAIR = false, bool DYN = false, bool STRIP = false>
 __global__ void __launch_bounds__(256) benor_mfma_kernel(KParams p) {
   static_assert(!PAIR || KIND == 0, "the paired form is KIND 0's");
   static_assert(!DYN || PAIR, "dynamic claims are the paired form's");
+  static_assert(!STRIP || (PAIR && W >= stripf::kMinW), "the strip is the paired plain-loop form's");
   constexpr int MT = 2 * W - (HALF ? 1 : 0);   // 32-receiver tiles (HALF: the last chunk holds <= 32 senders)
+  constexpr int MTM = STRIP ? MT - 1 : MT;     // ... that run in the 32-row shape
+  constexpr int NPAIR = (MTM + 1) / 2;         // their accumulators in the paired form
   constexpr int KP = (MT + 1) / 2;             // P-phase K chunks: two tiles' results each
   constexpr int NB = (W + 1) / 2;              // Philox init blocks per trial (128 senders each)
   constexpr int NJ = (NB + 1) / 2;             // blocks per lane: half h draws blocks h, h + 2, ...
@@ -316,11 +394,22 @@ __global__ void __launch_bounds__(256) benor_mfma_kernel(KParams p) {
     if (j < 8) tail0 |= nib;
     else tail1 |= nib;
   }
+  // STRIP: its 4-register accumulators start from the first four of cr / cp
+  // (opaque here, so that they are sub-registers and not copies)
+  if constexpr (STRIP) asm volatile("" : "+v"(cr), "+v"(cp));
   // Paired form: the last pair's packed dword k holds results 4k .. 4k + 3 of
   // its low tile (MT odd: the last tile; MT even: a full one) and of its high
   // tile (MT even: the last tile; MT odd: none, its field carries no count).
   uint32_t tailq[4] = {0u, 0u, 0u, 0u};
-  if constexpr (PAIRED) {
+  // STRIP: after the swap back a lane's two packed words hold rows 8h + i and
+  // 8h + 4 + i of the last tile in their low nibbles i.  The live-row masks
+  // of both lane halves stay in SGPRs (strip_live[2 h + word]): the kernel is
+  // at its VGPR limit for three waves per SIMD.
+  [[maybe_unused]] uint32_t strip_live[4] = {0u, 0u, 0u, 0u};
+  if constexpr (STRIP) {
+#pragma unroll
+    for (uint32_t i = 0; i < 4u; ++i) strip_live[i] = stripf::live_mask(mrem, i >> 1, i & 1u);
+  } else if constexpr (PAIRED) {
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       const uint32_t row = (uint32_t)((j & 3) + 8 * (j >> 2)) + 4u * h;
@@ -395,12 +484,14 @@ __global__ void __launch_bounds__(256) benor_mfma_kernel(KParams p) {
     } else if (random_init) {
       const uint64_t trial = lds_u64(keys + 2) + t;
       const uint2 kk = lds_keys(keys);
+      uint32_t hb = h;                         // STRIP: the block numbers 2j + h are not kept across groups (VGPRs)
+      if constexpr (STRIP) asm volatile("" : "+v"(hb));
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         // Block b = 2j + h: words 4b .. 4b+3 = chunks 2b, 2b+1.  Half h keeps
         // words 4b + h, 4b + 2 + h and trades the other two with lane l ^ 32.
         const uint4 r = philox4x32_10(kk.x, kk.y,
-                                      make_uint4((uint32_t)trial, (uint32_t)(trial >> 32), 2u * j + h, kStreamInit << 24));
+                                      make_uint4((uint32_t)trial, (uint32_t)(trial >> 32), 2u * j + hb, kStreamInit << 24));
         uint32_t q4[4];
         half_trade(r, h, q4);
 #pragma unroll
@@ -456,12 +547,12 @@ __global__ void __launch_bounds__(256) benor_mfma_kernel(KParams p) {
       }
     } else if constexpr (PAIRED) {
 #pragma unroll
-      for (int a = 0; a < KP; ++a) {
+      for (int a = 0; a < NPAIR; ++a) {
         asm volatile("" : "+v"(ones));
         mf_v16f acc = mfma_count(ones, bx[0], cr);
 #pragma unroll
         for (int c = 1; c < W; ++c) acc = mfma_count(ones, bx[c], acc);
-        if (2 * a + 1 < MT) {
+        if (2 * a + 1 < MTM) {
           asm volatile("" : "+v"(ones));
 #pragma unroll
           for (int c = 0; c < W; ++c) acc = mfma_count<pairf::kShiftR>(ones, bx[c], acc);
@@ -469,6 +560,35 @@ __global__ void __launch_bounds__(256) benor_mfma_kernel(KParams p) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) pb[a][k] = (int)pack_pair4(acc, 4 * k);
         __builtin_amdgcn_sched_barrier(0);     // one pair's accumulator live at a time
+      }
+      if constexpr (STRIP) {
+        // the last tile: bx[] to the 16-trial layouts in place, one product
+        // chain per trial half, each a lone low field
+        asm volatile("" : "+v"(ones));
+        const mf_v4f cr4 = __builtin_shufflevector(cr, cr, 0, 1, 2, 3);
+        mf_v4f sacc[2] = {cr4, cr4};
+#pragma unroll
+        for (int c = 0; c < W; c += 2) {
+          mf_v4i lo, hi;
+          strip_operands(bx, c, lo, hi);
+          sacc[0] = mfma_count16(ones, lo, sacc[0]);
+          sacc[1] = mfma_count16(ones, hi, sacc[1]);
+        }
+        uint32_t q0 = pack_pair4(sacc[0][0], sacc[0][1], sacc[0][2], sacc[0][3]);
+        uint32_t q1 = pack_pair4(sacc[1][0], sacc[1][1], sacc[1][2], sacc[1][3]);
+        row_swap(q0, q1);                      // every lane: proposals of its own trial
+        uint32_t l0 = strip_live[0], l1 = strip_live[1], l2 = strip_live[2], l3 = strip_live[3];
+        asm volatile("" : "+s"(l0), "+s"(l1), "+s"(l2), "+s"(l3));   // selected here, not once into VGPRs
+        q0 &= h ? l2 : l0;
+        q1 &= h ? l3 : l1;
+        if constexpr (MTM & 1) {
+          // chunk KP - 1 holds the last 32-row tile in its low nibbles
+          pb[KP - 1][0] |= (int)(q0 << 4);
+          pb[KP - 1][1] |= (int)(q1 << 4);
+        } else {
+          pb[KP - 1] = mf_v4i{(int)q0, (int)q1, 0, 0};
+        }
+        __builtin_amdgcn_sched_barrier(0);
       }
     } else if constexpr (SURE && W <= 4) {
       // Few products per tile (W): the sign packing of tile i - 1 is issued
@@ -524,7 +644,9 @@ __global__ void __launch_bounds__(256) benor_mfma_kernel(KParams p) {
       }
       __builtin_amdgcn_sched_barrier(0);   // one tile's accumulator live at a time
     }
-    if constexpr (PAIRED) {
+    if constexpr (STRIP) {
+      // masked above; a lone tile's high field packs to zero nibbles
+    } else if constexpr (PAIRED) {
       // padded receiver rows, and the high field of a last tile that runs alone
 #pragma unroll
       for (int k = 0; k < 4; ++k) pb[KP - 1][k] &= (int)tailq[k];
@@ -587,19 +709,46 @@ __global__ void __launch_bounds__(256) benor_mfma_kernel(KParams p) {
         __builtin_amdgcn_s_setprio(0);
       } else if constexpr (PAIRED) {
 #pragma unroll
-        for (int a = 0; a < KP; ++a) {
+        for (int a = 0; a < NPAIR; ++a) {
           asm volatile("" : "+v"(ones));
           mf_v16f acc = mfma_count(ones, pb[0], cp);
 #pragma unroll
           for (int c = 1; c < KP; ++c) acc = mfma_count(ones, pb[c], acc);
-          if (2 * a + 1 < MT) {
+          if (2 * a + 1 < MTM) {
             asm volatile("" : "+v"(ones));
 #pragma unroll
             for (int c = 0; c < KP; ++c) acc = mfma_count<pairf::kShiftP>(ones, pb[c], acc);
           }
           // padded receiver rows need no mask, as in the one-tile form below
-          fold_pair(acc, 2 * a + 1 >= MT);
+          fold_pair(acc, 2 * a + 1 >= MTM);
           asm volatile("" : "+v"(s_or), "+v"(s_and));   // fold pair by pair: one accumulator live
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (STRIP) {
+          // the last tile, as in the R-phase: pb[] in place, lone low fields;
+          // its padded rows need no mask either
+          asm volatile("" : "+v"(ones));
+          const mf_v4f cp4 = __builtin_shufflevector(cp, cp, 0, 1, 2, 3);
+          mf_v4f sacc[2] = {cp4, cp4};
+#pragma unroll
+          for (int c = 0; c < KP; c += 2) {
+            mf_v4i lo, hi;
+            strip_operands(pb, c, lo, hi);
+            sacc[0] = mfma_count16(ones, lo, sacc[0]);
+            sacc[1] = mfma_count16(ones, hi, sacc[1]);
+          }
+          uint32_t o[2], n[2];
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            const uint32_t u0 = __float_as_uint(sacc[i][0]), u1 = __float_as_uint(sacc[i][1]);
+            const uint32_t u2 = __float_as_uint(sacc[i][2]), u3 = __float_as_uint(sacc[i][3]);
+            o[i] = u0 | u1 | u2 | u3;
+            n[i] = u0 & u1 & u2 & u3;
+          }
+          row_swap(o[0], o[1]);                // every lane: decisions of its own trial
+          row_swap(n[0], n[1]);
+          s_or |= o[0] | o[1];
+          s_and &= (n[0] & n[1]) | pairf::kIndPHigh;
           __builtin_amdgcn_sched_barrier(0);
         }
       } else if constexpr (W <= 4) {
@@ -754,31 +903,47 @@ __global__ void __launch_bounds__(256) benor_mfma_kernel(KParams p) {
   flush_hist(lhist, p);
 }
 
-template <int W, int KIND, bool PAIR = false, bool DYN = false>
+template <int W, int KIND, bool PAIR = false, bool DYN = false, bool STRIP = false>
 static inline void launch_mfma_kind(const KParams &p, int grid, hipStream_t s) {
   if (p.m <= 64u * (uint32_t)(W - 1) + 32u)
-    hipLaunchKernelGGL((benor_mfma_kernel<W, true, KIND, PAIR, DYN>), dim3(grid), dim3(64 * kWavesPerBlock), p.hist_bytes, s, p);
+    hipLaunchKernelGGL((benor_mfma_kernel<W, true, KIND, PAIR, DYN, STRIP>), dim3(grid), dim3(64 * kWavesPerBlock), p.hist_bytes, s, p);
   else
-    hipLaunchKernelGGL((benor_mfma_kernel<W, false, KIND, PAIR, DYN>), dim3(grid), dim3(64 * kWavesPerBlock), p.hist_bytes, s, p);
+    hipLaunchKernelGGL((benor_mfma_kernel<W, false, KIND, PAIR, DYN, STRIP>), dim3(grid), dim3(64 * kWavesPerBlock), p.hist_bytes, s, p);
 }
+
 
 // KIND 0's form: two receiver tiles per accumulator; BENOR_MFMA_PAIR=0
 // (validation) runs the one-tile form on the same trials, always statically
 // scheduled.  p.mfma_chunk > 0 (mfma_chunk(), per launch): the dynamic form.
 template <int W>
 static inline void launch_mfma_sure(const KParams &p, int grid, hipStream_t s) {
-  if (knob_is("BENOR_MFMA_PAIR", "0")) launch_mfma_kind<W, 0, false>(p, grid, s);
-  else if (p.mfma_chunk && p.mfma_claim) launch_mfma_kind<W, 0, true, true>(p, grid, s);
+  if (knob_is("BENOR_MFMA_PAIR", "0")) return launch_mfma_kind<W, 0, false>(p, grid, s);
+  const bool dyn = p.mfma_chunk && p.mfma_claim;
+  if constexpr (W >= stripf::kMinW) {
+    if (mfma_strip_form(p)) {
+      if (dyn) launch_mfma_kind<W, 0, true, true, true>(p, grid, s);
+      else launch_mfma_kind<W, 0, true, false, true>(p, grid, s);
+      return;
+    }
+  }
+  if (dyn) launch_mfma_kind<W, 0, true, true>(p, grid, s);
   else launch_mfma_kind<W, 0, true>(p, grid, s);
 }
 
 template <int W>
 int mfma_sure_blocks_per_cu(const KParams &p) {
   int n = 0;
-  const hipError_t e =
-      p.m <= 64u * (uint32_t)(W - 1) + 32u
-          ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, benor_mfma_kernel<W, true, 0, true, true>, 64 * kWavesPerBlock, p.hist_bytes)
-          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, benor_mfma_kernel<W, false, 0, true, true>, 64 * kWavesPerBlock, p.hist_bytes);
+  const bool half = p.m <= 64u * (uint32_t)(W - 1) + 32u;
+  hipError_t e = hipSuccess;
+  bool strip = false;
+  if constexpr (W >= stripf::kMinW) {
+    if ((strip = mfma_strip_form(p)))
+      e = half ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, benor_mfma_kernel<W, true, 0, true, true, true>, 64 * kWavesPerBlock, p.hist_bytes)
+               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, benor_mfma_kernel<W, false, 0, true, true, true>, 64 * kWavesPerBlock, p.hist_bytes);
+  }
+  if (!strip)
+    e = half ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, benor_mfma_kernel<W, true, 0, true, true>, 64 * kWavesPerBlock, p.hist_bytes)
+             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, benor_mfma_kernel<W, false, 0, true, true>, 64 * kWavesPerBlock, p.hist_bytes);
   if (e != hipSuccess) (void)hipGetLastError();
   return e == hipSuccess ? n : 0;
 }

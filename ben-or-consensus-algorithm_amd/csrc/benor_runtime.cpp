@@ -82,7 +82,8 @@ constexpr KnobSpec kKnobs[] = {
     {"BENOR_NO_MFMA_BIG", "validation"},        // "1": popcount kernels for m > 1024
     {"BENOR_MFMA_PAIR", "validation"},          // "0": KIND 0 matrix-core kernel, one receiver tile per accumulator
     {"BENOR_MFMA_DYNAMIC", "validation"},       // "0" / "1": KIND 0 matrix-core kernel, static stride / claimed chunks
-    {"BENOR_MFMA_CHUNK", "tuning"},             // its dynamic form: groups per claim (1..64)
+    {"BENOR_MFMA_STRIP", "validation"},         // "0" / "1": its last receiver tile of <= 16 live rows in the 32-row shape / as a 16-row strip from W = 5
+    {"BENOR_MFMA_CHUNK", "tuning"},            // its dynamic form: groups per claim (1..64)
     {"BENOR_BIG_FORM", "validation"},           // "wave" / "coop": big-network matrix-core form
     {"BENOR_COOP_BW", "validation"},            // 4 / 8: waves per cooperative workgroup
     {"BENOR_SMALL_MIN_TRIALS", "validation"},   // packed matrix-core kernel from this launch size
@@ -1010,7 +1011,7 @@ static hipError_t launch_with_timeline(benor::KParams kp, int grid, hipStream_t 
   if (FILE *f = std::fopen(path, "a")) {
     std::fprintf(f, "# launch m=%u trials=%llu grid=%d waves=%d", kp.m, (unsigned long long)kp.trial_count, grid,
                  grid * benor::kWavesPerBlock);
-    if (kp.variant == 7) std::fprintf(f, " kernel=mfma chunk=%u", kp.mfma_chunk);
+    if (kp.variant == 7) std::fprintf(f, " kernel=mfma chunk=%u strip=%d", kp.mfma_chunk, benor::mfma_strip_form(kp) ? 1 : 0);
     std::fprintf(f, "\n");
     for (size_t w = 0; w < (size_t)grid * benor::kWavesPerBlock; ++w) {
       const unsigned long long *t = h.data() + w * benor::kTimelineWords;
