@@ -53,6 +53,11 @@ BO_MODE_BYZ_RULE_B = 9         # mode 8 under Ben-Or's Byzantine-tolerant rule (
                                # 2 c_v > N + F; adopt the strict majority v iff c_v > F and decide iff 2 c_v > N + F,
                                # else the coin.  Everything else, byzantine / byz_one / byz_strategy included, is mode
                                # 8's; b = 0 runs this mode's kernel (it is not mode 4's plan)
+BO_MODE_BYZ_COIN = 10          # mode 8 with a shared coin: coin_common / 2^32 is the probability that a round's coin is common
+                               # to all honest nodes (Philox stream 12, keyed by trial and round); in such a round
+                               # every node that takes a coin gets the same bit.  0 is mode 8's plan (mode 4's at b = 0)
+BO_MODE_BYZ_RULE_B_COIN = 11   # mode 9 with the same shared coin; coin_common = 0 is mode 9's plan
+COIN_ALL = 0xFFFFFFFF          # coin_common: every round's coin is common
 BYZ_RANDOM = 0                 # byz_strategy: each Byzantine message is 1 with probability byz_one / 2^32 (equivocation)
 BYZ_OPPOSE = 1                 # ... every one carries the value fewer honest senders hold (byz_one's step on a tie)
 BYZ_BALANCE = 3                # ... the Byzantine messages a receiver drew make its two tallies as equal as they can
@@ -79,6 +84,8 @@ BO_KERNEL_TALLY_PARTIAL = 12
 BO_KERNEL_TALLY_SUBSET = 13
 BO_KERNEL_TALLY_BYZ = 14
 BO_KERNEL_TALLY_BYZ_B = 15
+BO_KERNEL_TALLY_BYZ_COIN = 16
+BO_KERNEL_TALLY_BYZ_B_COIN = 17
 KERNEL_NAMES = {BO_KERNEL_NONE: "none", BO_KERNEL_BLOCKED: "blocked popcount", BO_KERNEL_W: "W popcount",
                 BO_KERNEL_RANDOM: "random delivery", BO_KERNEL_EVENT: "event level", BO_KERNEL_LANE: "lane",
                 BO_KERNEL_MFMA: "matrix core (e2m1 MFMA)", BO_KERNEL_MFMA_SMALL: "packed matrix core (e2m1 MFMA, m <= 32)",
@@ -92,7 +99,11 @@ KERNEL_NAMES = {BO_KERNEL_NONE: "none", BO_KERNEL_BLOCKED: "blocked popcount", B
                 BO_KERNEL_TALLY_BYZ: "count-level random delivery with Byzantine senders (an honest plane, wave-uniform "
                                      "steps from a staged row, per-lane Binomial lies and draws otherwise)",
                 BO_KERNEL_TALLY_BYZ_B: "count-level random delivery with Byzantine senders under Ben-Or's Byzantine-"
-                                       "tolerant rule (the same two trial loops with thresholds at (N + F) / 2 and F + 1)"}
+                                       "tolerant rule (the same two trial loops with thresholds at (N + F) / 2 and F + 1)",
+                BO_KERNEL_TALLY_BYZ_COIN: "count-level random delivery with Byzantine senders and a shared coin (the same "
+                                          "two trial loops, one wave-uniform coin block per round)",
+                BO_KERNEL_TALLY_BYZ_B_COIN: "count-level random delivery with Byzantine senders under Ben-Or's Byzantine-"
+                                            "tolerant rule with a shared coin"}
 BO_MAX_N = 4096
 BO_MAX_K = 1024
 
@@ -492,12 +503,16 @@ def reach_word(p: float) -> int:
     return REACH_ALL if p >= 1.0 else int(p * 2.0 ** 32)
 
 
+_BYZ_MODES = (BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B, BO_MODE_BYZ_COIN, BO_MODE_BYZ_RULE_B_COIN)
+
+
 def _byz_words(mode, crash_cut, crash_count, byzantine, byz_one, byz_strategy):
-    """Modes 8 and 9 read the crash_cut word as byz_one and the crash_count word as byz_strategy."""
+    """Modes 8 to 11 read the crash_cut word as byz_one and the crash_count word as byz_strategy."""
     if byzantine is None and byz_one is None and byz_strategy is None:
         return crash_cut, crash_count
-    if mode not in (BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B):
-        raise ValueError("byzantine, byz_one and byz_strategy need mode=BO_MODE_BYZ_TALLY or BO_MODE_BYZ_RULE_B")
+    if mode not in _BYZ_MODES:
+        raise ValueError("byzantine, byz_one and byz_strategy need mode=BO_MODE_BYZ_TALLY or BO_MODE_BYZ_RULE_B "
+                         "(or their shared-coin modes)")
     if crash_cut or crash_count:
         raise ValueError("byz_one / byz_strategy name the configuration words of crash_cut / crash_count: give one")
     byz_one = 0 if byz_one is None else byz_one
@@ -506,10 +521,23 @@ def _byz_words(mode, crash_cut, crash_count, byzantine, byz_one, byz_strategy):
     return byz_one, (BYZ_RANDOM if byz_strategy is None else byz_strategy)
 
 
+def _coin_word(mode, crash_window, coin_common):
+    """Modes 10 and 11 read the crash_window word as coin_common."""
+    if coin_common is None:
+        return crash_window
+    if mode not in (BO_MODE_BYZ_COIN, BO_MODE_BYZ_RULE_B_COIN):
+        raise ValueError("coin_common needs mode=BO_MODE_BYZ_COIN or BO_MODE_BYZ_RULE_B_COIN")
+    if crash_window:
+        raise ValueError("coin_common names the configuration word of crash_window: give one")
+    if not 0 <= coin_common <= 0xFFFFFFFF:
+        raise ValueError("coin_common is a probability in units of 2**-32: 0 .. 2**32 - 1")
+    return coin_common
+
+
 def _faulty_array(N, faulty, byzantine, mode):
-    """The faulty bytes: 1 for a faulty node, and in modes 8 and 9 2 for a Byzantine one (an int entry of
+    """The faulty bytes: 1 for a faulty node, and in modes 8 to 11 2 for a Byzantine one (an int entry of
     `faulty` goes through as it is there, so that the library's validation can be reached)."""
-    raw = mode in (BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B)
+    raw = mode in _BYZ_MODES
     fl = [v if raw and type(v) is int else (1 if v else 0) for v in faulty]
     if byzantine is not None:
         if len(byzantine) != len(fl):
@@ -524,8 +552,9 @@ def _faulty_array(N, faulty, byzantine, mode):
 
 def _trials_cfg(N, F, faulty=None, *, seed=0, k_max=DEFAULT_K_MAX, initial_values=None, mode=BO_MODE_LOCKSTEP,
                 crash_at=None, crash_count=0, crash_window=0, crash_cut=0, crash_reach=None, byzantine=None,
-                byz_one=None, byz_strategy=None):
+                byz_one=None, byz_strategy=None, coin_common=None):
     """bo_trials_cfg for a shape, and the ctypes arrays it points into."""
+    crash_window = _coin_word(mode, crash_window, coin_common)
     crash_cut = _cut_word(crash_cut, crash_reach)
     crash_cut, crash_count = _byz_words(mode, crash_cut, crash_count, byzantine, byz_one, byz_strategy)
     if faulty is None:                       # start.ts:7-18 placement: the first F nodes
@@ -563,13 +592,14 @@ class TrialsPlan:
                  mode: int = BO_MODE_LOCKSTEP, crash_at: Sequence | None = None, crash_count: int = 0,
                  crash_window: int = 0, crash_cut: int = 0, crash_reach: int | None = None,
                  byzantine: Sequence[bool] | None = None, byz_one: int | None = None,
-                 byz_strategy: int | None = None):
+                 byz_strategy: int | None = None, coin_common: int | None = None):
         self.N, self.F, self.k_max, self.seed = N, F, k_max, seed
         self.mode = mode
         self._cfg, self._keep = _trials_cfg(N, F, faulty, seed=seed, k_max=k_max, initial_values=initial_values,
                                             mode=mode, crash_at=crash_at, crash_count=crash_count,
                                             crash_window=crash_window, crash_cut=crash_cut, crash_reach=crash_reach,
-                                            byzantine=byzantine, byz_one=byz_one, byz_strategy=byz_strategy)
+                                            byzantine=byzantine, byz_one=byz_one, byz_strategy=byz_strategy,
+                                            coin_common=coin_common)
         h = ctypes.c_void_p()
         _check(lib().bo_plan_create(ctypes.byref(self._cfg), ctypes.byref(h)))
         self._h = h
@@ -621,8 +651,9 @@ def run_trial_states(N: int, F: int, faulty: Sequence[bool], *, seed: int = 0, t
                      mode: int = BO_MODE_LOCKSTEP, crash_at: Sequence | None = None, crash_count: int = 0,
                      crash_window: int = 0, crash_cut: int = 0, crash_reach: int | None = None,
                      byzantine: Sequence[bool] | None = None, byz_one: int | None = None,
-                     byz_strategy: int | None = None):
+                     byz_strategy: int | None = None, coin_common: int | None = None):
     """Per-node final states of one trial: (rounds, [NodeState dict] * N)."""
+    crash_window = _coin_word(mode, crash_window, coin_common)
     crash_cut = _cut_word(crash_cut, crash_reach)
     crash_cut, crash_count = _byz_words(mode, crash_cut, crash_count, byzantine, byz_one, byz_strategy)
     fl = _faulty_array(N, faulty, byzantine, mode)

@@ -15,10 +15,14 @@
                                                                           # 100 Byzantine senders, a fair coin per receiver and step
     python -m benor.cli trials --N 1024 --F 204 --mode byzb --crashed 0 --byzantine 16 --byz-strategy split
                                                                           # ... under Ben-Or's Byzantine-tolerant rule (N > 5F)
+    python -m benor.cli trials --N 1024 --F 204 --mode byzb --crashed 0 --byzantine 16 --byz-strategy split --coin-common 1
+                                                                          # ... with a shared coin in every round
     python -m benor.cli sweep --N 64,128,...,4096 --steps 32 --trials 2**30 --out sweep.csv
                                                                           # C5 phase diagram
     python -m benor.cli sweep --cells 4096:0,4096:1984 --per-cell 4793490  # two cells of it
     python -m benor.cli sweep --mode tally3 --crashed 0 --N 64,128 --steps 8  # the diagram under random delivery
+    python -m benor.cli sweep --mode byzb --N 64,256 --steps 8 --byz-steps 4 --byz-strategy split --coin-common 1
+                                                                          # the (N, F, b) diagram of the Byzantine modes
 
 `start` re-states src/start.ts:6-43: same default scenario (N = 10, nodes
 0-3 faulty, every initial value 1), same checks ("Lengths don't match",
@@ -33,6 +37,12 @@ into one [cells, H] histogram buffer, merged with a single all-reduce.  Rows: N,
 undecided, agreement violations.  `--mode tally3 --crashed f` draws the same
 diagram under count-level random delivery (BO_MODE_RANDOM_TALLY3) with the first
 f nodes of every cell crashed (f at most each cell's F; the rows' m is N - f).
+`--mode byz` and `--mode byzb` (BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B, and with
+`--coin-common p` their shared-coin modes) cross every (N, F) cell with
+b = floor(beta (F - f)) Byzantine nodes, beta = i / S for i = 0..S (`--byz-steps S`),
+placed as `trials` places them: the first f nodes crashed, the next b Byzantine.
+`--cells` then also takes N:F:b.  Their rows add b, mode, byz_strategy,
+byz_one_word and coin_common_word.
 """
 from __future__ import annotations
 
@@ -88,6 +98,30 @@ def cmd_start(a) -> int:
     return 0
 
 
+_BYZ_STRATEGIES = ("random", "oppose", "balance", "split")
+
+
+def byz_sched(a, benor) -> dict:
+    """The --byz-strategy / --byz-one / --coin-common words of `trials` and `sweep` (mode byz or byzb)."""
+    if not 0.0 <= a.byz_one <= 1.0:
+        raise SystemExit("--byz-one is a probability in [0, 1]")
+    sched = {"byz_one": benor.reach_word(a.byz_one),
+             "byz_strategy": {"random": benor.BYZ_RANDOM, "oppose": benor.BYZ_OPPOSE, "balance": benor.BYZ_BALANCE,
+                              "split": benor.BYZ_SPLIT}[a.byz_strategy]}
+    if a.coin_common is not None:                                 # a shared coin (DESIGN §4.3.10)
+        if not 0.0 <= a.coin_common <= 1.0:
+            raise SystemExit("--coin-common is a probability in [0, 1]")
+        sched["coin_common"] = benor.reach_word(a.coin_common)
+    return sched
+
+
+def byz_mode(a, benor) -> int:
+    """BO_MODE_* of --mode byz / byzb: with --coin-common, the shared-coin mode."""
+    if a.coin_common is not None:
+        return benor.BO_MODE_BYZ_COIN if a.mode == "byz" else benor.BO_MODE_BYZ_RULE_B_COIN
+    return benor.BO_MODE_BYZ_TALLY if a.mode == "byz" else benor.BO_MODE_BYZ_RULE_B
+
+
 def cmd_trials(a) -> int:
     import benor
 
@@ -126,16 +160,15 @@ def cmd_trials(a) -> int:
     elif a.crash_reach is not None:
         raise SystemExit("--crash-reach needs --mode subset")
     if a.mode in ("byz", "byzb"):                                 # Byzantine senders (byzb: §4.3.9)
-        if not 0.0 <= a.byz_one <= 1.0:
-            raise SystemExit("--byz-one is a probability in [0, 1]")
+        sched = byz_sched(a, benor)
+        mode = byz_mode(a, benor)
         if not 0 <= a.byzantine <= a.N - crashed:
             raise SystemExit("--byzantine counts live nodes: 0 .. N - crashed")
-        sched = {"byzantine": [crashed <= i < crashed + a.byzantine for i in range(a.N)],   # the live nodes after the crashed
-                 "byz_one": benor.reach_word(a.byz_one),
-                 "byz_strategy": {"random": benor.BYZ_RANDOM, "oppose": benor.BYZ_OPPOSE, "balance": benor.BYZ_BALANCE,
-                                  "split": benor.BYZ_SPLIT}[a.byz_strategy]}
+        sched["byzantine"] = [crashed <= i < crashed + a.byzantine for i in range(a.N)]   # the live nodes after the crashed
     elif a.byzantine:
         raise SystemExit("--byzantine needs --mode byz or --mode byzb")
+    elif a.coin_common is not None:
+        raise SystemExit("--coin-common needs --mode byz or --mode byzb")
     plan = benor.TrialsPlan(a.N, a.F, [i < crashed for i in range(a.N)], seed=a.seed, k_max=a.k_max, mode=mode,
                             **sched)
     t0 = time.perf_counter()
@@ -154,12 +187,64 @@ def cmd_trials(a) -> int:
     if a.mode in ("byz", "byzb"):
         row.update(byzantine=a.byzantine, byz_one=a.byz_one, byz_one_word=sched["byz_one"], byz_strategy=a.byz_strategy,
                    kernel=benor.KERNEL_NAMES[plan.kernel])
+        if a.coin_common is not None:
+            row.update(coin_common=a.coin_common, coin_common_word=sched["coin_common"])
     row["seconds"] = dt
     print(json.dumps(row))
     return 0
 
 
+def byz_grid(cells, steps: int, crashed: int = 0):
+    """Every (N, F) cell crossed with b = floor(beta (F - crashed)), beta = i / steps, i = 0..steps."""
+    if steps < 1:
+        raise SystemExit("--byz-steps is at least 1")
+    bad = [f"{N}:{F}" for (N, F) in cells if crashed > F]
+    if bad:
+        raise SystemExit(f"sweep --crashed {crashed} exceeds F in cells {','.join(bad)}")
+    return [(N, F, i * (F - crashed) // steps) for (N, F) in cells for i in range(steps + 1)]
+
+
+def parse_cells(text: str, byz: bool = False):
+    """--cells: N:F,N:F,...; with `byz` also N:F:b."""
+    cells = [tuple(_int(x) for x in c.split(":")) for c in text.split(",")]
+    if byz and any(len(c) not in (2, 3) for c in cells):
+        raise SystemExit("--cells takes N:F or N:F:b")
+    if not byz and any(len(c) == 3 for c in cells):
+        raise SystemExit("--cells N:F:b needs --mode byz or --mode byzb")
+    return cells
+
+
+def sweep_byz_cells(a):
+    """The (N, F, b) cells of `sweep --mode byz|byzb` and their argument checks (no device needed)."""
+    crashed = 0 if a.crashed is None else a.crashed
+    if crashed < 0:
+        raise SystemExit("--crashed counts nodes")
+    if a.cells:
+        cells = []
+        for c in parse_cells(a.cells, byz=True):
+            cells += [c] if len(c) == 3 else byz_grid([c], a.byz_steps, crashed)
+    else:
+        cells = byz_grid(grid_cells(_ints(a.N), a.steps), a.byz_steps, crashed)
+    bad = [f"{N}:{F}:{b}" for (N, F, b) in cells if b < 0 or crashed + b > F]
+    if bad:
+        raise SystemExit(f"sweep: crashed + b exceeds F in cells {','.join(bad)}")
+    return cells, crashed
+
+
 def cmd_sweep(a) -> int:
+    byz = a.mode in ("byz", "byzb")
+    if not byz and (a.coin_common is not None or a.byz_steps is not None or a.byz_strategy is not None or
+                    a.byz_one is not None):
+        raise SystemExit("--byz-steps / --byz-strategy / --byz-one / --coin-common need --mode byz or --mode byzb")
+    if byz:                                                       # argument errors before the device is touched
+        import benor
+
+        a.byz_steps = 4 if a.byz_steps is None else a.byz_steps
+        a.byz_strategy = "random" if a.byz_strategy is None else a.byz_strategy
+        a.byz_one = 0.5 if a.byz_one is None else a.byz_one
+        byz_cells, byz_crashed = sweep_byz_cells(a)
+        sched = byz_sched(a, benor)
+
     import torch
 
     import benor
@@ -178,16 +263,21 @@ def cmd_sweep(a) -> int:
             dist.init_process_group("nccl", device_id=torch.device("cuda", dev))
         else:
             dist.init_process_group(backend)
-    if a.cells:
+    if byz:
+        cells = byz_cells
+    elif a.cells:
         # selected cells of a full sweep, re-run at that sweep's per-cell budget (--per-cell):
         # a cell's rows depend only on (N, F, seed, per-cell trials, k_max)
-        cells = [tuple(_int(x) for x in c.split(":")) for c in a.cells.split(",")]
+        cells = parse_cells(a.cells)
     else:
         cells = grid_cells(_ints(a.N), a.steps)
     per_cell = _int(str(a.per_cell)) if a.per_cell else max(1, _int(str(a.trials)) // len(cells))
     if a.mode == "lockstep" and a.crashed is not None:
         raise SystemExit("sweep --crashed needs --mode tally3 (lockstep crashes exactly F nodes per cell)")
-    if a.mode == "tally3":
+    if byz:
+        rows, elapsed = run_sweep(cells, per_cell, a.seed, a.k_max, a.streams, rank, world, a.progress,
+                                  mode=a.mode, crashed=byz_crashed, byz=dict(sched, strategy_name=a.byz_strategy))
+    elif a.mode == "tally3":
         crashed = 0 if a.crashed is None else a.crashed
         bad = [f"{N}:{F}" for (N, F) in cells if crashed > F]
         if bad:
@@ -218,12 +308,15 @@ def rows_csv(rows: list[dict]) -> str:
 
 
 def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progress=False, mode="lockstep",
-              crashed=None):
+              crashed=None, byz=None):
     """The sweep's GPU work on the current device: (rows, seconds).  Under
     torch.distributed (world > 1) each cell's trials are split over the ranks
     and the histograms merged by one all-reduce.  mode "lockstep": F crashed
     per cell; "tally3": BO_MODE_RANDOM_TALLY3 with the first `crashed` nodes of
-    every cell crashed (a count, at most each cell's F; default 0)."""
+    every cell crashed (a count, at most each cell's F; default 0).  "byz" and
+    "byzb": cells are (N, F, b), the first `crashed` nodes crashed and the next b
+    Byzantine; `byz` holds byz_one and byz_strategy (words), strategy_name for the
+    rows, and with coin_common the shared-coin modes' word."""
     import torch
 
     import benor
@@ -250,8 +343,26 @@ def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progre
             raise ValueError(f"crashed = {crashed} exceeds a cell's F")
         plans = [benor.TrialsPlan(N, F, [i < crashed for i in range(N)], seed=seed ^ (N << 20) ^ F, k_max=k_max,
                                   mode=benor.BO_MODE_RANDOM_TALLY3) for (N, F) in cells]
+    elif mode in ("byz", "byzb"):
+        crashed = 0 if crashed is None else crashed
+        byz = dict(byz or {})
+        name = byz.pop("strategy_name", None)
+        byz.setdefault("byz_one", benor.reach_word(0.5))
+        byz.setdefault("byz_strategy", benor.BYZ_RANDOM)
+        if name is None:
+            name = {benor.BYZ_RANDOM: "random", benor.BYZ_OPPOSE: "oppose", benor.BYZ_BALANCE: "balance",
+                    benor.BYZ_SPLIT: "split"}[byz["byz_strategy"]]
+        if any(crashed + b > F for (_, F, b) in cells):
+            raise ValueError("crashed + b exceeds a cell's F")
+        coin = "coin_common" in byz
+        bo_mode = {("byz", False): benor.BO_MODE_BYZ_TALLY, ("byzb", False): benor.BO_MODE_BYZ_RULE_B,
+                   ("byz", True): benor.BO_MODE_BYZ_COIN, ("byzb", True): benor.BO_MODE_BYZ_RULE_B_COIN}[mode, coin]
+        plans = [benor.TrialsPlan(N, F, [i < crashed for i in range(N)], seed=seed ^ (N << 20) ^ F ^ (b << 44),
+                                  k_max=k_max, mode=bo_mode,
+                                  byzantine=[crashed <= i < crashed + b for i in range(N)], **byz)
+                 for (N, F, b) in cells]
     else:
-        raise ValueError(f"mode must be 'lockstep' or 'tally3': {mode!r}")
+        raise ValueError(f"mode must be 'lockstep', 'tally3', 'byz' or 'byzb': {mode!r}")
     H = plans[0].hist_len
     hists = torch.zeros((len(cells), H), dtype=torch.int64, device="cuda")
     streams = [stream] + [torch.cuda.Stream() for _ in range(max(1, streams_n) - 1)]
@@ -266,7 +377,11 @@ def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progre
         stream.wait_stream(s)
     merge_histogram(hists)
     allh = hists.cpu().numpy().astype(np.uint64)
-    rows = [summarize(allh[ci], N, F, k_max, crashed) for ci, (N, F) in enumerate(cells)]
+    rows = [summarize(allh[ci], c[0], c[1], k_max, crashed) for ci, c in enumerate(cells)]
+    if mode in ("byz", "byzb"):
+        for row, (_, _, b) in zip(rows, cells):
+            row.update(b=b, mode=mode, byz_strategy=name, byz_one_word=byz["byz_one"],
+                       coin_common_word=byz.get("coin_common", 0))
     elapsed = time.perf_counter() - t0
     for plan in plans:
         plan.check()                               # device-side capacity invariants of every cell
@@ -320,19 +435,28 @@ def main(argv=None) -> int:
                         "senders hold; --byz-one on a tie), balance (the liars in a receiver's inbox see its honest "
                         "messages and make its two tallies as equal as they can) or split (they say 1 to receivers of odd "
                         "compact index and 0 to the others); the last two do not read --byz-one")
+    t.add_argument("--coin-common", type=float, default=None,
+                   help="byz, byzb: a shared coin (BO_MODE_BYZ_COIN, BO_MODE_BYZ_RULE_B_COIN): the probability in [0, 1] "
+                        "that a round's coin is common to all honest nodes (0: the mode without it)")
     w = sub.add_parser("sweep", help="C5 decision-round phase diagram")
     w.add_argument("--N", default="64,128,256,512,1024,2048,4096")
     w.add_argument("--steps", type=int, default=32)
     w.add_argument("--trials", default="2**30")
     w.add_argument("--seed", type=int, default=0x243F6A8885A308D3)
     w.add_argument("--k-max", type=int, default=32)
-    w.add_argument("--cells", default=None, help="N:F,N:F,... instead of the N x phi grid")
+    w.add_argument("--cells", default=None, help="N:F,N:F,... instead of the N x phi grid (byz, byzb: also N:F:b)")
     w.add_argument("--per-cell", default=None, help="trials per cell (default: --trials / cells)")
     w.add_argument("--streams", type=int, default=4, help="HIP streams the cells are spread over")
-    w.add_argument("--mode", choices=["lockstep", "tally3"], default="lockstep",
-                   help="delivery model of every cell: lockstep (F crashed) or tally3 (count-level random delivery)")
+    w.add_argument("--mode", choices=["lockstep", "tally3", "byz", "byzb"], default="lockstep",
+                   help="delivery model of every cell: lockstep (F crashed), tally3 (count-level random delivery), "
+                        "byz (tally3 with Byzantine senders) or byzb (byz under Ben-Or's Byzantine-tolerant rule)")
     w.add_argument("--crashed", type=int, default=None,
-                   help="tally3: crash the first f nodes of every cell (default 0; at most each cell's F)")
+                   help="tally3, byz, byzb: crash the first f nodes of every cell (default 0; at most each cell's F)")
+    w.add_argument("--byz-steps", type=int, default=None,
+                   help="byz, byzb: every (N, F) cell is crossed with b = floor(i / S (F - f)), i = 0..S (default 4)")
+    w.add_argument("--byz-strategy", choices=list(_BYZ_STRATEGIES), default=None, help="byz, byzb: as in `trials`")
+    w.add_argument("--byz-one", type=float, default=None, help="byz, byzb: as in `trials` (default 0.5)")
+    w.add_argument("--coin-common", type=float, default=None, help="byz, byzb: as in `trials`")
     w.add_argument("--out", default=None)
     w.add_argument("--progress", action="store_true")
     a = ap.parse_args(argv)

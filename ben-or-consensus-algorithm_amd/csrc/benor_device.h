@@ -219,6 +219,16 @@ __device__ __forceinline__ uint64_t coin_ballot(uint32_t k0, uint32_t k1, uint32
   return ballot(c1) & tie;
 }
 
+// The shared coin of round r of a trial (BO_MODE_BYZ_COIN, BO_MODE_BYZ_RULE_B_COIN): words 0 and 1 of the block
+//   ctr = {trial_lo, trial_hi, 0, (r-1) | kStreamCommonCoin << 24},
+// wave-uniform.  The key words are laundered as in coin_ballot, so that the round keys of this rare
+// path are rebuilt here and not kept in SGPRs across the round loop.
+__device__ __forceinline__ uint2 common_coin(uint32_t k0, uint32_t k1, uint32_t tlo, uint32_t thi, uint32_t round) {
+  asm volatile("" : "+s"(k0), "+s"(k1));
+  const uint4 b = philox4x32_10<false>(k0, k1, make_uint4(tlo, thi, 0u, (round - 1u) | (kStreamCommonCoin << 24)));
+  return make_uint2((uint32_t)__builtin_amdgcn_readfirstlane((int)b.x), (uint32_t)__builtin_amdgcn_readfirstlane((int)b.y));
+}
+
 // Philox key words re-read from LDS at the point of use.  The volatile load
 // cannot be hoisted, so the key schedule of a rare path (coins, the per-batch
 // init pass) is rebuilt there instead of being kept -- i.e. spilled -- in SGPRs

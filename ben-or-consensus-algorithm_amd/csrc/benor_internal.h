@@ -25,6 +25,7 @@ constexpr uint32_t kStreamCut = 8u;        // BO_MODE_CRASH_PARTIAL: a crasher's
 constexpr uint32_t kStreamReach = 9u;      // BO_MODE_CRASH_SUBSET: whether crasher p's last message reaches receiver c
 constexpr uint32_t kStreamLie = 10u;       // BO_MODE_BYZ_TALLY: a receiver's Binomial count of Byzantine messages that carry 1
 constexpr uint32_t kStreamHeard = 11u;     // ... BO_BYZ_BALANCE / BO_BYZ_SPLIT: how many of a receiver's messages are Byzantine (selection sampling)
+constexpr uint32_t kStreamCommonCoin = 12u; // BO_MODE_BYZ_COIN, BO_MODE_BYZ_RULE_B_COIN: a round's shared coin, keyed by trial and round
 
 constexpr int kWavesPerBlock = 4;          // 256-thread workgroups, one trial per wave
 
@@ -73,6 +74,7 @@ struct KParams {
                             // 13: ... or a random subset of them, receiver by receiver (benor_tally_subset.hip),
                             // 14: three-valued count-level random delivery with Byzantine senders (benor_tally_byz.hip)
                             // 15: ... under Ben-Or's Byzantine-tolerant rule (the same file's loops, Protocol B's rule)
+                            // 16, 17: variants 14 and 15 with a shared coin (the same loops, the CoinShared policy)
   uint32_t base_variant;    // variant 7: the popcount kernel (1 W, 0 blocked) that serves the state
   uint32_t base_G;          //   launches and the deferred trials, and its G
   uint32_t mode;            // BO_MODE_LOCKSTEP / BO_MODE_RANDOM_DELIVERY / BO_MODE_EVENT / BO_MODE_RANDOM_TALLY /
@@ -80,7 +82,8 @@ struct KParams {
                             // mode 3's scope holds BO_MODE_RANDOM_TALLY here: it is that mode's plan; a
                             // BO_MODE_CRASH_TALLY, BO_MODE_CRASH_PARTIAL or BO_MODE_CRASH_SUBSET plan with an empty
                             // schedule is BO_MODE_RANDOM_TALLY3's, and so is a BO_MODE_BYZ_TALLY plan without a
-                            // Byzantine node; a BO_MODE_BYZ_RULE_B plan keeps its mode at b = 0)
+                            // Byzantine node; a BO_MODE_BYZ_RULE_B plan keeps its mode at b = 0; a BO_MODE_BYZ_COIN
+                            // or BO_MODE_BYZ_RULE_B_COIN plan with coin_common = 0 is its parent mode's plan)
   uint32_t q;               // quorum N - F (messages each receiver tallies per phase)
   uint32_t k_max;
   uint32_t init_mode;       // BO_INIT_RANDOM / BO_INIT_FIXED
@@ -195,6 +198,9 @@ struct KParams {
   // launches) and the chunk C, set per launch; mfma_chunk = 0: the static form
   uint32_t *mfma_claim;
   uint32_t mfma_chunk;
+  // variants 16 and 17: the probability, in units of 2^-32, that a round's coin is common to the honest
+  // nodes (bo_trials_cfg::coin_common, never 0 here; UINT32_MAX: every round)
+  uint32_t coin_common;
 };
 
 constexpr uint32_t kTimelineWords = 12;

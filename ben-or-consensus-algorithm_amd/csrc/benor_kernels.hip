@@ -646,7 +646,7 @@ void plan_geometry(KParams &p) {
   }
   if (p.mode == BO_MODE_RANDOM_TALLY || p.mode == BO_MODE_RANDOM_TALLY3 || p.mode == BO_MODE_CRASH_TALLY ||
       p.mode == BO_MODE_CRASH_PARTIAL || p.mode == BO_MODE_CRASH_SUBSET || p.mode == BO_MODE_BYZ_TALLY ||
-      p.mode == BO_MODE_BYZ_RULE_B) {
+      p.mode == BO_MODE_BYZ_RULE_B || p.mode == BO_MODE_BYZ_COIN || p.mode == BO_MODE_BYZ_RULE_B_COIN) {
     // The count-level kernels (benor_tally*.hip; layouts: benor_tally_common.h).  The row region is the
     // widest row of HG(m, ., q): no pool of the crash family exceeds m0, and the Byzantine kernels run on
     // mode 4's table.
@@ -663,11 +663,13 @@ void plan_geometry(KParams &p) {
       case BO_MODE_CRASH_PARTIAL: p.variant = 12u, bytes = crash_wave_bytes(W, p.tally_cap, p.cr_n, random, true); break;
       case BO_MODE_CRASH_SUBSET: p.variant = 13u, bytes = crash_wave_bytes(W, p.tally_cap, p.cr_n, random, true); break;
       case BO_MODE_BYZ_TALLY: p.variant = 14u, bytes = byz_wave_bytes(W, p.tally_cap); break;
-      default: p.variant = 15u, bytes = byz_wave_bytes(W, p.tally_cap); break;   // BO_MODE_BYZ_RULE_B: variant 14's layout
+      case BO_MODE_BYZ_RULE_B: p.variant = 15u, bytes = byz_wave_bytes(W, p.tally_cap); break;   // variant 14's layout
+      case BO_MODE_BYZ_COIN: p.variant = 16u, bytes = byz_wave_bytes(W, p.tally_cap); break;     // (and the shared-coin entries')
+      default: p.variant = 17u, bytes = byz_wave_bytes(W, p.tally_cap); break;                   // BO_MODE_BYZ_RULE_B_COIN
     }
     p.wave_bytes = (bytes + 15u) & ~15u;
     p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
-    if (p.variant == 14u || p.variant == 15u) {   // the Binomial thresholds ride in LDS when that costs no resident workgroup
+    if (p.variant >= 14u && p.variant <= 17u) {   // the Binomial thresholds ride in LDS when that costs no resident workgroup
       p.byz_lds = p.byz_n != 0u && !byz_heard(p) && byz_thr_in_lds(p.lds_bytes, p.byz_n) ? 1u : 0u;   // (the inbox-reading strategies and b = 0 have none)
       if (p.byz_lds) p.lds_bytes += 8u * p.byz_n;
     }
@@ -809,7 +811,7 @@ hipError_t launch_lockstep(const KParams &p, int grid, hipStream_t s) {
   if (p.variant == 11) return launch_tally_crash(p, grid, s);
   if (p.variant == 12) return launch_tally_partial(p, grid, s);
   if (p.variant == 13) return launch_tally_subset(p, grid, s);
-  if (p.variant == 14 || p.variant == 15) return launch_tally_byz(p, grid, s);
+  if (p.variant >= 14 && p.variant <= 17) return launch_tally_byz(p, grid, s);
   if (p.variant == 2 && p.rd_a) return launch_random_bern(p, grid, s);
   if (p.variant == 2) {                      // Floyd sampler
     if (p.lds_bytes > 64u * 1024u) {
@@ -899,7 +901,7 @@ uint32_t mfma_chunk(const KParams &p, int device) {
   return c;
 }
 
-// Resident workgroups per CU of the count-level kernel of variant 9..15 (0 = unknown).
+// Resident workgroups per CU of the count-level kernel of variant 9..17 (0 = unknown).
 static int count_level_blocks_per_cu(const KParams &p) {
   switch (p.variant) {
     case 9: return tally_blocks_per_cu(p);
@@ -970,7 +972,7 @@ int lockstep_grid(const KParams &p, int device) {
     const uint64_t lds_fit = lds_groups_per_cu(lds);
     if (lds_fit < per_cu) per_cu = lds_fit ? lds_fit : 1;
   }
-  if (p.variant >= 9 && p.variant <= 15) {   // the count-level kernels are register-bound (benor_tally.hip: per unroll)
+  if (p.variant >= 9 && p.variant <= 17) {   // the count-level kernels are register-bound (benor_tally.hip: per unroll)
     const uint64_t fit = (uint64_t)count_level_blocks_per_cu(p);
     if (fit >= 1u && fit < per_cu) per_cu = fit;
   }

@@ -570,10 +570,12 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   if (cfg->mode != BO_MODE_LOCKSTEP && cfg->mode != BO_MODE_RANDOM_DELIVERY && cfg->mode != BO_MODE_EVENT &&
       cfg->mode != BO_MODE_RANDOM_TALLY && cfg->mode != BO_MODE_RANDOM_TALLY3 && cfg->mode != BO_MODE_CRASH_TALLY &&
       cfg->mode != BO_MODE_CRASH_PARTIAL && cfg->mode != BO_MODE_CRASH_SUBSET && cfg->mode != BO_MODE_BYZ_TALLY &&
-      cfg->mode != BO_MODE_BYZ_RULE_B)
+      cfg->mode != BO_MODE_BYZ_RULE_B && cfg->mode != BO_MODE_BYZ_COIN && cfg->mode != BO_MODE_BYZ_RULE_B_COIN)
     return fail(BO_ERR_UNSUPPORTED, "unknown delivery mode");
-  const bool rule_b = cfg->mode == BO_MODE_BYZ_RULE_B;   // BO_MODE_BYZ_TALLY's configuration and validation, another rule
-  const bool byz_mode = cfg->mode == BO_MODE_BYZ_TALLY || rule_b;
+  // BO_MODE_BYZ_COIN and BO_MODE_BYZ_RULE_B_COIN: their parent modes' configuration and validation; the crash_window word is coin_common
+  const bool coin_mode = cfg->mode == BO_MODE_BYZ_COIN || cfg->mode == BO_MODE_BYZ_RULE_B_COIN;
+  const bool rule_b = cfg->mode == BO_MODE_BYZ_RULE_B || cfg->mode == BO_MODE_BYZ_RULE_B_COIN;   // BO_MODE_BYZ_TALLY's configuration and validation, another rule
+  const bool byz_mode = cfg->mode == BO_MODE_BYZ_TALLY || cfg->mode == BO_MODE_BYZ_COIN || rule_b;
   const bool crash_mode = cfg->mode == BO_MODE_CRASH_TALLY || cfg->mode == BO_MODE_CRASH_PARTIAL ||
                           cfg->mode == BO_MODE_CRASH_SUBSET;
   const bool random_mode = cfg->mode == BO_MODE_RANDOM_DELIVERY || cfg->mode == BO_MODE_RANDOM_TALLY ||
@@ -587,8 +589,11 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   if (byz_mode) {
     for (uint32_t i = 0; i < cfg->N; ++i)
       if (cfg->faulty[i] > 2u)
-        return fail(BO_ERR_INVALID_ARGUMENT, rule_b ? "BO_MODE_BYZ_RULE_B: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)"
-                                                    : "BO_MODE_BYZ_TALLY: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)");
+        return fail(BO_ERR_INVALID_ARGUMENT,
+                    cfg->mode == BO_MODE_BYZ_RULE_B_COIN ? "BO_MODE_BYZ_RULE_B_COIN: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)"
+                    : cfg->mode == BO_MODE_BYZ_COIN      ? "BO_MODE_BYZ_COIN: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)"
+                    : rule_b                             ? "BO_MODE_BYZ_RULE_B: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)"
+                                                         : "BO_MODE_BYZ_TALLY: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)");
     if (cfg->byz_strategy != BO_BYZ_RANDOM && cfg->byz_strategy != BO_BYZ_OPPOSE && cfg->byz_strategy != BO_BYZ_BALANCE &&
         cfg->byz_strategy != BO_BYZ_SPLIT)
       return fail(BO_ERR_INVALID_ARGUMENT,
@@ -607,8 +612,11 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   if (random_mode && f > cfg->F)
     return fail(BO_ERR_FAULTY_COUNT, "random delivery needs at most F crash-faulty nodes");
   if (f + nbyz > cfg->F)
-    return fail(BO_ERR_FAULTY_COUNT, rule_b ? "BO_MODE_BYZ_RULE_B needs at most F nodes crashed or Byzantine"
-                                            : "BO_MODE_BYZ_TALLY needs at most F nodes crashed or Byzantine");
+    return fail(BO_ERR_FAULTY_COUNT,
+                cfg->mode == BO_MODE_BYZ_RULE_B_COIN ? "BO_MODE_BYZ_RULE_B_COIN needs at most F nodes crashed or Byzantine"
+                : cfg->mode == BO_MODE_BYZ_COIN      ? "BO_MODE_BYZ_COIN needs at most F nodes crashed or Byzantine"
+                : rule_b                             ? "BO_MODE_BYZ_RULE_B needs at most F nodes crashed or Byzantine"
+                                                     : "BO_MODE_BYZ_TALLY needs at most F nodes crashed or Byzantine");
   live.clear();
   for (uint32_t i = 0; i < cfg->N; ++i)
     if (!crashed(i)) live.push_back(i);
@@ -644,9 +652,12 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   kp.init_mode = cfg->init_mode;
   kp.seed = cfg->seed;
   kp.mode = cfg->mode;
+  // A shared-coin plan whose rounds are never common is its parent mode's plan; otherwise it carries the word.
+  if (coin_mode && cfg->coin_common == 0u) kp.mode = rule_b ? BO_MODE_BYZ_RULE_B : BO_MODE_BYZ_TALLY;
+  if (coin_mode) kp.coin_common = cfg->coin_common;
   kp.q = cfg->N - cfg->F;
   kp.crash_count = byz_mode ? 0u : cfg->crash_count;   // (BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B: the word is byz_strategy)
-  kp.crash_window = cfg->crash_window;
+  kp.crash_window = coin_mode ? 0u : cfg->crash_window;   // (BO_MODE_BYZ_COIN, BO_MODE_BYZ_RULE_B_COIN: the word is coin_common)
   if (cfg->mode == BO_MODE_EVENT && !cfg->crash_at && cfg->crash_count > 0 && cfg->crash_window > 0)
     kp.ev_rstops = std::min<uint32_t>(cfg->crash_count, m);   // per-trial random /stop schedule
   kp.live = live_run && cfg->mode == BO_MODE_EVENT ? 1u : 0u;
@@ -684,8 +695,10 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   if (crash_mode && n_crash == 0) kp.mode = BO_MODE_RANDOM_TALLY3;
   // ... and so is a BO_MODE_BYZ_TALLY plan without a Byzantine node, at every byz_one and strategy
   // (BO_MODE_BYZ_RULE_B keeps its plan: the rule differs).
-  if (cfg->mode == BO_MODE_BYZ_TALLY && nbyz == 0) kp.mode = BO_MODE_RANDOM_TALLY3;
-  if (kp.mode == BO_MODE_BYZ_TALLY || kp.mode == BO_MODE_BYZ_RULE_B) {
+  // (a shared coin keeps its plan at b = 0: mode 4 has no such coin)
+  if (kp.mode == BO_MODE_BYZ_TALLY && nbyz == 0) kp.mode = BO_MODE_RANDOM_TALLY3;
+  if (kp.mode == BO_MODE_BYZ_TALLY || kp.mode == BO_MODE_BYZ_RULE_B || kp.mode == BO_MODE_BYZ_COIN ||
+      kp.mode == BO_MODE_BYZ_RULE_B_COIN) {
     kp.byz_n = nbyz;
     kp.byz_strategy = cfg->byz_strategy;
     kp.byz_one = cfg->byz_one;
@@ -866,8 +879,8 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
       kp.init_x = pl->d_init_x;
       kp.crash_at = pl->d_crash;
       kp.scratch = pl->d_scratch;
-    } else if (kp.variant == 9 || kp.variant == 10 || kp.variant == 14 || kp.variant == 15) {
-      // BO_MODE_RANDOM_TALLY, BO_MODE_RANDOM_TALLY3, BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B:
+    } else if (kp.variant == 9 || kp.variant == 10 || (kp.variant >= 14 && kp.variant <= 17)) {
+      // BO_MODE_RANDOM_TALLY, BO_MODE_RANDOM_TALLY3, BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B and their shared-coin modes:
       // the whole table HG(m, K, q), K = 0..m: at most ~3.7 * 10^6 thresholds (30 MB) at m = 4096
       std::vector<uint32_t> off(m + 2u, 0u);
       std::vector<uint64_t> thr;
@@ -880,7 +893,7 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
       const size_t off_bytes = (sizeof(uint32_t) * off.size() + 7u) & ~size_t(7);
       const size_t thr_bytes = sizeof(uint64_t) * std::max<size_t>(thr.size(), 1u);
       // ... and, with Byzantine senders, the Binomial thresholds and the honest plane behind it
-      const bool byz = kp.variant == 14 || kp.variant == 15;
+      const bool byz = kp.variant >= 14 && kp.variant <= 17;
       std::vector<uint64_t> lie;
       if (byz && !benor::byz_heard(kp)) byz_row(kp.byz_n, kp.byz_one, lie);   // (BALANCE, SPLIT, b = 0: no thresholds)
       const size_t lie_bytes = sizeof(uint64_t) * lie.size();
@@ -985,7 +998,8 @@ uint64_t bo_plan_popc_words_per_node_round(const bo_plan *pl) {
   if (pl->kp.mode != BO_MODE_RANDOM_DELIVERY && pl->kp.mode != BO_MODE_RANDOM_TALLY &&
       pl->kp.mode != BO_MODE_RANDOM_TALLY3 && pl->kp.mode != BO_MODE_CRASH_TALLY &&
       pl->kp.mode != BO_MODE_CRASH_PARTIAL && pl->kp.mode != BO_MODE_CRASH_SUBSET &&
-      pl->kp.mode != BO_MODE_BYZ_TALLY && pl->kp.mode != BO_MODE_BYZ_RULE_B)
+      pl->kp.mode != BO_MODE_BYZ_TALLY && pl->kp.mode != BO_MODE_BYZ_RULE_B && pl->kp.mode != BO_MODE_BYZ_COIN &&
+      pl->kp.mode != BO_MODE_BYZ_RULE_B_COIN)
     counts = ((pl->kp.m - pl->kp.init_q) & 1u) ? 2ull : 3ull;
   return counts * ((pl->kp.m + 31ull) / 32ull);
 }
@@ -1316,7 +1330,8 @@ void initial_states(const bo_trials_cfg *cfg, std::vector<bo_node_state> &st) {
   for (uint32_t i = 0; i < cfg->N; ++i) {
     const bool f = cfg->faulty[i] != 0;
     // (BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B: a Byzantine node is alive and has no protocol state; no kernel writes its entry)
-    const bool byz = (cfg->mode == BO_MODE_BYZ_TALLY || cfg->mode == BO_MODE_BYZ_RULE_B) && cfg->faulty[i] == 2u;
+    const bool byz = (cfg->mode == BO_MODE_BYZ_TALLY || cfg->mode == BO_MODE_BYZ_RULE_B || cfg->mode == BO_MODE_BYZ_COIN ||
+                      cfg->mode == BO_MODE_BYZ_RULE_B_COIN) && cfg->faulty[i] == 2u;
     st[i].killed = f && !byz ? 1 : 0;
     st[i].x = f ? -1 : (cfg->init_mode == BO_INIT_FIXED ? cfg->init[i] : -1);
     st[i].decided = f ? -1 : 0;

@@ -2,9 +2,12 @@
 // senders (BO_MODE_BYZ_TALLY with b > 0 Byzantine nodes), and the same
 // under Ben-Or's Byzantine-tolerant rule (BO_MODE_BYZ_RULE_B, b >= 0).
 //
-// Four entries from two trial loops, each a template over the rule applied to a
-// receiver's counts (RuleRef, RuleB below): variant 14 runs <RuleRef>, variant 15
-// <RuleB>.  Everything else in this comment holds for both.
+// Two trial loops, each a template over the rule applied to a receiver's counts
+// (RuleRef, RuleB below) and over the coin a P-phase takes (CoinLocal, CoinShared;
+// benor_tally_common.h): variant 14 runs <RuleRef, CoinLocal>, variant 15 <RuleB,
+// CoinLocal>, and variants 16 and 17 the same two rules with <CoinShared>, the shared
+// coin of BO_MODE_BYZ_COIN and BO_MODE_BYZ_RULE_B_COIN.  Everything
+// else in this comment holds for all of them.
 //
 // The model is benor_tally3.hip's with b of the m live nodes Byzantine: they send
 // at every step and lie, they never receive.  The h = m - b honest nodes run the
@@ -61,16 +64,17 @@ constexpr uint32_t kByzWgPerCu = 6u;               // resident workgroups the re
 // kNoLiar: the mode runs its kernel without a Byzantine node too (byz_n = 0: every step wave-uniform
 // with B1 = 0, no threshold read).
 struct RuleRef {                                   // the reference's crash-tolerant rule (node.ts:46-158)
-  static constexpr bool kNoLiar = false;           // (b = 0 is mode 4's plan)
+  static constexpr bool kNoLiar = false;           // (b = 0 is mode 4's plan; with a shared coin it is not, and runs here)
   static __device__ __forceinline__ void r(uint32_t c0, uint32_t c1, uint32_t, uint32_t, uint64_t hp, uint64_t &p0,
                                            uint64_t &p1) {
     p0 = ballot(c0 > c1) & hp;
     p1 = ballot(c1 > c0) & hp;
   }
+  template <class Coin>
   static __device__ __forceinline__ uint64_t p(uint32_t c0, uint32_t c1, uint32_t, uint32_t F, uint64_t hp, uint32_t k0,
                                                uint32_t k1, uint32_t tlo, uint32_t thi, uint32_t j, uint32_t r,
-                                               bool &decided) {
-    return p_rule(c0, c1, F, hp, k0, k1, tlo, thi, j, r, decided);
+                                               bool &decided, Coin &coin) {
+    return p_rule(c0, c1, F, hp, k0, k1, tlo, thi, j, r, decided, coin);
   }
 };
 struct RuleB {                                     // Ben-Or's Protocol B, t = F
@@ -79,18 +83,25 @@ struct RuleB {                                     // Ben-Or's Protocol B, t = F
                                            uint64_t &p1) {
     r_rule_b(c0, c1, N, F, hp, p0, p1);
   }
+  template <class Coin>
   static __device__ __forceinline__ uint64_t p(uint32_t c0, uint32_t c1, uint32_t N, uint32_t F, uint64_t hp, uint32_t k0,
                                                uint32_t k1, uint32_t tlo, uint32_t thi, uint32_t j, uint32_t r,
-                                               bool &decided) {
-    return p_rule_b(c0, c1, N, F, hp, k0, k1, tlo, thi, j, r, decided);
+                                               bool &decided, Coin &coin) {
+    return p_rule_b(c0, c1, N, F, hp, k0, k1, tlo, thi, j, r, decided, coin);
   }
 };
+
+template <class Coin>
+__device__ __forceinline__ Coin make_coin(const KParams &p) {
+  if constexpr (Coin::kShared) return Coin{p.coin_common, 0u};
+  else return Coin{};
+}
 
 // The oblivious strategies (BO_BYZ_RANDOM, BO_BYZ_OPPOSE), for either rule: benor_tally_byz_kernel<RuleRef> is
 // variant 14's entry, <RuleB> variant 15's.  The entries themselves are the templates: a rule-templated
 // device function called from two plain entries compiles variant 14 with six more SGPR spills.
 // (six waves per SIMD: one more than benor_tally_crash.hip, there is no schedule and no alive plane to maintain)
-template <class Rule>
+template <class Rule, class Coin>
 __global__ void __launch_bounds__(256, 6) benor_tally_byz_kernel(KParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t lane = threadIdx.x & 63u;
@@ -119,6 +130,7 @@ __global__ void __launch_bounds__(256, 6) benor_tally_byz_kernel(KParams p) {
 
   const uint32_t k0 = (uint32_t)p.seed, k1 = (uint32_t)(p.seed >> 32);
   const uint64_t waves_total = (uint64_t)gridDim.x * kWavesPerBlock;
+  Coin coin = make_coin<Coin>(p);
 
   // What the Byzantine senders say at a step with honest class sizes (H0, H1): true if every
   // receiver has a B1 of its own, else B1u for all of them.
@@ -129,7 +141,7 @@ __global__ void __launch_bounds__(256, 6) benor_tally_byz_kernel(KParams p) {
       return false;
     }
     B1u = p.byz_one == kByzCertain ? nb : 0u;
-    if constexpr (Rule::kNoLiar)
+    if constexpr (Rule::kNoLiar || Coin::kShared)
       if (nb == 0u) return false;                  // no Byzantine node: byz_thr is not there to search
     return p.byz_one != 0u && p.byz_one != kByzCertain;
   };
@@ -151,6 +163,7 @@ __global__ void __launch_bounds__(256, 6) benor_tally_byz_kernel(KParams p) {
     uint32_t R = 0;
     bool all_dec = false;
     for (uint32_t r = 1; r <= p.k_max; ++r) {
+      coin.round_start();
       // ---- R-phase ("proposal phase", node.ts:46-82)
       uint32_t H0 = 0, H1 = 0;
       for (uint32_t j = 0; j < W; ++j) {
@@ -213,7 +226,7 @@ __global__ void __launch_bounds__(256, 6) benor_tally_byz_kernel(KParams p) {
                      c1);
         }
         bool decided;
-        const uint64_t x1 = Rule::p(c0, c1, N, F, hp, k0, k1, tlo, thi, j, r, decided);
+        const uint64_t x1 = Rule::p(c0, c1, N, F, hp, k0, k1, tlo, thi, j, r, decided, coin);
         if (mine && decided) dec |= 1ull << j;     // sticky
         undecided = undecided || (mine && !((dec >> j) & 1ull));
         if (lane == 0) X1[j] = (X1[j] & ~hp) | x1;                       // a Byzantine node's bit is never written
@@ -275,7 +288,7 @@ __device__ __forceinline__ uint32_t heard_lies(uint32_t strategy, uint32_t c, ui
 
 // benor_tally_byz_kernel's trial loop with every step of the first kind: no Binomial
 // thresholds (byz_thr and byz_lds are not read), no per-lane row.  byz_n > 0 (launch_tally_byz).
-template <class Rule>
+template <class Rule, class Coin>
 __global__ void __launch_bounds__(256, 6) benor_tally_heard_kernel(KParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t lane = threadIdx.x & 63u;
@@ -299,6 +312,7 @@ __global__ void __launch_bounds__(256, 6) benor_tally_heard_kernel(KParams p) {
 
   const uint32_t k0 = (uint32_t)p.seed, k1 = (uint32_t)(p.seed >> 32);
   const uint64_t waves_total = (uint64_t)gridDim.x * kWavesPerBlock;
+  Coin coin = make_coin<Coin>(p);
 
   for (uint64_t t = (uint64_t)blockIdx.x * kWavesPerBlock + wv; t < p.trial_count; t += waves_total) {
     const uint64_t trial = p.trial_begin + t;
@@ -311,6 +325,7 @@ __global__ void __launch_bounds__(256, 6) benor_tally_heard_kernel(KParams p) {
     uint32_t R = 0;
     bool all_dec = false;
     for (uint32_t r = 1; r <= p.k_max; ++r) {
+      coin.round_start();
       // ---- R-phase ("proposal phase", node.ts:46-82)
       uint32_t H0 = 0, H1 = 0;
       for (uint32_t j = 0; j < W; ++j) {
@@ -363,7 +378,7 @@ __global__ void __launch_bounds__(256, 6) benor_tally_heard_kernel(KParams p) {
         const uint32_t l1 = heard_lies(strategy, c, h0, h1, nB);
         const uint32_t c0 = h0 + nB - l1, c1 = h1 + l1;
         bool decided;
-        const uint64_t x1 = Rule::p(c0, c1, N, F, hp, k0, k1, tlo, thi, j, r, decided);
+        const uint64_t x1 = Rule::p(c0, c1, N, F, hp, k0, k1, tlo, thi, j, r, decided, coin);
         if (mine && decided) dec |= 1ull << j;     // sticky
         undecided = undecided || (mine && !((dec >> j) & 1ull));
         if (lane == 0) X1[j] = (X1[j] & ~hp) | x1;                       // a Byzantine node's bit is never written
@@ -400,24 +415,34 @@ bool byz_thr_in_lds(uint32_t lds_bytes, uint32_t b) {
   return lds_groups_per_cu(lds_bytes + 8u * b) >= without;
 }
 
-// Workgroups of the kernel that one CU holds at once (registers and LDS; 0 = unknown).
-int byz_blocks_per_cu(const KParams &p) {
-  if (p.variant == 15u) return blocks_per_cu(byz_heard(p) ? benor_tally_heard_kernel<RuleB> : benor_tally_byz_kernel<RuleB>, p);
-  return blocks_per_cu(byz_heard(p) ? benor_tally_heard_kernel<RuleRef> : benor_tally_byz_kernel<RuleRef>, p);
+// The entry of a plan: its rule and coin by the variant, its loop by the strategy.
+using ByzKernel = void (*)(KParams);
+static ByzKernel byz_entry(const KParams &p) {
+  const bool heard = byz_heard(p);
+  switch (p.variant) {
+    case 14u: return heard ? benor_tally_heard_kernel<RuleRef, CoinLocal> : benor_tally_byz_kernel<RuleRef, CoinLocal>;
+    case 15u: return heard ? benor_tally_heard_kernel<RuleB, CoinLocal> : benor_tally_byz_kernel<RuleB, CoinLocal>;
+    case 16u: return heard ? benor_tally_heard_kernel<RuleRef, CoinShared> : benor_tally_byz_kernel<RuleRef, CoinShared>;
+    default: return heard ? benor_tally_heard_kernel<RuleB, CoinShared> : benor_tally_byz_kernel<RuleB, CoinShared>;
+  }
 }
 
-// Variants 14 and 15.  Variant 15 alone runs without a Byzantine node (byz_n = 0: no thresholds, none in LDS).
+// Workgroups of the kernel that one CU holds at once (registers and LDS; 0 = unknown).
+int byz_blocks_per_cu(const KParams &p) { return blocks_per_cu(byz_entry(p), p); }
+
+// Variants 14 to 17.  Variant 14 alone needs a Byzantine node; the others run without one too (byz_n = 0: no
+// thresholds, none in LDS).  Variants 16 and 17 need coin_common != 0 (0 is the parent mode's plan).
 hipError_t launch_tally_byz(const KParams &plan, int grid, hipStream_t s) {
   const KParams p = state_launch(plan, byz_state_bytes(plan.W));
-  const bool rule_b = p.variant == 15u;
+  const bool shared = p.variant == 16u || p.variant == 17u;
   const bool heard = byz_heard(p);                 // BO_BYZ_BALANCE, BO_BYZ_SPLIT: no thresholds, none in LDS
   const bool no_thr = heard || p.byz_n == 0u;
   if (!p.tally_off || !p.tally_thr || !p.byz_plane || (no_thr ? p.byz_lds != 0u : !p.byz_thr) || p.W > kMaxW ||
-      (p.byz_n == 0u && !rule_b) || p.byz_n > p.m - p.q || plan.wave_bytes < byz_wave_bytes(p.W, p.tally_cap) ||
+      (p.byz_n == 0u && p.variant == 14u) || (shared && p.coin_common == 0u) || p.byz_n > p.m - p.q ||
+      plan.wave_bytes < byz_wave_bytes(p.W, p.tally_cap) ||
       plan.lds_bytes < p.hist_bytes + kWavesPerBlock * plan.wave_bytes + (p.byz_lds ? 8u * p.byz_n : 0u))
     return hipErrorInvalidValue;
-  if (rule_b) return launch_lds(heard ? benor_tally_heard_kernel<RuleB> : benor_tally_byz_kernel<RuleB>, p, grid, s);
-  return launch_lds(heard ? benor_tally_heard_kernel<RuleRef> : benor_tally_byz_kernel<RuleRef>, p, grid, s);
+  return launch_lds(byz_entry(p), p, grid, s);
 }
 
 }  // namespace benor

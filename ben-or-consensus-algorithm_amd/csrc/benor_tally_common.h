@@ -360,14 +360,44 @@ __device__ __forceinline__ void trial_end(uint32_t *lhist, const KParams &p, uin
   }
 }
 
+// ---- the coin a P-phase rule takes, a compile-time policy of the trial loop
+// operator() returns the x = 1 bits of the lanes of `take` (wave-uniform, not empty) in group j.
+struct CoinLocal {                                 // every node its own: coin_ballot, the coin stream of every batch mode
+  static constexpr bool kShared = false;
+  __device__ __forceinline__ void round_start() {}
+  __device__ __forceinline__ uint64_t operator()(uint32_t k0, uint32_t k1, uint32_t tlo, uint32_t thi, uint32_t j,
+                                                 uint32_t r, uint64_t take) const {
+    return coin_ballot(k0, k1, tlo, thi, j, r, take);
+  }
+};
+// A shared coin (BO_MODE_BYZ_COIN, BO_MODE_BYZ_RULE_B_COIN; `common` = KParams::coin_common != 0).  One wave is
+// one trial, so the round's stream-12 block is wave-uniform: it is drawn when a group of the round first
+// takes a coin and kept as two bits.  A common round runs no per-lane coin block at all.
+struct CoinShared {
+  static constexpr bool kShared = true;
+  uint32_t common;
+  uint32_t st;                                     // this round: 0 not drawn yet, 1 each node its own coin, 2 | v common with value v
+  __device__ __forceinline__ void round_start() { st = 0u; }
+  __device__ __forceinline__ uint64_t operator()(uint32_t k0, uint32_t k1, uint32_t tlo, uint32_t thi, uint32_t j,
+                                                 uint32_t r, uint64_t take) {
+    if (st == 0u) {
+      const uint2 w = common_coin(k0, k1, tlo, thi, r);
+      st = (common == 0xFFFFFFFFu || w.x < common) ? 2u | (w.y & 1u) : 1u;
+    }
+    if (st & 2u) return (st & 1u) ? take : 0ull;
+    return coin_ballot(k0, k1, tlo, thi, j, r, take);
+  }
+};
+
 // ---- the P-phase rule ("voting phase", node.ts:83-158) for receiver group j
 // c0 > F -> 0 decided, else c1 > F -> 1 decided, else the strict majority, else the
 // node's coin (coin_ballot, compact index and round: the coin stream of every batch
 // mode).  `mask` holds the group's lanes that vote; returns their new x = 1 bits,
 // and in `decided` whether this lane's counts decide (sticky in the caller, which
-// also applies its own mask to it).
+// also applies its own mask to it).  `coin` is the trial loop's coin policy; without one, CoinLocal.
+template <class Coin>
 __device__ __forceinline__ uint64_t p_rule(uint32_t c0, uint32_t c1, uint32_t F, uint64_t mask, uint32_t k0, uint32_t k1,
-                                           uint32_t tlo, uint32_t thi, uint32_t j, uint32_t r, bool &decided) {
+                                           uint32_t tlo, uint32_t thi, uint32_t j, uint32_t r, bool &decided, Coin &coin) {
   const bool d0l = c0 > F, d1l = !d0l && c1 > F;
   const uint64_t d0 = ballot(d0l) & mask;
   const uint64_t d1 = ballot(d1l) & mask;
@@ -376,10 +406,15 @@ __device__ __forceinline__ uint64_t p_rule(uint32_t c0, uint32_t c1, uint32_t F,
   if (rest) {
     x1 |= ballot(c1 > c0) & rest;
     const uint64_t tie = ballot(c1 == c0) & rest;  // an empty tally included
-    if (tie) x1 |= coin_ballot(k0, k1, tlo, thi, j, r, tie);
+    if (tie) x1 |= coin(k0, k1, tlo, thi, j, r, tie);
   }
   decided = d0l || d1l;
   return x1;
+}
+__device__ __forceinline__ uint64_t p_rule(uint32_t c0, uint32_t c1, uint32_t F, uint64_t mask, uint32_t k0, uint32_t k1,
+                                           uint32_t tlo, uint32_t thi, uint32_t j, uint32_t r, bool &decided) {
+  CoinLocal coin;
+  return p_rule(c0, c1, F, mask, k0, k1, tlo, thi, j, r, decided, coin);
 }
 
 // ---- Ben-Or's Byzantine-tolerant rule (Protocol B, N > 5t with t = F; BO_MODE_BYZ_RULE_B)
@@ -394,15 +429,16 @@ __device__ __forceinline__ void r_rule_b(uint32_t c0, uint32_t c1, uint32_t N, u
 // The P-phase, p_rule's interface: v = the value with the strictly larger count (none on
 // c0 == c1, an empty tally included); with c_v > F the node adopts v, and decides iff
 // 2 c_v > N + F; otherwise x is the node's coin (coin_ballot, the coin stream of every batch
-// mode).  Ballots and integer compares only; counts are at most N <= 4096.
+// mode; or the trial loop's coin policy).  Ballots and integer compares only; counts are at most N <= 4096.
+template <class Coin>
 __device__ __forceinline__ uint64_t p_rule_b(uint32_t c0, uint32_t c1, uint32_t N, uint32_t F, uint64_t mask, uint32_t k0,
                                              uint32_t k1, uint32_t tlo, uint32_t thi, uint32_t j, uint32_t r,
-                                             bool &decided) {
+                                             bool &decided, Coin &coin) {
   const uint32_t cv = c1 > c0 ? c1 : c0;
   const bool adopt = c0 != c1 && cv > F;
-  const uint64_t coin = mask & ~ballot(adopt);
+  const uint64_t take = mask & ~ballot(adopt);
   uint64_t x1 = ballot(adopt && c1 > c0) & mask;
-  if (coin) x1 |= coin_ballot(k0, k1, tlo, thi, j, r, coin);
+  if (take) x1 |= coin(k0, k1, tlo, thi, j, r, take);
   decided = adopt && 2u * cv > N + F;
   return x1;
 }

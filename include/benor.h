@@ -219,7 +219,7 @@ enum {
  * b = 0 is RANDOM_TALLY3's plan at every byz_one and strategy: its kernel choice
  * and its results bit for bit.  Not modelled: Byzantine nodes together with
  * crashes during the run, lies that say "?", explicit lie masks.  Batch API only
- * (no network API, no `sweep`). */
+ * (no network API; `sweep --mode byz` draws its (N, F, b) diagram). */
 /* BYZ_RULE_B is BYZ_TALLY with the other rule of the same paper:
  * Ben-Or's Byzantine-tolerant Protocol B, stated for N > 5t, with F as its t.
  * Who is Byzantine (faulty[i] == 2) and f + b <= F, compact indices, senders and
@@ -241,8 +241,31 @@ enum {
  * is NOT RANDOM_TALLY3's plan, the rule differs: it runs this mode's kernel with
  * every step wave-uniform and no stream-10 or stream-11 word, the same results
  * at every byz_one and strategy (f = F then gives m == q).  Not modelled: what
- * BYZ_TALLY does not model, other rules (Protocol A, Bracha), a common coin.
- * Batch API only (no network API, no `sweep`). */
+ * BYZ_TALLY does not model, other rules (Protocol A, Bracha).
+ * Batch API only (no network API; `sweep --mode byzb` draws its (N, F, b) diagram). */
+/* BYZ_COIN is BYZ_TALLY word for word, and BYZ_RULE_B_COIN is BYZ_RULE_B word for
+ * word, with a shared coin (Rabin's, or its weak form): the word
+ * that other modes call crash_window is read as coin_common, the probability, in
+ * units of 2^-32, that a round's coin is common to all honest nodes (every value
+ * valid, 0: never, UINT32_MAX: certainly).  For trial t and round r the common-coin
+ * block is Philox4x32-10 with ctr = {trial_lo, trial_hi, 0, (r-1) | 12 << 24}, key =
+ * seed (stream 12).  Round r is common iff coin_common == UINT32_MAX or out[0] <
+ * coin_common; its value is out[1] & 1.  In a common round every honest node whose
+ * P-phase rule takes a coin (the reference rule's tie, Protocol B's "otherwise")
+ * gets x = that one bit; in any other round each such node takes its own coin from
+ * RANDOM_TALLY3's coin stream, as in the parent mode.  The word depends on the
+ * trial and the round only: not on the launch split and not on which nodes take a
+ * coin.  coin_common == 0 draws no stream-12 word and is the parent mode's plan
+ * (BYZ_TALLY's, RANDOM_TALLY3's at b = 0, BYZ_RULE_B's): its kernel choice and its
+ * results bit for bit.  coin_common != 0 with b = 0 is valid in both modes and runs
+ * the shared-coin kernels; BYZ_COIN at b = 0 is then the reference's crash-tolerant
+ * rule under random delivery with a shared coin.  Who is Byzantine, f + b <= F, the
+ * four strategies and streams 5, 6, 10 and 11, halting over the honest nodes, the
+ * histogram layout, the per-node states and every validation error are the parent
+ * mode's.  Not modelled: an adversary that chooses the coin values in non-common
+ * rounds, or that sees the coin before it lies; a coin shared by a subset of the
+ * nodes; a shared coin in the lockstep, event and crash modes.  Batch API only
+ * (no network API; `sweep --mode byz|byzb --coin-common p`). */
 enum {
   BO_MODE_LOCKSTEP = 0,
   BO_MODE_RANDOM_DELIVERY = 1,
@@ -253,10 +276,12 @@ enum {
   BO_MODE_CRASH_PARTIAL = 6,
   BO_MODE_CRASH_SUBSET = 7,
   BO_MODE_BYZ_TALLY = 8,
-  BO_MODE_BYZ_RULE_B = 9
+  BO_MODE_BYZ_RULE_B = 9,
+  BO_MODE_BYZ_COIN = 10,
+  BO_MODE_BYZ_RULE_B_COIN = 11
 };
 
-/* BO_MODE_BYZ_TALLY and BO_MODE_BYZ_RULE_B, byz_strategy. */
+/* BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B and their shared-coin modes, byz_strategy. */
 /* (2 is not a strategy: it stays BO_ERR_INVALID_ARGUMENT, as it was before BALANCE and SPLIT existed) */
 enum { BO_BYZ_RANDOM = 0, BO_BYZ_OPPOSE = 1, BO_BYZ_BALANCE = 3, BO_BYZ_SPLIT = 4 };
 
@@ -403,12 +428,12 @@ typedef struct bo_trials_cfg {
         uint32_t crash_cut;   /* CRASH_PARTIAL: every crasher's cut, 0..m0, or BO_CUT_RANDOM */
         uint32_t crash_reach; /* CRASH_SUBSET: the probability, in units of 2^-32, that a crasher's last message
                                  reaches a receiver (0: never, UINT32_MAX: certainly); every value is valid */
-        uint32_t byz_one;     /* BYZ_TALLY, BYZ_RULE_B: the probability, in units of 2^-32, that a Byzantine message carries 1
+        uint32_t byz_one;     /* BYZ_TALLY, BYZ_RULE_B, BYZ_COIN, BYZ_RULE_B_COIN: the probability, in units of 2^-32, that a Byzantine message carries 1
                                  (0: never, UINT32_MAX: certainly); every value is valid */
     };                        /* the other modes ignore it */
     uint64_t seed;            /* Philox4x32-10 key */
     const uint8_t *faulty;    /* host [N]; non-zero = faulty: exactly F set (LOCKSTEP, EVENT), at most F (RANDOM_DELIVERY, RANDOM_TALLY, RANDOM_TALLY3, CRASH_TALLY, CRASH_PARTIAL, CRASH_SUBSET);
-                                 BYZ_TALLY and BYZ_RULE_B alone read the value: 1 crashed from the start, 2 Byzantine, together at most F */
+                                 BYZ_TALLY, BYZ_RULE_B, BYZ_COIN and BYZ_RULE_B_COIN alone read the value: 1 crashed from the start, 2 Byzantine, together at most F */
     const int8_t *init;       /* host [N]; used when init_mode == BO_INIT_FIXED */
     /* EVENT mode: GET /stop schedule.  crash_at[i] = number of deliveries
      * after which node i is stopped (UINT32_MAX = never), or, when crash_at is
@@ -418,14 +443,19 @@ typedef struct bo_trials_cfg {
      * at which node i crashes (UINT32_MAX = never; entries of faulty nodes are
      * ignored), or, when crash_at is NULL, crash_count distinct initially-live
      * nodes at uniform steps in [0, crash_window), drawn per trial.
-     * The other modes ignore the three fields, except that BYZ_TALLY and BYZ_RULE_B
-     * read the crash_count word as byz_strategy. */
+     * The other modes ignore the three fields, except that BYZ_TALLY, BYZ_RULE_B, BYZ_COIN and
+     * BYZ_RULE_B_COIN read the crash_count word as byz_strategy, and the last two the crash_window
+     * word as coin_common. */
     const uint32_t *crash_at; /* host [N] or NULL */
     union {                   /* one word, the layout of the struct is that of ABI version 8 */
         uint32_t crash_count;
-        uint32_t byz_strategy; /* BYZ_TALLY, BYZ_RULE_B: a BO_BYZ_* strategy */
+        uint32_t byz_strategy; /* BYZ_TALLY, BYZ_RULE_B, BYZ_COIN, BYZ_RULE_B_COIN: a BO_BYZ_* strategy */
     };
-    uint32_t crash_window;
+    union {                   /* one word, the layout of the struct is that of ABI version 8 */
+        uint32_t crash_window;
+        uint32_t coin_common; /* BYZ_COIN, BYZ_RULE_B_COIN: the probability, in units of 2^-32, that a round's coin is
+                                 common to all honest nodes (0: never, UINT32_MAX: certainly); every value is valid */
+    };
 } bo_trials_cfg;
 
 /* Histogram length for a round cap: (k_max + 1) * 3 + 1 uint64 bins.
@@ -467,7 +497,7 @@ int bo_plan_check(bo_plan *plan);
  * (c0 = M - c1); the P-phase counts c1 when M is odd (no tie, so no "?"
  * proposal: c0 = m - c1) and c0, c1 otherwise -- 2 or 3 x ceil(m/32).
  * RANDOM_DELIVERY: both values in both phases, 4 x ceil(m/32).  RANDOM_TALLY,
- * RANDOM_TALLY3, CRASH_TALLY, CRASH_PARTIAL, CRASH_SUBSET, BYZ_TALLY and BYZ_RULE_B answer RANDOM_DELIVERY's
+ * RANDOM_TALLY3, CRASH_TALLY, CRASH_PARTIAL, CRASH_SUBSET, BYZ_TALLY, BYZ_RULE_B and their shared-coin modes answer RANDOM_DELIVERY's
  * unit, the work they stand in for (the crash modes with m = the initially-live count,
  * BYZ_TALLY and BYZ_RULE_B with m = the live nodes, honest and Byzantine, as bo_plan_live_nodes reports it). */
 uint64_t bo_plan_popc_words_per_node_round(const bo_plan *plan);
@@ -515,9 +545,13 @@ enum {
                               Binomial count of lying 1s (Philox stream 10) and searches the row of its own
                               class sizes in global memory; one table, (m, q) (b = 0 runs RANDOM_TALLY3's
                               kernel choice) */
-  BO_KERNEL_TALLY_BYZ_B = 15 /* BO_MODE_BYZ_RULE_B with an honest node, b = 0 included: TALLY_BYZ's two trial loops
+  BO_KERNEL_TALLY_BYZ_B = 15, /* BO_MODE_BYZ_RULE_B with an honest node, b = 0 included: TALLY_BYZ's two trial loops
                               instantiated with Protocol B's rule (thresholds at (N + F) / 2 and F + 1); the same
                               LDS layout, launch bounds, grid and state launch */
+  BO_KERNEL_TALLY_BYZ_COIN = 16, /* BO_MODE_BYZ_COIN with coin_common != 0, b = 0 included: TALLY_BYZ's two trial loops
+                              instantiated with the shared coin (one stream-12 block per round, drawn when an
+                              honest node first takes a coin; no per-node coin in a common round) */
+  BO_KERNEL_TALLY_BYZ_B_COIN = 17 /* BO_MODE_BYZ_RULE_B_COIN with coin_common != 0: TALLY_BYZ_B's with the shared coin */
 };
 
 /* The kernel family bo_plan_launch runs for this plan.  (The per-node-state

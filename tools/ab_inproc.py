@@ -60,6 +60,14 @@ next to mode:byz on the same liars it times the two rules, whose rounds per tria
     python tools/ab_inproc.py --rounds 7 --reps 5 --shapes "1024,204,100000,0" --variants \
         "m8=mode:byz,byzantine:16,byz_strategy:split;m9=mode:byzb,byzantine:16,byz_strategy:split"
 
+`coin_common` (`all`, a probability with a decimal point or the 32-bit word) on mode:byz or mode:byzb
+selects the shared-coin modes (BO_MODE_BYZ_COIN, BO_MODE_BYZ_RULE_B_COIN).  At `coin_common:1` (one round
+in 2^32 is common) the outcomes are the parent mode's through the shared-coin entry, so that pair times
+the coin policy alone; at `coin_common:all` the rounds per trial differ by design:
+
+    python tools/ab_inproc.py --rounds 5 --reps 3 --shapes "1024,204,100000,0" --variants \
+        "m9=mode:byzb,byzantine:16,byz_strategy:split;one=mode:byzb,byzantine:16,byz_strategy:split,coin_common:1;all=mode:byzb,byzantine:16,byz_strategy:split,coin_common:all"
+
 Every line also reports
 the live node-rounds per second its launches represent (bench.py node_rounds)
 and the rounds a trial ran on average (k_max for an undecided one),
@@ -102,7 +110,7 @@ def main():
         shapes.append((v[0], v[1], v[2], v[3] if len(v) > 3 else v[1]))
     modes = {name: env.pop("mode", None) for name, env in variants}   # `mode` is no environment variable
     scheds = {name: {k: env.pop(k) for k in ("crash_count", "crash_window", "crash_at", "crash_cut", "crash_reach",
-                                             "byzantine", "byz_one", "byz_strategy")
+                                             "byzantine", "byz_one", "byz_strategy", "coin_common")
                      if k in env}
               for name, env in variants}                              # ... nor is the crash schedule
     knobs = sorted({k for _, env in variants for k in env})
@@ -119,7 +127,7 @@ def main():
     bad = sorted({v for v in modes.values() if v is not None and v not in mode_ids})
     if bad:
         ap.error(f"mode must be one of {sorted(mode_ids)}: {bad}")
-    byz_keys = ("byzantine", "byz_one", "byz_strategy")
+    byz_keys = ("byzantine", "byz_one", "byz_strategy", "coin_common")
     if any(any(k in sc for k in byz_keys) != (modes[name] in ("byz", "byzb")) for name, sc in scheds.items()):
         ap.error("byzantine / byz_one / byz_strategy go with mode:byz or mode:byzb, and they with them")
     if any(any(k not in byz_keys for k in sc) and modes[name] not in ("crash", "partial", "subset")
@@ -134,7 +142,10 @@ def main():
         sc, kw = dict(scheds[name]), {}
         if modes[name] in ("byz", "byzb"):
             b, one = int(sc.get("byzantine", 0)), sc.get("byz_one", "0.5")
-            return {"byzantine": [f <= i < f + b for i in range(N)],
+            coin = sc.get("coin_common")
+            if coin is not None:
+                kw["coin_common"] = 0xFFFFFFFF if coin == "all" else benor.reach_word(float(coin)) if "." in coin else int(coin)
+            return {**kw, "byzantine": [f <= i < f + b for i in range(N)],
                     "byz_one": 0xFFFFFFFF if one == "all" else benor.reach_word(float(one)) if "." in one else int(one),
                     "byz_strategy": {"random": benor.BYZ_RANDOM, "oppose": benor.BYZ_OPPOSE, "balance": benor.BYZ_BALANCE,
                                      "split": benor.BYZ_SPLIT}[sc.get("byz_strategy", "random")]}
@@ -174,6 +185,8 @@ def main():
         plans = {}                                    # one plan per delivery mode the variants name
         for name, _ in variants:
             mode = mode_ids[modes[name]] if modes[name] else dflt
+            if "coin_common" in scheds[name]:
+                mode = benor.BO_MODE_BYZ_COIN if modes[name] == "byz" else benor.BO_MODE_BYZ_RULE_B_COIN
             key = (mode, tuple(sorted(scheds[name].items())))
             if key not in plans:
                 plans[key] = benor.TrialsPlan(N, F, [i < f for i in range(N)], seed=0x5EED + N, k_max=32, mode=mode,
