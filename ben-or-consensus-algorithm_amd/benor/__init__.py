@@ -57,6 +57,12 @@ BO_MODE_BYZ_COIN = 10          # mode 8 with a shared coin: coin_common / 2^32 i
                                # to all honest nodes (Philox stream 12, keyed by trial and round); in such a round
                                # every node that takes a coin gets the same bit.  0 is mode 8's plan (mode 4's at b = 0)
 BO_MODE_BYZ_RULE_B_COIN = 11   # mode 9 with the same shared coin; coin_common = 0 is mode 9's plan
+BO_MODE_SCHED_TALLY = 12       # mode 10 under an adversarial scheduler: the adversary, not a draw, picks the q messages each
+                               # honest receiver hears at every step and what the Byzantine senders among them say;
+                               # byz_strategy BYZ_SPLIT (receivers of odd index driven to 1, even ones to 0) or
+                               # BYZ_BALANCE ("?" first, then the tallies as level as the senders allow); byz_one is not
+                               # read; b = 0 and coin_common = 0 keep the mode (no other mode's plan); no table
+BO_MODE_SCHED_RULE_B = 13      # mode 11 under the same scheduler (Protocol B's rule)
 COIN_ALL = 0xFFFFFFFF          # coin_common: every round's coin is common
 BYZ_RANDOM = 0                 # byz_strategy: each Byzantine message is 1 with probability byz_one / 2^32 (equivocation)
 BYZ_OPPOSE = 1                 # ... every one carries the value fewer honest senders hold (byz_one's step on a tie)
@@ -86,6 +92,10 @@ BO_KERNEL_TALLY_BYZ = 14
 BO_KERNEL_TALLY_BYZ_B = 15
 BO_KERNEL_TALLY_BYZ_COIN = 16
 BO_KERNEL_TALLY_BYZ_B_COIN = 17
+BO_KERNEL_TALLY_SCHED = 18
+BO_KERNEL_TALLY_SCHED_B = 19
+BO_KERNEL_TALLY_SCHED_COIN = 20
+BO_KERNEL_TALLY_SCHED_B_COIN = 21
 KERNEL_NAMES = {BO_KERNEL_NONE: "none", BO_KERNEL_BLOCKED: "blocked popcount", BO_KERNEL_W: "W popcount",
                 BO_KERNEL_RANDOM: "random delivery", BO_KERNEL_EVENT: "event level", BO_KERNEL_LANE: "lane",
                 BO_KERNEL_MFMA: "matrix core (e2m1 MFMA)", BO_KERNEL_MFMA_SMALL: "packed matrix core (e2m1 MFMA, m <= 32)",
@@ -103,7 +113,13 @@ KERNEL_NAMES = {BO_KERNEL_NONE: "none", BO_KERNEL_BLOCKED: "blocked popcount", B
                 BO_KERNEL_TALLY_BYZ_COIN: "count-level random delivery with Byzantine senders and a shared coin (the same "
                                           "two trial loops, one wave-uniform coin block per round)",
                 BO_KERNEL_TALLY_BYZ_B_COIN: "count-level random delivery with Byzantine senders under Ben-Or's Byzantine-"
-                                            "tolerant rule with a shared coin"}
+                                            "tolerant rule with a shared coin",
+                BO_KERNEL_TALLY_SCHED: "count-level delivery under an adversarial scheduler (closed-form counts per "
+                                       "receiver parity: no table, no search, no walk)",
+                BO_KERNEL_TALLY_SCHED_B: "count-level delivery under an adversarial scheduler, Ben-Or's Byzantine-tolerant rule",
+                BO_KERNEL_TALLY_SCHED_COIN: "count-level delivery under an adversarial scheduler with a shared coin",
+                BO_KERNEL_TALLY_SCHED_B_COIN: "count-level delivery under an adversarial scheduler, Ben-Or's Byzantine-"
+                                              "tolerant rule with a shared coin"}
 BO_MAX_N = 4096
 BO_MAX_K = 1024
 
@@ -503,11 +519,12 @@ def reach_word(p: float) -> int:
     return REACH_ALL if p >= 1.0 else int(p * 2.0 ** 32)
 
 
-_BYZ_MODES = (BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B, BO_MODE_BYZ_COIN, BO_MODE_BYZ_RULE_B_COIN)
+_SCHED_MODES = (BO_MODE_SCHED_TALLY, BO_MODE_SCHED_RULE_B)
+_BYZ_MODES = (BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B, BO_MODE_BYZ_COIN, BO_MODE_BYZ_RULE_B_COIN) + _SCHED_MODES
 
 
 def _byz_words(mode, crash_cut, crash_count, byzantine, byz_one, byz_strategy):
-    """Modes 8 to 11 read the crash_cut word as byz_one and the crash_count word as byz_strategy."""
+    """Modes 8 to 13 read the crash_cut word as byz_one and the crash_count word as byz_strategy."""
     if byzantine is None and byz_one is None and byz_strategy is None:
         return crash_cut, crash_count
     if mode not in _BYZ_MODES:
@@ -522,10 +539,10 @@ def _byz_words(mode, crash_cut, crash_count, byzantine, byz_one, byz_strategy):
 
 
 def _coin_word(mode, crash_window, coin_common):
-    """Modes 10 and 11 read the crash_window word as coin_common."""
+    """Modes 10 to 13 read the crash_window word as coin_common."""
     if coin_common is None:
         return crash_window
-    if mode not in (BO_MODE_BYZ_COIN, BO_MODE_BYZ_RULE_B_COIN):
+    if mode not in (BO_MODE_BYZ_COIN, BO_MODE_BYZ_RULE_B_COIN) + _SCHED_MODES:
         raise ValueError("coin_common needs mode=BO_MODE_BYZ_COIN or BO_MODE_BYZ_RULE_B_COIN")
     if crash_window:
         raise ValueError("coin_common names the configuration word of crash_window: give one")
@@ -535,7 +552,7 @@ def _coin_word(mode, crash_window, coin_common):
 
 
 def _faulty_array(N, faulty, byzantine, mode):
-    """The faulty bytes: 1 for a faulty node, and in modes 8 to 11 2 for a Byzantine one (an int entry of
+    """The faulty bytes: 1 for a faulty node, and in modes 8 to 13 2 for a Byzantine one (an int entry of
     `faulty` goes through as it is there, so that the library's validation can be reached)."""
     raw = mode in _BYZ_MODES
     fl = [v if raw and type(v) is int else (1 if v else 0) for v in faulty]

@@ -17,6 +17,8 @@
                                                                           # ... under Ben-Or's Byzantine-tolerant rule (N > 5F)
     python -m benor.cli trials --N 1024 --F 204 --mode byzb --crashed 0 --byzantine 16 --byz-strategy split --coin-common 1
                                                                           # ... with a shared coin in every round
+    python -m benor.cli trials --N 64 --F 20 --mode byz --crashed 0 --byzantine 0 --byz-strategy split --delivery adversarial
+                                                                          # an adversarial scheduler, no Byzantine node
     python -m benor.cli sweep --N 64,128,...,4096 --steps 32 --trials 2**30 --out sweep.csv
                                                                           # C5 phase diagram
     python -m benor.cli sweep --cells 4096:0,4096:1984 --per-cell 4793490  # two cells of it
@@ -38,7 +40,8 @@ undecided, agreement violations.  `--mode tally3 --crashed f` draws the same
 diagram under count-level random delivery (BO_MODE_RANDOM_TALLY3) with the first
 f nodes of every cell crashed (f at most each cell's F; the rows' m is N - f).
 `--mode byz` and `--mode byzb` (BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B, and with
-`--coin-common p` their shared-coin modes) cross every (N, F) cell with
+`--coin-common p` their shared-coin modes, with `--delivery adversarial` the
+adversarial scheduler's modes, whose rows add a delivery column) cross every (N, F) cell with
 b = floor(beta (F - f)) Byzantine nodes, beta = i / S for i = 0..S (`--byz-steps S`),
 placed as `trials` places them: the first f nodes crashed, the next b Byzantine.
 `--cells` then also takes N:F:b.  Their rows add b, mode, byz_strategy,
@@ -115,8 +118,23 @@ def byz_sched(a, benor) -> dict:
     return sched
 
 
+def check_delivery(a) -> bool:
+    """--delivery of `trials` and `sweep`: whether an adversarial scheduler delivers.  Its argument
+    errors need no device."""
+    if a.delivery != "adversarial":
+        return False
+    if a.mode not in ("byz", "byzb"):
+        raise SystemExit("--delivery adversarial needs --mode byz or --mode byzb")
+    if a.byz_strategy not in ("balance", "split"):
+        raise SystemExit("--delivery adversarial needs --byz-strategy balance or --byz-strategy split")
+    return True
+
+
 def byz_mode(a, benor) -> int:
-    """BO_MODE_* of --mode byz / byzb: with --coin-common, the shared-coin mode."""
+    """BO_MODE_* of --mode byz / byzb: with --delivery adversarial the scheduler's mode, else with --coin-common
+    the shared-coin mode."""
+    if a.delivery == "adversarial":
+        return benor.BO_MODE_SCHED_TALLY if a.mode == "byz" else benor.BO_MODE_SCHED_RULE_B
     if a.coin_common is not None:
         return benor.BO_MODE_BYZ_COIN if a.mode == "byz" else benor.BO_MODE_BYZ_RULE_B_COIN
     return benor.BO_MODE_BYZ_TALLY if a.mode == "byz" else benor.BO_MODE_BYZ_RULE_B
@@ -131,6 +149,7 @@ def cmd_trials(a) -> int:
             "subset": benor.BO_MODE_CRASH_SUBSET, "byz": benor.BO_MODE_BYZ_TALLY,
             "byzb": benor.BO_MODE_BYZ_RULE_B}[a.mode]
     crashed = a.F if a.crashed is None else a.crashed            # the first f nodes (start.ts:7-18 placement)
+    adversarial = check_delivery(a)
     sched = {}
     if a.mode in ("crash", "partial", "subset"):                  # crashes during the run, in steps
         if a.crash_at and a.crash_count:
@@ -189,6 +208,8 @@ def cmd_trials(a) -> int:
                    kernel=benor.KERNEL_NAMES[plan.kernel])
         if a.coin_common is not None:
             row.update(coin_common=a.coin_common, coin_common_word=sched["coin_common"])
+        if adversarial:
+            row.update(delivery=a.delivery)
     row["seconds"] = dt
     print(json.dumps(row))
     return 0
@@ -233,6 +254,7 @@ def sweep_byz_cells(a):
 
 def cmd_sweep(a) -> int:
     byz = a.mode in ("byz", "byzb")
+    adversarial = check_delivery(a)
     if not byz and (a.coin_common is not None or a.byz_steps is not None or a.byz_strategy is not None or
                     a.byz_one is not None):
         raise SystemExit("--byz-steps / --byz-strategy / --byz-one / --coin-common need --mode byz or --mode byzb")
@@ -276,7 +298,8 @@ def cmd_sweep(a) -> int:
         raise SystemExit("sweep --crashed needs --mode tally3 (lockstep crashes exactly F nodes per cell)")
     if byz:
         rows, elapsed = run_sweep(cells, per_cell, a.seed, a.k_max, a.streams, rank, world, a.progress,
-                                  mode=a.mode, crashed=byz_crashed, byz=dict(sched, strategy_name=a.byz_strategy))
+                                  mode=a.mode, crashed=byz_crashed, byz=dict(sched, strategy_name=a.byz_strategy),
+                                  delivery="adversarial" if adversarial else "random")
     elif a.mode == "tally3":
         crashed = 0 if a.crashed is None else a.crashed
         bad = [f"{N}:{F}" for (N, F) in cells if crashed > F]
@@ -308,7 +331,7 @@ def rows_csv(rows: list[dict]) -> str:
 
 
 def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progress=False, mode="lockstep",
-              crashed=None, byz=None):
+              crashed=None, byz=None, delivery="random"):
     """The sweep's GPU work on the current device: (rows, seconds).  Under
     torch.distributed (world > 1) each cell's trials are split over the ranks
     and the histograms merged by one all-reduce.  mode "lockstep": F crashed
@@ -316,7 +339,9 @@ def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progre
     every cell crashed (a count, at most each cell's F; default 0).  "byz" and
     "byzb": cells are (N, F, b), the first `crashed` nodes crashed and the next b
     Byzantine; `byz` holds byz_one and byz_strategy (words), strategy_name for the
-    rows, and with coin_common the shared-coin modes' word."""
+    rows, and with coin_common the shared-coin modes' word; `delivery` "adversarial"
+    runs them under the adversarial scheduler (byz_strategy balance or split), and
+    the rows then add a delivery column."""
     import torch
 
     import benor
@@ -333,6 +358,8 @@ def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progre
     # round-robin over --streams streams: each plan owns its buffers, so cells are
     # independent, and one cell's short passes (deferred-trial rounds, the last
     # groups of a launch) overlap the next cell's launches instead of idling CUs.
+    if delivery not in ("random", "adversarial") or (delivery == "adversarial" and mode not in ("byz", "byzb")):
+        raise ValueError("delivery is 'random', or 'adversarial' with mode 'byz' or 'byzb'")
     if mode == "lockstep":
         if crashed is not None:
             raise ValueError("crashed needs mode 'tally3' (lockstep crashes exactly F nodes per cell)")
@@ -357,6 +384,8 @@ def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progre
         coin = "coin_common" in byz
         bo_mode = {("byz", False): benor.BO_MODE_BYZ_TALLY, ("byzb", False): benor.BO_MODE_BYZ_RULE_B,
                    ("byz", True): benor.BO_MODE_BYZ_COIN, ("byzb", True): benor.BO_MODE_BYZ_RULE_B_COIN}[mode, coin]
+        if delivery == "adversarial":
+            bo_mode = benor.BO_MODE_SCHED_TALLY if mode == "byz" else benor.BO_MODE_SCHED_RULE_B
         plans = [benor.TrialsPlan(N, F, [i < crashed for i in range(N)], seed=seed ^ (N << 20) ^ F ^ (b << 44),
                                   k_max=k_max, mode=bo_mode,
                                   byzantine=[crashed <= i < crashed + b for i in range(N)], **byz)
@@ -382,6 +411,8 @@ def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progre
         for row, (_, _, b) in zip(rows, cells):
             row.update(b=b, mode=mode, byz_strategy=name, byz_one_word=byz["byz_one"],
                        coin_common_word=byz.get("coin_common", 0))
+            if delivery == "adversarial":
+                row.update(delivery=delivery)
     elapsed = time.perf_counter() - t0
     for plan in plans:
         plan.check()                               # device-side capacity invariants of every cell
@@ -435,6 +466,10 @@ def main(argv=None) -> int:
                         "senders hold; --byz-one on a tie), balance (the liars in a receiver's inbox see its honest "
                         "messages and make its two tallies as equal as they can) or split (they say 1 to receivers of odd "
                         "compact index and 0 to the others); the last two do not read --byz-one")
+    t.add_argument("--delivery", choices=["random", "adversarial"], default="random",
+                   help="byz, byzb: who composes a receiver's inbox: random (a uniform draw of N - F of the live senders) "
+                        "or adversarial (a scheduler picks the N - F messages and the lies, BO_MODE_SCHED_TALLY and "
+                        "BO_MODE_SCHED_RULE_B; needs --byz-strategy balance or split, allows --byzantine 0)")
     t.add_argument("--coin-common", type=float, default=None,
                    help="byz, byzb: a shared coin (BO_MODE_BYZ_COIN, BO_MODE_BYZ_RULE_B_COIN): the probability in [0, 1] "
                         "that a round's coin is common to all honest nodes (0: the mode without it)")
@@ -457,6 +492,7 @@ def main(argv=None) -> int:
     w.add_argument("--byz-strategy", choices=list(_BYZ_STRATEGIES), default=None, help="byz, byzb: as in `trials`")
     w.add_argument("--byz-one", type=float, default=None, help="byz, byzb: as in `trials` (default 0.5)")
     w.add_argument("--coin-common", type=float, default=None, help="byz, byzb: as in `trials`")
+    w.add_argument("--delivery", choices=["random", "adversarial"], default="random", help="byz, byzb: as in `trials`")
     w.add_argument("--out", default=None)
     w.add_argument("--progress", action="store_true")
     a = ap.parse_args(argv)

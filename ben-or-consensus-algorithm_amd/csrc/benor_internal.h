@@ -75,6 +75,8 @@ struct KParams {
                             // 14: three-valued count-level random delivery with Byzantine senders (benor_tally_byz.hip)
                             // 15: ... under Ben-Or's Byzantine-tolerant rule (the same file's loops, Protocol B's rule)
                             // 16, 17: variants 14 and 15 with a shared coin (the same loops, the CoinShared policy)
+                            // 18..21: count-level delivery under an adversarial scheduler (benor_tally_sched.hip):
+                            //         18 the reference's rule, 19 Protocol B's, 20 and 21 the two with a shared coin
   uint32_t base_variant;    // variant 7: the popcount kernel (1 W, 0 blocked) that serves the state
   uint32_t base_G;          //   launches and the deferred trials, and its G
   uint32_t mode;            // BO_MODE_LOCKSTEP / BO_MODE_RANDOM_DELIVERY / BO_MODE_EVENT / BO_MODE_RANDOM_TALLY /
@@ -83,7 +85,8 @@ struct KParams {
                             // BO_MODE_CRASH_TALLY, BO_MODE_CRASH_PARTIAL or BO_MODE_CRASH_SUBSET plan with an empty
                             // schedule is BO_MODE_RANDOM_TALLY3's, and so is a BO_MODE_BYZ_TALLY plan without a
                             // Byzantine node; a BO_MODE_BYZ_RULE_B plan keeps its mode at b = 0; a BO_MODE_BYZ_COIN
-                            // or BO_MODE_BYZ_RULE_B_COIN plan with coin_common = 0 is its parent mode's plan)
+                            // or BO_MODE_BYZ_RULE_B_COIN plan with coin_common = 0 is its parent mode's plan;
+                            // a BO_MODE_SCHED_TALLY or BO_MODE_SCHED_RULE_B plan always keeps its mode)
   uint32_t q;               // quorum N - F (messages each receiver tallies per phase)
   uint32_t k_max;
   uint32_t init_mode;       // BO_INIT_RANDOM / BO_INIT_FIXED
@@ -190,6 +193,8 @@ struct KParams {
   // or where they lie in global memory.  tally_off / tally_thr hold the one table of (m, q).
   // BO_BYZ_BALANCE and BO_BYZ_SPLIT read no thresholds: byz_thr is unused and byz_lds is 0; so it is
   // in a variant-15 plan with byz_n = 0 (byz_thr NULL), which variant 14 does not have
+  // ... under an adversarial scheduler (variants 18 to 21): byz_plane and byz_n (>= 0) as above, byz_strategy
+  // BO_BYZ_BALANCE or BO_BYZ_SPLIT; no table (tally_off, tally_thr NULL, tally_cap 0), byz_thr and byz_one unused
   const unsigned long long *byz_plane;
   const unsigned long long *byz_thr;
   uint32_t byz_n, byz_strategy, byz_one, byz_lds;
@@ -198,7 +203,7 @@ struct KParams {
   // launches) and the chunk C, set per launch; mfma_chunk = 0: the static form
   uint32_t *mfma_claim;
   uint32_t mfma_chunk;
-  // variants 16 and 17: the probability, in units of 2^-32, that a round's coin is common to the honest
+  // variants 16, 17, 20 and 21: the probability, in units of 2^-32, that a round's coin is common to the honest
   // nodes (bo_trials_cfg::coin_common, never 0 here; UINT32_MAX: every round)
   uint32_t coin_common;
 };
@@ -267,6 +272,8 @@ bool byz_thr_in_lds(uint32_t lds_bytes, uint32_t b);
 bool byz_heard(const KParams &p);                 // BO_BYZ_BALANCE, BO_BYZ_SPLIT with byz_n > 0: the kernel without thresholds
 int byz_blocks_per_cu(const KParams &p);
 hipError_t launch_tally_byz(const KParams &p, int grid_blocks, hipStream_t stream);
+int sched_blocks_per_cu(const KParams &p);        // benor_tally_sched.hip: under an adversarial scheduler
+hipError_t launch_tally_sched(const KParams &p, int grid_blocks, hipStream_t stream);
 
 // Event level for kMaxEventN < N <= BO_MAX_N (benor_event_big.hip): one wave per trial.
 // The wave-per-trial event kernel keeps its message pool in LDS when it is at

@@ -675,6 +675,17 @@ void plan_geometry(KParams &p) {
     }
     return;
   }
+  if (p.mode == BO_MODE_SCHED_TALLY || p.mode == BO_MODE_SCHED_RULE_B) {
+    // The adversarial scheduler (benor_tally_sched.hip): the Byzantine kernels' planes and nothing else -- no
+    // row region (tally_cap stays 0: there is no table) and no thresholds behind the waves' regions.
+    p.G = 1;
+    p.nblocks = W;
+    p.tally_cap = 0u;
+    p.variant = 18u + (p.mode == BO_MODE_SCHED_RULE_B ? 1u : 0u) + (p.coin_common != 0u ? 2u : 0u);
+    p.wave_bytes = (byz_wave_bytes(W, 0u) + 15u) & ~15u;
+    p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
+    return;
+  }
   if (p.m <= kMaxLaneM) {                           // lane kernel: one trial per lane
     const uint32_t M1 = p.m - p.init_q;
     const bool odd = (p.m & 1u) && (M1 & 1u);        // every vote count odd: no tie, no coin
@@ -812,6 +823,7 @@ hipError_t launch_lockstep(const KParams &p, int grid, hipStream_t s) {
   if (p.variant == 12) return launch_tally_partial(p, grid, s);
   if (p.variant == 13) return launch_tally_subset(p, grid, s);
   if (p.variant >= 14 && p.variant <= 17) return launch_tally_byz(p, grid, s);
+  if (p.variant >= 18 && p.variant <= 21) return launch_tally_sched(p, grid, s);
   if (p.variant == 2 && p.rd_a) return launch_random_bern(p, grid, s);
   if (p.variant == 2) {                      // Floyd sampler
     if (p.lds_bytes > 64u * 1024u) {
@@ -901,7 +913,7 @@ uint32_t mfma_chunk(const KParams &p, int device) {
   return c;
 }
 
-// Resident workgroups per CU of the count-level kernel of variant 9..17 (0 = unknown).
+// Resident workgroups per CU of the count-level kernel of variant 9..21 (0 = unknown).
 static int count_level_blocks_per_cu(const KParams &p) {
   switch (p.variant) {
     case 9: return tally_blocks_per_cu(p);
@@ -909,6 +921,7 @@ static int count_level_blocks_per_cu(const KParams &p) {
     case 11: return crash_blocks_per_cu(p);
     case 12: return partial_blocks_per_cu(p);
     case 13: return subset_blocks_per_cu(p);
+    case 18: case 19: case 20: case 21: return sched_blocks_per_cu(p);
     default: return byz_blocks_per_cu(p);
   }
 }
@@ -972,7 +985,7 @@ int lockstep_grid(const KParams &p, int device) {
     const uint64_t lds_fit = lds_groups_per_cu(lds);
     if (lds_fit < per_cu) per_cu = lds_fit ? lds_fit : 1;
   }
-  if (p.variant >= 9 && p.variant <= 17) {   // the count-level kernels are register-bound (benor_tally.hip: per unroll)
+  if (p.variant >= 9 && p.variant <= 21) {   // the count-level kernels are register-bound (benor_tally.hip: per unroll)
     const uint64_t fit = (uint64_t)count_level_blocks_per_cu(p);
     if (fit >= 1u && fit < per_cu) per_cu = fit;
   }

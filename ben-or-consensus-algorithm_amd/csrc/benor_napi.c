@@ -587,11 +587,11 @@ static napi_value run_trials(napi_env env, napi_callback_info info) {
     j->trial_begin = prop_u64(env, o, "trialBegin", 0);
     j->trial_count = prop_u64(env, o, "trialCount", 1);
     uint32_t mode = BO_MODE_LOCKSTEP;
-    prop_u32(env, o, "mode", BO_MODE_LOCKSTEP, &mode);          /* 0 lockstep, 1 random delivery, 2 event, 3 random tally, 4 random tally3, 5 crash tally, 6 crash partial, 7 crash subset, 8 byz tally, 9 byz rule B, 10 and 11 the two with a shared coin */
+    prop_u32(env, o, "mode", BO_MODE_LOCKSTEP, &mode);          /* 0 lockstep, 1 random delivery, 2 event, 3 random tally, 4 random tally3, 5 crash tally, 6 crash partial, 7 crash subset, 8 byz tally, 9 byz rule B, 10 and 11 the two with a shared coin, 12 and 13 the two under an adversarial scheduler */
     j->cfg.mode = mode;
     prop_u32(env, o, "crashCount", 0, &j->cfg.crash_count);
     prop_u32(env, o, "crashWindow", 0, &j->cfg.crash_window);
-    prop_u32(env, o, "coinCommon", j->cfg.crash_window, &j->cfg.coin_common);   /* modes 10, 11: the same word, the probability that a round's coin is common */
+    prop_u32(env, o, "coinCommon", j->cfg.crash_window, &j->cfg.coin_common);   /* modes 10 to 13: the same word, the probability that a round's coin is common */
     prop_u32(env, o, "crashCut", 0, &j->cfg.crash_cut);          /* mode 6: 0 .. N - f, or BO_CUT_RANDOM */
     prop_u32(env, o, "crashReach", j->cfg.crash_cut, &j->cfg.crash_reach);   /* mode 7: the same word, a probability in units of 2^-32 */
     prop_u32(env, o, "byzOne", j->cfg.crash_cut, &j->cfg.byz_one);           /* modes 8, 9: the same word, the probability that a Byzantine message carries 1 */
@@ -618,7 +618,8 @@ static napi_value run_trials(napi_env env, napi_callback_info info) {
     }
     napi_has_named_property(env, o, "byzantineList", &has);
     if (has && (mode == BO_MODE_BYZ_TALLY || mode == BO_MODE_BYZ_RULE_B || mode == BO_MODE_BYZ_COIN ||
-                mode == BO_MODE_BYZ_RULE_B_COIN)) {   /* modes 8 to 11: a live node that lies; faulty[i] = 2 */
+                mode == BO_MODE_BYZ_RULE_B_COIN || mode == BO_MODE_SCHED_TALLY ||
+                mode == BO_MODE_SCHED_RULE_B)) {   /* modes 8 to 13: a live node that lies; faulty[i] = 2 */
         napi_get_named_property(env, o, "byzantineList", &arr);
         uint32_t n = 0;
         if (read_array(env, arr, &n))

@@ -570,12 +570,17 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   if (cfg->mode != BO_MODE_LOCKSTEP && cfg->mode != BO_MODE_RANDOM_DELIVERY && cfg->mode != BO_MODE_EVENT &&
       cfg->mode != BO_MODE_RANDOM_TALLY && cfg->mode != BO_MODE_RANDOM_TALLY3 && cfg->mode != BO_MODE_CRASH_TALLY &&
       cfg->mode != BO_MODE_CRASH_PARTIAL && cfg->mode != BO_MODE_CRASH_SUBSET && cfg->mode != BO_MODE_BYZ_TALLY &&
-      cfg->mode != BO_MODE_BYZ_RULE_B && cfg->mode != BO_MODE_BYZ_COIN && cfg->mode != BO_MODE_BYZ_RULE_B_COIN)
+      cfg->mode != BO_MODE_BYZ_RULE_B && cfg->mode != BO_MODE_BYZ_COIN && cfg->mode != BO_MODE_BYZ_RULE_B_COIN &&
+      cfg->mode != BO_MODE_SCHED_TALLY && cfg->mode != BO_MODE_SCHED_RULE_B)
     return fail(BO_ERR_UNSUPPORTED, "unknown delivery mode");
+  // BO_MODE_SCHED_TALLY and BO_MODE_SCHED_RULE_B: BO_MODE_BYZ_COIN's and BO_MODE_BYZ_RULE_B_COIN's configuration and
+  // validation; the strategy names the scheduler's aim, and the plan keeps its mode at b = 0 and at coin_common = 0
+  const bool sched_mode = cfg->mode == BO_MODE_SCHED_TALLY || cfg->mode == BO_MODE_SCHED_RULE_B;
   // BO_MODE_BYZ_COIN and BO_MODE_BYZ_RULE_B_COIN: their parent modes' configuration and validation; the crash_window word is coin_common
-  const bool coin_mode = cfg->mode == BO_MODE_BYZ_COIN || cfg->mode == BO_MODE_BYZ_RULE_B_COIN;
-  const bool rule_b = cfg->mode == BO_MODE_BYZ_RULE_B || cfg->mode == BO_MODE_BYZ_RULE_B_COIN;   // BO_MODE_BYZ_TALLY's configuration and validation, another rule
-  const bool byz_mode = cfg->mode == BO_MODE_BYZ_TALLY || cfg->mode == BO_MODE_BYZ_COIN || rule_b;
+  const bool coin_mode = cfg->mode == BO_MODE_BYZ_COIN || cfg->mode == BO_MODE_BYZ_RULE_B_COIN || sched_mode;
+  const bool rule_b = cfg->mode == BO_MODE_BYZ_RULE_B || cfg->mode == BO_MODE_BYZ_RULE_B_COIN ||
+                      cfg->mode == BO_MODE_SCHED_RULE_B;   // BO_MODE_BYZ_TALLY's configuration and validation, another rule
+  const bool byz_mode = cfg->mode == BO_MODE_BYZ_TALLY || cfg->mode == BO_MODE_BYZ_COIN || rule_b || sched_mode;
   const bool crash_mode = cfg->mode == BO_MODE_CRASH_TALLY || cfg->mode == BO_MODE_CRASH_PARTIAL ||
                           cfg->mode == BO_MODE_CRASH_SUBSET;
   const bool random_mode = cfg->mode == BO_MODE_RANDOM_DELIVERY || cfg->mode == BO_MODE_RANDOM_TALLY ||
@@ -590,7 +595,9 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
     for (uint32_t i = 0; i < cfg->N; ++i)
       if (cfg->faulty[i] > 2u)
         return fail(BO_ERR_INVALID_ARGUMENT,
-                    cfg->mode == BO_MODE_BYZ_RULE_B_COIN ? "BO_MODE_BYZ_RULE_B_COIN: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)"
+                    cfg->mode == BO_MODE_SCHED_RULE_B    ? "BO_MODE_SCHED_RULE_B: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)"
+                    : cfg->mode == BO_MODE_SCHED_TALLY   ? "BO_MODE_SCHED_TALLY: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)"
+                    : cfg->mode == BO_MODE_BYZ_RULE_B_COIN ? "BO_MODE_BYZ_RULE_B_COIN: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)"
                     : cfg->mode == BO_MODE_BYZ_COIN      ? "BO_MODE_BYZ_COIN: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)"
                     : rule_b                             ? "BO_MODE_BYZ_RULE_B: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)"
                                                          : "BO_MODE_BYZ_TALLY: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)");
@@ -598,6 +605,10 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
         cfg->byz_strategy != BO_BYZ_SPLIT)
       return fail(BO_ERR_INVALID_ARGUMENT,
                   "byz_strategy must be BO_BYZ_RANDOM, BO_BYZ_OPPOSE, BO_BYZ_BALANCE or BO_BYZ_SPLIT");
+    if (sched_mode && cfg->byz_strategy != BO_BYZ_BALANCE && cfg->byz_strategy != BO_BYZ_SPLIT)
+      return fail(BO_ERR_INVALID_ARGUMENT,
+                  "byz_strategy must be BO_BYZ_BALANCE or BO_BYZ_SPLIT under an adversarial scheduler "
+                  "(BO_MODE_SCHED_TALLY, BO_MODE_SCHED_RULE_B)");
   }
   const auto crashed = [&](uint32_t i) { return byz_mode ? cfg->faulty[i] == 1u : cfg->faulty[i] != 0u; };
   uint32_t f = 0, nbyz = 0;
@@ -613,7 +624,9 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
     return fail(BO_ERR_FAULTY_COUNT, "random delivery needs at most F crash-faulty nodes");
   if (f + nbyz > cfg->F)
     return fail(BO_ERR_FAULTY_COUNT,
-                cfg->mode == BO_MODE_BYZ_RULE_B_COIN ? "BO_MODE_BYZ_RULE_B_COIN needs at most F nodes crashed or Byzantine"
+                cfg->mode == BO_MODE_SCHED_RULE_B    ? "BO_MODE_SCHED_RULE_B needs at most F nodes crashed or Byzantine"
+                : cfg->mode == BO_MODE_SCHED_TALLY   ? "BO_MODE_SCHED_TALLY needs at most F nodes crashed or Byzantine"
+                : cfg->mode == BO_MODE_BYZ_RULE_B_COIN ? "BO_MODE_BYZ_RULE_B_COIN needs at most F nodes crashed or Byzantine"
                 : cfg->mode == BO_MODE_BYZ_COIN      ? "BO_MODE_BYZ_COIN needs at most F nodes crashed or Byzantine"
                 : rule_b                             ? "BO_MODE_BYZ_RULE_B needs at most F nodes crashed or Byzantine"
                                                      : "BO_MODE_BYZ_TALLY needs at most F nodes crashed or Byzantine");
@@ -653,7 +666,7 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   kp.seed = cfg->seed;
   kp.mode = cfg->mode;
   // A shared-coin plan whose rounds are never common is its parent mode's plan; otherwise it carries the word.
-  if (coin_mode && cfg->coin_common == 0u) kp.mode = rule_b ? BO_MODE_BYZ_RULE_B : BO_MODE_BYZ_TALLY;
+  if (coin_mode && !sched_mode && cfg->coin_common == 0u) kp.mode = rule_b ? BO_MODE_BYZ_RULE_B : BO_MODE_BYZ_TALLY;
   if (coin_mode) kp.coin_common = cfg->coin_common;
   kp.q = cfg->N - cfg->F;
   kp.crash_count = byz_mode ? 0u : cfg->crash_count;   // (BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B: the word is byz_strategy)
@@ -698,7 +711,7 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   // (a shared coin keeps its plan at b = 0: mode 4 has no such coin)
   if (kp.mode == BO_MODE_BYZ_TALLY && nbyz == 0) kp.mode = BO_MODE_RANDOM_TALLY3;
   if (kp.mode == BO_MODE_BYZ_TALLY || kp.mode == BO_MODE_BYZ_RULE_B || kp.mode == BO_MODE_BYZ_COIN ||
-      kp.mode == BO_MODE_BYZ_RULE_B_COIN) {
+      kp.mode == BO_MODE_BYZ_RULE_B_COIN || sched_mode) {
     kp.byz_n = nbyz;
     kp.byz_strategy = cfg->byz_strategy;
     kp.byz_one = cfg->byz_one;
@@ -914,6 +927,13 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
         if (lie_bytes) kp.byz_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + off_bytes + thr_bytes);
         kp.byz_plane = reinterpret_cast<const unsigned long long *>(pl->d_tally + off_bytes + thr_bytes + lie_bytes);
       }
+    } else if (kp.variant >= 18 && kp.variant <= 21) {
+      // BO_MODE_SCHED_TALLY, BO_MODE_SCHED_RULE_B: the honest plane alone -- the scheduler's counts are a closed form
+      const size_t plane_bytes = sizeof(uint64_t) * crash.honest.size();
+      e = hipMalloc(&pl->d_tally, plane_bytes);
+      if (e == hipSuccess) e = hipMemcpy(pl->d_tally, crash.honest.data(), plane_bytes, hipMemcpyHostToDevice);
+      if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "honest plane upload"); }
+      kp.byz_plane = reinterpret_cast<const unsigned long long *>(pl->d_tally);
     } else if (kp.variant == 11 || kp.variant == 12 || kp.variant == 13) {
       // BO_MODE_CRASH_TALLY, BO_MODE_CRASH_PARTIAL, BO_MODE_CRASH_SUBSET: one table per reachable live count (pool
       // size), and their directory
@@ -999,7 +1019,7 @@ uint64_t bo_plan_popc_words_per_node_round(const bo_plan *pl) {
       pl->kp.mode != BO_MODE_RANDOM_TALLY3 && pl->kp.mode != BO_MODE_CRASH_TALLY &&
       pl->kp.mode != BO_MODE_CRASH_PARTIAL && pl->kp.mode != BO_MODE_CRASH_SUBSET &&
       pl->kp.mode != BO_MODE_BYZ_TALLY && pl->kp.mode != BO_MODE_BYZ_RULE_B && pl->kp.mode != BO_MODE_BYZ_COIN &&
-      pl->kp.mode != BO_MODE_BYZ_RULE_B_COIN)
+      pl->kp.mode != BO_MODE_BYZ_RULE_B_COIN && pl->kp.mode != BO_MODE_SCHED_TALLY && pl->kp.mode != BO_MODE_SCHED_RULE_B)
     counts = ((pl->kp.m - pl->kp.init_q) & 1u) ? 2ull : 3ull;
   return counts * ((pl->kp.m + 31ull) / 32ull);
 }
@@ -1331,7 +1351,8 @@ void initial_states(const bo_trials_cfg *cfg, std::vector<bo_node_state> &st) {
     const bool f = cfg->faulty[i] != 0;
     // (BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B: a Byzantine node is alive and has no protocol state; no kernel writes its entry)
     const bool byz = (cfg->mode == BO_MODE_BYZ_TALLY || cfg->mode == BO_MODE_BYZ_RULE_B || cfg->mode == BO_MODE_BYZ_COIN ||
-                      cfg->mode == BO_MODE_BYZ_RULE_B_COIN) && cfg->faulty[i] == 2u;
+                      cfg->mode == BO_MODE_BYZ_RULE_B_COIN || cfg->mode == BO_MODE_SCHED_TALLY ||
+                      cfg->mode == BO_MODE_SCHED_RULE_B) && cfg->faulty[i] == 2u;
     st[i].killed = f && !byz ? 1 : 0;
     st[i].x = f ? -1 : (cfg->init_mode == BO_INIT_FIXED ? cfg->init[i] : -1);
     st[i].decided = f ? -1 : 0;

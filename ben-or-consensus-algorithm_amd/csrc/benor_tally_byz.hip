@@ -3,8 +3,8 @@
 // under Ben-Or's Byzantine-tolerant rule (BO_MODE_BYZ_RULE_B, b >= 0).
 //
 // Two trial loops, each a template over the rule applied to a receiver's counts
-// (RuleRef, RuleB below) and over the coin a P-phase takes (CoinLocal, CoinShared;
-// benor_tally_common.h): variant 14 runs <RuleRef, CoinLocal>, variant 15 <RuleB,
+// (RuleRef, RuleB) and over the coin a P-phase takes (CoinLocal, CoinShared; all four
+// in benor_tally_common.h): variant 14 runs <RuleRef, CoinLocal>, variant 15 <RuleB,
 // CoinLocal>, and variants 16 and 17 the same two rules with <CoinShared>, the shared
 // coin of BO_MODE_BYZ_COIN and BO_MODE_BYZ_RULE_B_COIN.  Everything
 // else in this comment holds for all of them.
@@ -59,43 +59,7 @@ namespace {
 constexpr uint32_t kByzCertain = 0xFFFFFFFFu;      // KParams::byz_one: every Byzantine message carries 1
 constexpr uint32_t kByzWgPerCu = 6u;               // resident workgroups the registers allow (__launch_bounds__ below)
 
-// The rule a receiver applies to its counts (c0, c1), the one thing in which BO_MODE_BYZ_TALLY and
-// BO_MODE_BYZ_RULE_B differ: the R-phase's proposal ballots of a group and the P-phase rule.
-// kNoLiar: the mode runs its kernel without a Byzantine node too (byz_n = 0: every step wave-uniform
-// with B1 = 0, no threshold read).
-struct RuleRef {                                   // the reference's crash-tolerant rule (node.ts:46-158)
-  static constexpr bool kNoLiar = false;           // (b = 0 is mode 4's plan; with a shared coin it is not, and runs here)
-  static __device__ __forceinline__ void r(uint32_t c0, uint32_t c1, uint32_t, uint32_t, uint64_t hp, uint64_t &p0,
-                                           uint64_t &p1) {
-    p0 = ballot(c0 > c1) & hp;
-    p1 = ballot(c1 > c0) & hp;
-  }
-  template <class Coin>
-  static __device__ __forceinline__ uint64_t p(uint32_t c0, uint32_t c1, uint32_t, uint32_t F, uint64_t hp, uint32_t k0,
-                                               uint32_t k1, uint32_t tlo, uint32_t thi, uint32_t j, uint32_t r,
-                                               bool &decided, Coin &coin) {
-    return p_rule(c0, c1, F, hp, k0, k1, tlo, thi, j, r, decided, coin);
-  }
-};
-struct RuleB {                                     // Ben-Or's Protocol B, t = F
-  static constexpr bool kNoLiar = true;
-  static __device__ __forceinline__ void r(uint32_t c0, uint32_t c1, uint32_t N, uint32_t F, uint64_t hp, uint64_t &p0,
-                                           uint64_t &p1) {
-    r_rule_b(c0, c1, N, F, hp, p0, p1);
-  }
-  template <class Coin>
-  static __device__ __forceinline__ uint64_t p(uint32_t c0, uint32_t c1, uint32_t N, uint32_t F, uint64_t hp, uint32_t k0,
-                                               uint32_t k1, uint32_t tlo, uint32_t thi, uint32_t j, uint32_t r,
-                                               bool &decided, Coin &coin) {
-    return p_rule_b(c0, c1, N, F, hp, k0, k1, tlo, thi, j, r, decided, coin);
-  }
-};
-
-template <class Coin>
-__device__ __forceinline__ Coin make_coin(const KParams &p) {
-  if constexpr (Coin::kShared) return Coin{p.coin_common, 0u};
-  else return Coin{};
-}
+// (RuleRef, RuleB and make_coin: benor_tally_common.h, shared with benor_tally_sched.hip)
 
 // The oblivious strategies (BO_BYZ_RANDOM, BO_BYZ_OPPOSE), for either rule: benor_tally_byz_kernel<RuleRef> is
 // variant 14's entry, <RuleB> variant 15's.  The entries themselves are the templates: a rule-templated

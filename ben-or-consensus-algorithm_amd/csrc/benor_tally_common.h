@@ -1,6 +1,6 @@
 // benor_tally_common.h -- what the count-level kernels share:
 // benor_tally.hip, benor_tally3.hip, benor_tally_crash.hip, benor_tally_partial.hip,
-// benor_tally_subset.hip and benor_tally_byz.hip (two kernels).  Each piece stands
+// benor_tally_subset.hip, benor_tally_byz.hip (two kernels) and benor_tally_sched.hip.  Each piece stands
 // here once: the per-wave LDS layouts, the threshold search, the three-class draw
 // in its wave-uniform and its per-lane form, the stream-6 walk whose word order is
 // the bit-exact contract with the oracle, a trial's start and end, the P-phase
@@ -441,6 +441,46 @@ __device__ __forceinline__ uint64_t p_rule_b(uint32_t c0, uint32_t c1, uint32_t 
   if (take) x1 |= coin(k0, k1, tlo, thi, j, r, take);
   decided = adopt && 2u * cv > N + F;
   return x1;
+}
+
+// ---- the rule as a compile-time policy of the Byzantine and the scheduler trial loops
+// (benor_tally_byz.hip, benor_tally_sched.hip)
+// The rule a receiver applies to its counts (c0, c1), the one thing in which BO_MODE_BYZ_TALLY and
+// BO_MODE_BYZ_RULE_B differ: the R-phase's proposal ballots of a group and the P-phase rule.
+// kNoLiar: the mode runs its kernel without a Byzantine node too (byz_n = 0: every step wave-uniform
+// with B1 = 0, no threshold read).
+struct RuleRef {                                   // the reference's crash-tolerant rule (node.ts:46-158)
+  static constexpr bool kNoLiar = false;           // (b = 0 is mode 4's plan; with a shared coin it is not, and runs here)
+  static __device__ __forceinline__ void r(uint32_t c0, uint32_t c1, uint32_t, uint32_t, uint64_t hp, uint64_t &p0,
+                                           uint64_t &p1) {
+    p0 = ballot(c0 > c1) & hp;
+    p1 = ballot(c1 > c0) & hp;
+  }
+  template <class Coin>
+  static __device__ __forceinline__ uint64_t p(uint32_t c0, uint32_t c1, uint32_t, uint32_t F, uint64_t hp, uint32_t k0,
+                                               uint32_t k1, uint32_t tlo, uint32_t thi, uint32_t j, uint32_t r,
+                                               bool &decided, Coin &coin) {
+    return p_rule(c0, c1, F, hp, k0, k1, tlo, thi, j, r, decided, coin);
+  }
+};
+struct RuleB {                                     // Ben-Or's Protocol B, t = F
+  static constexpr bool kNoLiar = true;
+  static __device__ __forceinline__ void r(uint32_t c0, uint32_t c1, uint32_t N, uint32_t F, uint64_t hp, uint64_t &p0,
+                                           uint64_t &p1) {
+    r_rule_b(c0, c1, N, F, hp, p0, p1);
+  }
+  template <class Coin>
+  static __device__ __forceinline__ uint64_t p(uint32_t c0, uint32_t c1, uint32_t N, uint32_t F, uint64_t hp, uint32_t k0,
+                                               uint32_t k1, uint32_t tlo, uint32_t thi, uint32_t j, uint32_t r,
+                                               bool &decided, Coin &coin) {
+    return p_rule_b(c0, c1, N, F, hp, k0, k1, tlo, thi, j, r, decided, coin);
+  }
+};
+
+template <class Coin>
+__device__ __forceinline__ Coin make_coin(const KParams &p) {
+  if constexpr (Coin::kShared) return Coin{p.coin_common, 0u};
+  else return Coin{};
 }
 
 // ---- the per-node-state write-out of a state launch (one trial)

@@ -101,8 +101,11 @@ export interface TrialsConfig {
    *    iff 2 c_v > N + F, adopt the strict majority v iff c_v > F and decide iff 2 c_v > N + F, else the coin;
    *    byzantineList, byzOne and byzStrategy as in mode 8; without a Byzantine node it still runs this rule),
    *  10, 11 modes 8 and 9 with a shared coin (MODE_BYZ_COIN, MODE_BYZ_RULE_B_COIN: in a common round every honest
-   *    node that takes a coin gets the same bit; coinCommon = 0 is mode 8 or 9 bit for bit) */
-  mode?: 0 | 1 | 2 | 3 | 4 | 5 | 6 | 7 | 8 | 9 | 10 | 11;
+   *    node that takes a coin gets the same bit; coinCommon = 0 is mode 8 or 9 bit for bit),
+   *  12, 13 modes 10 and 11 under an adversarial scheduler (MODE_SCHED_TALLY, MODE_SCHED_RULE_B: the adversary, not
+   *    a draw, picks the N - F messages each honest receiver hears at every step and what the Byzantine senders
+   *    among them say; byzStrategy BYZ_BALANCE or BYZ_SPLIT, byzOne is not read, no Byzantine node is needed) */
+  mode?: 0 | 1 | 2 | 3 | 4 | 5 | 6 | 7 | 8 | 9 | 10 | 11 | 12 | 13;
   /** event mode: deliveries after which node i is stopped (null = never);
    *  MODE_CRASH_TALLY, MODE_CRASH_PARTIAL, MODE_CRASH_SUBSET: the step at which node i crashes (null = never) */
   crashAt?: (number | null)[];
@@ -127,7 +130,7 @@ export interface TrialsConfig {
    *  compact index, 0 to one of even index); the last two do not read byzOne.  It fills the word that crashCount
    *  fills */
   byzStrategy?: 0 | 1 | 3 | 4;
-  /** MODE_BYZ_COIN, MODE_BYZ_RULE_B_COIN: the probability, in units of 2^-32, that a round's coin is common to all
+  /** MODE_BYZ_COIN, MODE_BYZ_RULE_B_COIN, MODE_SCHED_TALLY, MODE_SCHED_RULE_B: the probability, in units of 2^-32, that a round's coin is common to all
    *  honest nodes (0 .. COIN_ALL = 2^32 - 1: certainly), per trial and round; it fills the word that crashWindow fills */
   coinCommon?: number;
 }
@@ -149,6 +152,8 @@ export declare const MODE_BYZ_TALLY: 8;
 export declare const MODE_BYZ_RULE_B: 9;
 export declare const MODE_BYZ_COIN: 10;
 export declare const MODE_BYZ_RULE_B_COIN: 11;
+export declare const MODE_SCHED_TALLY: 12;
+export declare const MODE_SCHED_RULE_B: 13;
 export declare const COIN_ALL: 4294967295;
 /** TrialsConfig.byzStrategy (include/benor.h BO_BYZ_RANDOM, BO_BYZ_OPPOSE, BO_BYZ_BALANCE, BO_BYZ_SPLIT). */
 export declare const BYZ_RANDOM: 0;

@@ -23,7 +23,9 @@ const MODE_LOCKSTEP = 0, MODE_RANDOM_DELIVERY = 1, MODE_EVENT = 2, MODE_RANDOM_T
   MODE_BYZ_TALLY = 8,
   MODE_BYZ_RULE_B = 9,
   MODE_BYZ_COIN = 10,         // modes 8 and 9 with a shared coin: cfg.coinCommon / 2^32 is the probability that a
-  MODE_BYZ_RULE_B_COIN = 11;  // round's coin is common to all honest nodes (COIN_ALL: every round; 0: modes 8 and 9)
+  MODE_BYZ_RULE_B_COIN = 11,  // round's coin is common to all honest nodes (COIN_ALL: every round; 0: modes 8 and 9)
+  MODE_SCHED_TALLY = 12,      // modes 10 and 11 under an adversarial scheduler: it picks the N - F messages each honest
+  MODE_SCHED_RULE_B = 13;     // receiver hears and the lies (cfg.byzStrategy BYZ_BALANCE or BYZ_SPLIT; byzOne is not read)
 const COIN_ALL = 0xFFFFFFFF;
 // runTrials cfg.byzStrategy (MODE_BYZ_TALLY, MODE_BYZ_RULE_B): BO_BYZ_RANDOM, BO_BYZ_OPPOSE, BO_BYZ_BALANCE, BO_BYZ_SPLIT
 const BYZ_RANDOM = 0, BYZ_OPPOSE = 1, BYZ_BALANCE = 3, BYZ_SPLIT = 4;   // (2 is no strategy)
@@ -227,5 +229,5 @@ module.exports = {
   waitConsensus, liveStopEvents, getNodesStateAt,
   MODE_LOCKSTEP, MODE_RANDOM_DELIVERY, MODE_EVENT, MODE_RANDOM_TALLY, MODE_RANDOM_TALLY3, MODE_CRASH_TALLY,
   MODE_CRASH_PARTIAL, CUT_RANDOM, MODE_CRASH_SUBSET, REACH_ALL, MODE_BYZ_TALLY, MODE_BYZ_RULE_B, BYZ_RANDOM, BYZ_OPPOSE, BYZ_BALANCE, BYZ_SPLIT,
-  MODE_BYZ_COIN, MODE_BYZ_RULE_B_COIN, COIN_ALL,
+  MODE_BYZ_COIN, MODE_BYZ_RULE_B_COIN, COIN_ALL, MODE_SCHED_TALLY, MODE_SCHED_RULE_B,
 };

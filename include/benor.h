@@ -266,6 +266,43 @@ enum {
  * rounds, or that sees the coin before it lies; a coin shared by a subset of the
  * nodes; a shared coin in the lockstep, event and crash modes.  Batch API only
  * (no network API; `sweep --mode byz|byzb --coin-common p`). */
+/* SCHED_TALLY is BYZ_COIN word for word, and SCHED_RULE_B is BYZ_RULE_B_COIN word
+ * for word, except for how a receiver's inbox is composed: an
+ * adversarial scheduler, the asynchronous model's adversary, chooses which q = N-F
+ * messages every honest receiver hears at every step, and what each Byzantine
+ * sender among them says.  Who is Byzantine (faulty[i] == 2), crashed
+ * (faulty[i] == 1) and f + b <= F, compact indices over the m = N - f live nodes,
+ * honest nodes alone receiving, Byzantine messages that carry 0 or 1, the init and
+ * coin streams, coin_common in the crash_window word (stream 12; 0: every coin is
+ * local), halting over the honest nodes, the histogram layout, the per-node states
+ * and every validation error are those modes'.  byz_strategy names the scheduler's
+ * aim and must be BO_BYZ_BALANCE or BO_BYZ_SPLIT (anything else is
+ * BO_ERR_INVALID_ARGUMENT); byz_one is not read.  With (H0, H1, Hq) the class sizes
+ * over the honest senders at the step (h = H0 + H1 + Hq >= q, since f + b <= F),
+ * honest receiver c is delivered exactly q messages from distinct senders, honest
+ * ones carrying their true value, and counts
+ *   push(v):  c_v = min(q, H_v + b), rest = q - c_v, c_{1-v} = rest - min(rest, Hq)
+ *     -- the most v that any inbox allows, and then the least 1 - v;
+ *   even():   hq = min(q, Hq), r = q - hq, lo = r - min(r, H1 + b),
+ *     hi = min(r, H0 + b), c0 = clamp((r + (c & 1)) >> 1, lo, hi), c1 = r - c0
+ *     -- "?" messages first, then the two tallies as level as the senders allow:
+ *     the smallest possible larger tally.
+ *   BO_BYZ_SPLIT: push(c & 1) in both phases (odd compact indices driven to 1, even
+ *     ones to 0: the attack on agreement).
+ *   BO_BYZ_BALANCE: even() in both phases (the attack on liveness).
+ * Both counts are realisable by an inbox at every class size, push is
+ * lexicographically extreme and even attains the minimum of max(c0, c1) (checked by
+ * brute force over every inbox for N <= 10).  No word of streams 5, 6, 10 or 11 is
+ * drawn, and the plan holds no threshold table.  b = 0 is valid in both modes and is
+ * NOT another mode's plan: crash-only adversarial scheduling.  coin_common == 0 keeps
+ * the mode (its local-coin kernel).  With f = F and b = 0, m == q and the scheduler has
+ * no choice: SCHED_TALLY then gives RANDOM_TALLY3's histogram and states bit for bit
+ * (BYZ_COIN's at coin_common != 0), SCHED_RULE_B gives BYZ_RULE_B's (BYZ_RULE_B_COIN's).
+ * The two strategies are per-step greedy aims, not the provably optimal attack on
+ * either rule.  Not modelled: a scheduler that holds messages back across rounds
+ * (every step's messages are delivered or dropped within the step), lies that say
+ * "?", an adversary that sees coins before it schedules, crashes during the run.
+ * Batch API only (no network API; `sweep --mode byz|byzb --delivery adversarial`). */
 enum {
   BO_MODE_LOCKSTEP = 0,
   BO_MODE_RANDOM_DELIVERY = 1,
@@ -278,7 +315,9 @@ enum {
   BO_MODE_BYZ_TALLY = 8,
   BO_MODE_BYZ_RULE_B = 9,
   BO_MODE_BYZ_COIN = 10,
-  BO_MODE_BYZ_RULE_B_COIN = 11
+  BO_MODE_BYZ_RULE_B_COIN = 11,
+  BO_MODE_SCHED_TALLY = 12,
+  BO_MODE_SCHED_RULE_B = 13
 };
 
 /* BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B and their shared-coin modes, byz_strategy. */
@@ -429,11 +468,11 @@ typedef struct bo_trials_cfg {
         uint32_t crash_reach; /* CRASH_SUBSET: the probability, in units of 2^-32, that a crasher's last message
                                  reaches a receiver (0: never, UINT32_MAX: certainly); every value is valid */
         uint32_t byz_one;     /* BYZ_TALLY, BYZ_RULE_B, BYZ_COIN, BYZ_RULE_B_COIN: the probability, in units of 2^-32, that a Byzantine message carries 1
-                                 (0: never, UINT32_MAX: certainly); every value is valid */
+                                 (0: never, UINT32_MAX: certainly); every value is valid.  SCHED_TALLY, SCHED_RULE_B: not read */
     };                        /* the other modes ignore it */
     uint64_t seed;            /* Philox4x32-10 key */
     const uint8_t *faulty;    /* host [N]; non-zero = faulty: exactly F set (LOCKSTEP, EVENT), at most F (RANDOM_DELIVERY, RANDOM_TALLY, RANDOM_TALLY3, CRASH_TALLY, CRASH_PARTIAL, CRASH_SUBSET);
-                                 BYZ_TALLY, BYZ_RULE_B, BYZ_COIN and BYZ_RULE_B_COIN alone read the value: 1 crashed from the start, 2 Byzantine, together at most F */
+                                 BYZ_TALLY, BYZ_RULE_B, BYZ_COIN, BYZ_RULE_B_COIN, SCHED_TALLY and SCHED_RULE_B alone read the value: 1 crashed from the start, 2 Byzantine, together at most F */
     const int8_t *init;       /* host [N]; used when init_mode == BO_INIT_FIXED */
     /* EVENT mode: GET /stop schedule.  crash_at[i] = number of deliveries
      * after which node i is stopped (UINT32_MAX = never), or, when crash_at is
@@ -445,15 +484,15 @@ typedef struct bo_trials_cfg {
      * nodes at uniform steps in [0, crash_window), drawn per trial.
      * The other modes ignore the three fields, except that BYZ_TALLY, BYZ_RULE_B, BYZ_COIN and
      * BYZ_RULE_B_COIN read the crash_count word as byz_strategy, and the last two the crash_window
-     * word as coin_common. */
+     * word as coin_common; SCHED_TALLY and SCHED_RULE_B read both words so. */
     const uint32_t *crash_at; /* host [N] or NULL */
     union {                   /* one word, the layout of the struct is that of ABI version 8 */
         uint32_t crash_count;
-        uint32_t byz_strategy; /* BYZ_TALLY, BYZ_RULE_B, BYZ_COIN, BYZ_RULE_B_COIN: a BO_BYZ_* strategy */
+        uint32_t byz_strategy; /* BYZ_TALLY, BYZ_RULE_B, BYZ_COIN, BYZ_RULE_B_COIN: a BO_BYZ_* strategy; SCHED_TALLY, SCHED_RULE_B: BO_BYZ_BALANCE or BO_BYZ_SPLIT */
     };
     union {                   /* one word, the layout of the struct is that of ABI version 8 */
         uint32_t crash_window;
-        uint32_t coin_common; /* BYZ_COIN, BYZ_RULE_B_COIN: the probability, in units of 2^-32, that a round's coin is
+        uint32_t coin_common; /* BYZ_COIN, BYZ_RULE_B_COIN, SCHED_TALLY, SCHED_RULE_B: the probability, in units of 2^-32, that a round's coin is
                                  common to all honest nodes (0: never, UINT32_MAX: certainly); every value is valid */
     };
 } bo_trials_cfg;
@@ -497,7 +536,7 @@ int bo_plan_check(bo_plan *plan);
  * (c0 = M - c1); the P-phase counts c1 when M is odd (no tie, so no "?"
  * proposal: c0 = m - c1) and c0, c1 otherwise -- 2 or 3 x ceil(m/32).
  * RANDOM_DELIVERY: both values in both phases, 4 x ceil(m/32).  RANDOM_TALLY,
- * RANDOM_TALLY3, CRASH_TALLY, CRASH_PARTIAL, CRASH_SUBSET, BYZ_TALLY, BYZ_RULE_B and their shared-coin modes answer RANDOM_DELIVERY's
+ * RANDOM_TALLY3, CRASH_TALLY, CRASH_PARTIAL, CRASH_SUBSET, BYZ_TALLY, BYZ_RULE_B, their shared-coin modes, SCHED_TALLY and SCHED_RULE_B answer RANDOM_DELIVERY's
  * unit, the work they stand in for (the crash modes with m = the initially-live count,
  * BYZ_TALLY and BYZ_RULE_B with m = the live nodes, honest and Byzantine, as bo_plan_live_nodes reports it). */
 uint64_t bo_plan_popc_words_per_node_round(const bo_plan *plan);
@@ -551,7 +590,14 @@ enum {
   BO_KERNEL_TALLY_BYZ_COIN = 16, /* BO_MODE_BYZ_COIN with coin_common != 0, b = 0 included: TALLY_BYZ's two trial loops
                               instantiated with the shared coin (one stream-12 block per round, drawn when an
                               honest node first takes a coin; no per-node coin in a common round) */
-  BO_KERNEL_TALLY_BYZ_B_COIN = 17 /* BO_MODE_BYZ_RULE_B_COIN with coin_common != 0: TALLY_BYZ_B's with the shared coin */
+  BO_KERNEL_TALLY_BYZ_B_COIN = 17, /* BO_MODE_BYZ_RULE_B_COIN with coin_common != 0: TALLY_BYZ_B's with the shared coin */
+  BO_KERNEL_TALLY_SCHED = 18, /* BO_MODE_SCHED_TALLY with an honest node and coin_common == 0: one wave per trial on
+                              TALLY_BYZ's planes; a step's counts are the scheduler's closed form, one pair per
+                              receiver parity, computed wave-uniformly from the popcounted class sizes -- no table,
+                              no search, no walk; what is left per node-round is the rule's ballots and the coins */
+  BO_KERNEL_TALLY_SCHED_B = 19, /* BO_MODE_SCHED_RULE_B with coin_common == 0: the same loop with Protocol B's rule */
+  BO_KERNEL_TALLY_SCHED_COIN = 20, /* BO_MODE_SCHED_TALLY with coin_common != 0: the same loop with the shared coin */
+  BO_KERNEL_TALLY_SCHED_B_COIN = 21 /* BO_MODE_SCHED_RULE_B with coin_common != 0 */
 };
 
 /* The kernel family bo_plan_launch runs for this plan.  (The per-node-state

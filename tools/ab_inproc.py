@@ -68,6 +68,14 @@ the coin policy alone; at `coin_common:all` the rounds per trial differ by desig
     python tools/ab_inproc.py --rounds 5 --reps 3 --shapes "1024,204,100000,0" --variants \
         "m9=mode:byzb,byzantine:16,byz_strategy:split;one=mode:byzb,byzantine:16,byz_strategy:split,coin_common:1;all=mode:byzb,byzantine:16,byz_strategy:split,coin_common:all"
 
+`delivery:adversarial` on mode:byz or mode:byzb with `byz_strategy:balance` or `byz_strategy:split` selects the
+adversarial scheduler's modes (BO_MODE_SCHED_TALLY, BO_MODE_SCHED_RULE_B; `coin_common` stays a variable of
+theirs).  Next to the same line without it, it times the closed-form counts against the inbox-reading entries'
+draws; rounds per trial differ by design, so compare node_rounds_per_s:
+
+    python tools/ab_inproc.py --rounds 5 --reps 3 --shapes "1024,204,100000,0" --variants \
+        "m11=mode:byzb,byzantine:16,byz_strategy:split,coin_common:all;m13=mode:byzb,byzantine:16,byz_strategy:split,coin_common:all,delivery:adversarial"
+
 Every line also reports
 the live node-rounds per second its launches represent (bench.py node_rounds)
 and the rounds a trial ran on average (k_max for an undecided one),
@@ -110,7 +118,7 @@ def main():
         shapes.append((v[0], v[1], v[2], v[3] if len(v) > 3 else v[1]))
     modes = {name: env.pop("mode", None) for name, env in variants}   # `mode` is no environment variable
     scheds = {name: {k: env.pop(k) for k in ("crash_count", "crash_window", "crash_at", "crash_cut", "crash_reach",
-                                             "byzantine", "byz_one", "byz_strategy", "coin_common")
+                                             "byzantine", "byz_one", "byz_strategy", "coin_common", "delivery")
                      if k in env}
               for name, env in variants}                              # ... nor is the crash schedule
     knobs = sorted({k for _, env in variants for k in env})
@@ -127,9 +135,13 @@ def main():
     bad = sorted({v for v in modes.values() if v is not None and v not in mode_ids})
     if bad:
         ap.error(f"mode must be one of {sorted(mode_ids)}: {bad}")
-    byz_keys = ("byzantine", "byz_one", "byz_strategy", "coin_common")
+    byz_keys = ("byzantine", "byz_one", "byz_strategy", "coin_common", "delivery")
     if any(any(k in sc for k in byz_keys) != (modes[name] in ("byz", "byzb")) for name, sc in scheds.items()):
         ap.error("byzantine / byz_one / byz_strategy go with mode:byz or mode:byzb, and they with them")
+    if any(sc.get("delivery", "random") not in ("random", "adversarial") for sc in scheds.values()):
+        ap.error("delivery is random or adversarial")
+    if any(sc.get("delivery") == "adversarial" and sc.get("byz_strategy") not in ("balance", "split") for sc in scheds.values()):
+        ap.error("delivery:adversarial needs byz_strategy:balance or byz_strategy:split")
     if any(any(k not in byz_keys for k in sc) and modes[name] not in ("crash", "partial", "subset")
            for name, sc in scheds.items()):
         ap.error("crash_count / crash_window / crash_at need mode:crash, mode:partial or mode:subset")
@@ -187,6 +199,8 @@ def main():
             mode = mode_ids[modes[name]] if modes[name] else dflt
             if "coin_common" in scheds[name]:
                 mode = benor.BO_MODE_BYZ_COIN if modes[name] == "byz" else benor.BO_MODE_BYZ_RULE_B_COIN
+            if scheds[name].get("delivery") == "adversarial":
+                mode = benor.BO_MODE_SCHED_TALLY if modes[name] == "byz" else benor.BO_MODE_SCHED_RULE_B
             key = (mode, tuple(sorted(scheds[name].items())))
             if key not in plans:
                 plans[key] = benor.TrialsPlan(N, F, [i < f for i in range(N)], seed=0x5EED + N, k_max=32, mode=mode,
