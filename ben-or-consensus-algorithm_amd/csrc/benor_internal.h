@@ -8,6 +8,7 @@
 #include "benor.h"
 #include "benor_mfma_sched.h"
 #include "benor_mfma_strip.h"
+#include "benor_modes.h"
 
 namespace benor {
 
@@ -66,27 +67,12 @@ struct KParams {
                             // 8: packed matrix-core lockstep (2 <= m <= 32, benor_mfma_small.h; the lane kernel
                             //    serves its state launches),
                             // 6: lane lockstep (m <= 64), 1: W-specialised lockstep (W <= kMaxWSpecialised = 32),
-                            // 0: blocked lockstep, 2: random delivery, 4: event level,
-                            // 9: count-level random delivery (benor_tally.hip),
-                            // 10: three-valued count-level random delivery (benor_tally3.hip),
-                            // 11: the same with crashes during the run (benor_tally_crash.hip),
-                            // 12: ... whose last broadcast reaches a prefix of the receivers (benor_tally_partial.hip),
-                            // 13: ... or a random subset of them, receiver by receiver (benor_tally_subset.hip),
-                            // 14: three-valued count-level random delivery with Byzantine senders (benor_tally_byz.hip)
-                            // 15: ... under Ben-Or's Byzantine-tolerant rule (the same file's loops, Protocol B's rule)
-                            // 16, 17: variants 14 and 15 with a shared coin (the same loops, the CoinShared policy)
-                            // 18..21: count-level delivery under an adversarial scheduler (benor_tally_sched.hip):
-                            //         18 the reference's rule, 19 Protocol B's, 20 and 21 the two with a shared coin
+                            // 0: blocked lockstep, 2: random delivery, 4 and 5: event level,
+                            // 9..21: the count-level kernels (benor_modes.h: kVar* and the variant_* predicates)
   uint32_t base_variant;    // variant 7: the popcount kernel (1 W, 0 blocked) that serves the state
   uint32_t base_G;          //   launches and the deferred trials, and its G
-  uint32_t mode;            // BO_MODE_LOCKSTEP / BO_MODE_RANDOM_DELIVERY / BO_MODE_EVENT / BO_MODE_RANDOM_TALLY /
-                            // BO_MODE_RANDOM_TALLY3 / BO_MODE_CRASH_TALLY (a BO_MODE_RANDOM_TALLY3 plan inside
-                            // mode 3's scope holds BO_MODE_RANDOM_TALLY here: it is that mode's plan; a
-                            // BO_MODE_CRASH_TALLY, BO_MODE_CRASH_PARTIAL or BO_MODE_CRASH_SUBSET plan with an empty
-                            // schedule is BO_MODE_RANDOM_TALLY3's, and so is a BO_MODE_BYZ_TALLY plan without a
-                            // Byzantine node; a BO_MODE_BYZ_RULE_B plan keeps its mode at b = 0; a BO_MODE_BYZ_COIN
-                            // or BO_MODE_BYZ_RULE_B_COIN plan with coin_common = 0 is its parent mode's plan;
-                            // a BO_MODE_SCHED_TALLY or BO_MODE_SCHED_RULE_B plan always keeps its mode)
+  uint32_t mode;            // BO_MODE_* of the plan: the configuration's, or the mode whose plan it is (the
+                            // demotions of plan_host, benor_runtime.cpp; modes and families: benor_modes.h)
   uint32_t q;               // quorum N - F (messages each receiver tallies per phase)
   uint32_t k_max;
   uint32_t init_mode;       // BO_INIT_RANDOM / BO_INIT_FIXED

@@ -587,6 +587,41 @@ __global__ void __launch_bounds__(256) popc_peak_kernel(uint32_t *sink, int iter
 }
 
 // ------------------------------------------------------------ host side
+// The count-level kernels' host entry points, one row per file: the variants it serves, its launch, its
+// occupancy query (0 = unknown) and the per-wave LDS bytes of a batch launch in its layout
+// (benor_tally_common.h).  plan_geometry, launch_lockstep and lockstep_grid walk it.
+struct CountLevelKernel {
+  uint32_t first, last;
+  hipError_t (*launch)(const KParams &, int, hipStream_t);
+  int (*blocks_per_cu)(const KParams &);
+  uint32_t (*wave_bytes)(const KParams &);
+};
+static uint32_t tally_bytes(const KParams &p) { return tally_wave_bytes(p.W, p.tally_cap); }
+static uint32_t crash_bytes(const KParams &p) { return crash_wave_bytes(p.W, p.tally_cap, p.cr_n, p.cr_random != 0u, false); }
+static uint32_t crash_list_bytes(const KParams &p) { return crash_wave_bytes(p.W, p.tally_cap, p.cr_n, p.cr_random != 0u, true); }
+static uint32_t byz_bytes(const KParams &p) { return byz_wave_bytes(p.W, p.tally_cap); }   // (the scheduler: tally_cap 0)
+constexpr CountLevelKernel kCountLevel[] = {
+    {kVarTally, kVarTally, launch_tally, tally_blocks_per_cu, tally_bytes},
+    {kVarTally3, kVarTally3, launch_tally3, tally3_blocks_per_cu, tally_bytes},
+    {kVarCrash, kVarCrash, launch_tally_crash, crash_blocks_per_cu, crash_bytes},
+    {kVarPartial, kVarPartial, launch_tally_partial, partial_blocks_per_cu, crash_list_bytes},
+    {kVarSubset, kVarSubset, launch_tally_subset, subset_blocks_per_cu, crash_list_bytes},
+    {kVarByz, kVarSched - 1u, launch_tally_byz, byz_blocks_per_cu, byz_bytes},             // rule and coin: its entries
+    {kVarSched, kVarCountLevelEnd - 1u, launch_tally_sched, sched_blocks_per_cu, byz_bytes},
+};
+
+constexpr const CountLevelKernel *count_level_kernel(uint32_t variant) {
+  for (const CountLevelKernel &k : kCountLevel)
+    if (variant >= k.first && variant <= k.last) return &k;
+  return nullptr;
+}
+constexpr bool count_level_covered() {
+  for (uint32_t v = kVarTally; v < kVarCountLevelEnd; ++v)
+    if (!count_level_kernel(v)) return false;
+  return true;
+}
+static_assert(count_level_covered(), "a count-level variant without a row: plan_geometry reads its row");
+
 void plan_geometry(KParams &p) {
   const uint32_t W = p.W;
   p.hist_len = (p.k_max + 1u) * 3u + 1u;
@@ -644,46 +679,22 @@ void plan_geometry(KParams &p) {
     p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
     return;
   }
-  if (p.mode == BO_MODE_RANDOM_TALLY || p.mode == BO_MODE_RANDOM_TALLY3 || p.mode == BO_MODE_CRASH_TALLY ||
-      p.mode == BO_MODE_CRASH_PARTIAL || p.mode == BO_MODE_CRASH_SUBSET || p.mode == BO_MODE_BYZ_TALLY ||
-      p.mode == BO_MODE_BYZ_RULE_B || p.mode == BO_MODE_BYZ_COIN || p.mode == BO_MODE_BYZ_RULE_B_COIN) {
+  if (const ModeTraits &mode = *mode_traits(p.mode); mode.is(kModeCountLevel)) {   // (plan_host checked the mode)
     // The count-level kernels (benor_tally*.hip; layouts: benor_tally_common.h).  The row region is the
     // widest row of HG(m, ., q): no pool of the crash family exceeds m0, and the Byzantine kernels run on
-    // mode 4's table.
+    // mode 4's table.  The adversarial scheduler has the Byzantine kernels' planes and nothing else: no row
+    // region (tally_cap stays 0: there is no table) and no thresholds behind the waves' regions.
     p.G = 1;
     p.nblocks = W;
     const uint32_t e = p.m - p.q;
-    p.tally_cap = p.q <= e ? p.q : e;
-    const bool random = p.cr_random != 0u;
-    uint32_t bytes;
-    switch (p.mode) {
-      case BO_MODE_RANDOM_TALLY: p.variant = 9u, bytes = tally_wave_bytes(W, p.tally_cap); break;
-      case BO_MODE_RANDOM_TALLY3: p.variant = 10u, bytes = tally_wave_bytes(W, p.tally_cap); break;
-      case BO_MODE_CRASH_TALLY: p.variant = 11u, bytes = crash_wave_bytes(W, p.tally_cap, p.cr_n, random, false); break;
-      case BO_MODE_CRASH_PARTIAL: p.variant = 12u, bytes = crash_wave_bytes(W, p.tally_cap, p.cr_n, random, true); break;
-      case BO_MODE_CRASH_SUBSET: p.variant = 13u, bytes = crash_wave_bytes(W, p.tally_cap, p.cr_n, random, true); break;
-      case BO_MODE_BYZ_TALLY: p.variant = 14u, bytes = byz_wave_bytes(W, p.tally_cap); break;
-      case BO_MODE_BYZ_RULE_B: p.variant = 15u, bytes = byz_wave_bytes(W, p.tally_cap); break;   // variant 14's layout
-      case BO_MODE_BYZ_COIN: p.variant = 16u, bytes = byz_wave_bytes(W, p.tally_cap); break;     // (and the shared-coin entries')
-      default: p.variant = 17u, bytes = byz_wave_bytes(W, p.tally_cap); break;                   // BO_MODE_BYZ_RULE_B_COIN
-    }
-    p.wave_bytes = (bytes + 15u) & ~15u;
+    p.tally_cap = mode.is(kModeSched) ? 0u : (p.q <= e ? p.q : e);
+    p.variant = count_level_variant(p.mode, p.coin_common != 0u);
+    p.wave_bytes = (count_level_kernel(p.variant)->wave_bytes(p) + 15u) & ~15u;
     p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
-    if (p.variant >= 14u && p.variant <= 17u) {   // the Binomial thresholds ride in LDS when that costs no resident workgroup
+    if (variant_byz(p.variant)) {   // the Binomial thresholds ride in LDS when that costs no resident workgroup
       p.byz_lds = p.byz_n != 0u && !byz_heard(p) && byz_thr_in_lds(p.lds_bytes, p.byz_n) ? 1u : 0u;   // (the inbox-reading strategies and b = 0 have none)
       if (p.byz_lds) p.lds_bytes += 8u * p.byz_n;
     }
-    return;
-  }
-  if (p.mode == BO_MODE_SCHED_TALLY || p.mode == BO_MODE_SCHED_RULE_B) {
-    // The adversarial scheduler (benor_tally_sched.hip): the Byzantine kernels' planes and nothing else -- no
-    // row region (tally_cap stays 0: there is no table) and no thresholds behind the waves' regions.
-    p.G = 1;
-    p.nblocks = W;
-    p.tally_cap = 0u;
-    p.variant = 18u + (p.mode == BO_MODE_SCHED_RULE_B ? 1u : 0u) + (p.coin_common != 0u ? 2u : 0u);
-    p.wave_bytes = (byz_wave_bytes(W, 0u) + 15u) & ~15u;
-    p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
     return;
   }
   if (p.m <= kMaxLaneM) {                           // lane kernel: one trial per lane
@@ -817,13 +828,10 @@ hipError_t launch_lockstep(const KParams &p, int grid, hipStream_t s) {
     q.lds_bytes = q.hist_bytes + kWavesPerBlock * q.wave_bytes;
     return launch_lockstep(q, grid, s);
   }
-  if (p.variant == 9) return launch_tally(p, grid, s);
-  if (p.variant == 10) return launch_tally3(p, grid, s);
-  if (p.variant == 11) return launch_tally_crash(p, grid, s);
-  if (p.variant == 12) return launch_tally_partial(p, grid, s);
-  if (p.variant == 13) return launch_tally_subset(p, grid, s);
-  if (p.variant >= 14 && p.variant <= 17) return launch_tally_byz(p, grid, s);
-  if (p.variant >= 18 && p.variant <= 21) return launch_tally_sched(p, grid, s);
+  if (variant_count_level(p.variant)) {
+    const CountLevelKernel *k = count_level_kernel(p.variant);
+    return k ? k->launch(p, grid, s) : hipErrorInvalidValue;
+  }
   if (p.variant == 2 && p.rd_a) return launch_random_bern(p, grid, s);
   if (p.variant == 2) {                      // Floyd sampler
     if (p.lds_bytes > 64u * 1024u) {
@@ -913,17 +921,10 @@ uint32_t mfma_chunk(const KParams &p, int device) {
   return c;
 }
 
-// Resident workgroups per CU of the count-level kernel of variant 9..21 (0 = unknown).
+// Resident workgroups per CU of a count-level variant's kernel (0 = unknown).
 static int count_level_blocks_per_cu(const KParams &p) {
-  switch (p.variant) {
-    case 9: return tally_blocks_per_cu(p);
-    case 10: return tally3_blocks_per_cu(p);
-    case 11: return crash_blocks_per_cu(p);
-    case 12: return partial_blocks_per_cu(p);
-    case 13: return subset_blocks_per_cu(p);
-    case 18: case 19: case 20: case 21: return sched_blocks_per_cu(p);
-    default: return byz_blocks_per_cu(p);
-  }
+  const CountLevelKernel *k = count_level_kernel(p.variant);
+  return k ? k->blocks_per_cu(p) : 0;
 }
 
 int lockstep_grid(const KParams &p, int device) {
@@ -985,7 +986,7 @@ int lockstep_grid(const KParams &p, int device) {
     const uint64_t lds_fit = lds_groups_per_cu(lds);
     if (lds_fit < per_cu) per_cu = lds_fit ? lds_fit : 1;
   }
-  if (p.variant >= 9 && p.variant <= 21) {   // the count-level kernels are register-bound (benor_tally.hip: per unroll)
+  if (variant_count_level(p.variant)) {   // the count-level kernels are register-bound (benor_tally.hip: per unroll)
     const uint64_t fit = (uint64_t)count_level_blocks_per_cu(p);
     if (fit >= 1u && fit < per_cu) per_cu = fit;
   }

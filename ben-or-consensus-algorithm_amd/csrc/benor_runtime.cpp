@@ -543,15 +543,26 @@ int bo_byz_cdf(uint32_t b, uint32_t byz_one, uint64_t *thr_out, uint32_t cap, ui
 // -------------------------------------------------------------- batch API
 // Validation and kernel planning of a trial configuration, host only: the
 // live-node map, the fixed-init plane and the KParams shape (no device fields).
-// BO_MODE_CRASH_TALLY, host side of a non-empty schedule: the explicit list
+// Which words a mode reads and which family it belongs to: benor_modes.h.
+// plan_host is the common part; a family's own checks and plan are entered on
+// its traits flag (check_ / plan_crash_family, check_ / plan_byz_family: the
+// checks run where they always did, so the first error of a configuration is
+// the one it was).
+using benor::ModeTraits;
+using benor::mode_traits;
+
+// The crash family, host side of a non-empty schedule: the explicit list
 // (step << 12 | compact index, ascending, steps below 2 k_max: no run reaches a
 // later one) and, per number of crashes so far d = 0 .. kp.cr_n, whether the
 // live count m0 - d is reachable and so needs a table.
-// BO_MODE_BYZ_TALLY with Byzantine nodes: the honest plane, bit c of word c / 64 set for
-// an honest compact index c.
-struct CrashPlan {
+struct CrashSchedule {
   std::vector<uint32_t> list;
   std::vector<uint8_t> reach;
+};
+// What a plan uploads besides the live map and the init plane: the schedule, and the Byzantine
+// family's honest plane, bit c of word c / 64 set for an honest compact index c.
+struct PlanTables {
+  CrashSchedule crash;
   std::vector<uint64_t> honest;
 };
 
@@ -562,53 +573,113 @@ static uint64_t tally_table_len(uint32_t m, uint32_t q) {
   return n;
 }
 
+// The Byzantine family alone reads the value of a faulty entry: 1 crashed from the start, 2 Byzantine
+// (live: it sends); every other mode reads non-zero as faulty.  Under an adversarial scheduler the
+// strategy names the scheduler's aim.
+static int check_byz_family(const bo_trials_cfg *cfg, const ModeTraits &mode) {
+  for (uint32_t i = 0; i < cfg->N; ++i)
+    if (cfg->faulty[i] > 2u)
+      return fail(BO_ERR_INVALID_ARGUMENT, std::string(mode.name) + ": a faulty entry is 0, 1 (crashed) or 2 (Byzantine)");
+  const bool inbox = cfg->byz_strategy == BO_BYZ_BALANCE || cfg->byz_strategy == BO_BYZ_SPLIT;
+  if (!inbox && cfg->byz_strategy != BO_BYZ_RANDOM && cfg->byz_strategy != BO_BYZ_OPPOSE)
+    return fail(BO_ERR_INVALID_ARGUMENT,
+                "byz_strategy must be BO_BYZ_RANDOM, BO_BYZ_OPPOSE, BO_BYZ_BALANCE or BO_BYZ_SPLIT");
+  if (mode.is(benor::kModeSched) && !inbox)
+    return fail(BO_ERR_INVALID_ARGUMENT,
+                "byz_strategy must be BO_BYZ_BALANCE or BO_BYZ_SPLIT under an adversarial scheduler "
+                "(BO_MODE_SCHED_TALLY, BO_MODE_SCHED_RULE_B)");
+  return BO_OK;
+}
+
+// Crashes during the run: with the f initially faulty nodes at most F, so every step has a quorum of
+// live senders.  n_crash: the nodes scheduled; random: crash_count of them drawn per trial.
+static int check_crash_family(const bo_trials_cfg *cfg, const ModeTraits &mode, const std::vector<uint32_t> &live,
+                              uint32_t f, uint64_t &n_crash, bool &random) {
+  const uint32_t m = (uint32_t)live.size();
+  if (cfg->crash_at) {
+    for (uint32_t c = 0; c < m; ++c) n_crash += cfg->crash_at[live[c]] != 0xFFFFFFFFu ? 1u : 0u;
+  } else if (cfg->crash_count > 0) {
+    if (cfg->crash_window < 1) return fail(BO_ERR_INVALID_ARGUMENT, "crash_count > 0 needs crash_window >= 1");
+    n_crash = cfg->crash_count;
+    random = true;
+  }
+  if ((uint64_t)f + n_crash > cfg->F)
+    return fail(BO_ERR_FAULTY_COUNT, std::string(mode.name) + " needs at most F nodes faulty or scheduled to crash");
+  // Partial broadcasts: a cut counts initially-live receivers
+  // (BO_MODE_CRASH_SUBSET reads the word as crash_reach, a probability in units of 2^-32: every value is one)
+  if (cfg->mode == BO_MODE_CRASH_PARTIAL && cfg->crash_cut != BO_CUT_RANDOM && cfg->crash_cut > m)
+    return fail(BO_ERR_INVALID_ARGUMENT, "crash_cut must be at most the initially-live count N - f, or BO_CUT_RANDOM");
+  return BO_OK;
+}
+
+// A crash-family plan with a non-empty schedule: the list, the reachable live counts, the table limit.
+static int plan_crash_family(const bo_trials_cfg *cfg, const std::vector<uint32_t> &live, uint64_t n_crash, bool random,
+                             benor::KParams &kp, CrashSchedule &cs) {
+  const uint32_t m = kp.m;
+  cs.list.clear();
+  kp.cr_random = random ? 1u : 0u;
+  kp.cr_cut = kp.mode == BO_MODE_CRASH_PARTIAL ? cfg->crash_cut : 0u;
+  if (kp.mode == BO_MODE_CRASH_SUBSET) kp.cr_reach = cfg->crash_reach;
+  if (random) {
+    kp.cr_n = (uint32_t)n_crash;
+    cs.reach.assign(kp.cr_n + 1u, 1);            // every m0 - j, j = 0 .. crash_count
+  } else {
+    for (uint32_t c = 0; c < m; ++c) {
+      const uint32_t s = cfg->crash_at[live[c]];
+      if (s != 0xFFFFFFFFu && (uint64_t)s < 2ull * cfg->k_max) cs.list.push_back(s << 12 | c);
+    }
+    std::sort(cs.list.begin(), cs.list.end());
+    kp.cr_n = (uint32_t)cs.list.size();
+    cs.reach.assign(kp.cr_n + 1u, 0);            // m0 minus the cumulative crashes at each distinct step
+    cs.reach[0] = 1;
+    for (uint32_t i = 0; i < kp.cr_n; ++i)
+      if (i + 1u == kp.cr_n || (cs.list[i + 1u] >> 12) != (cs.list[i] >> 12)) cs.reach[i + 1u] = 1;
+    // Partial broadcasts: a receiver's pool is the alive set and the step's crashers that reach
+    // it.  A fixed cut gives all of them or none, live counts of the set above; random cuts
+    // any number of them, so every m0 - j
+    if (kp.mode == BO_MODE_CRASH_PARTIAL && kp.cr_cut == BO_CUT_RANDOM) cs.reach.assign(kp.cr_n + 1u, 1);
+    // A random subset: any number of a step's crashers may reach a receiver, every m0 - j (at reach
+    // 0 and UINT32_MAX too: one rule for the mode)
+    if (kp.mode == BO_MODE_CRASH_SUBSET) cs.reach.assign(kp.cr_n + 1u, 1);
+  }
+  uint64_t bytes = 0;
+  for (uint32_t d = 0; d <= kp.cr_n; ++d)
+    if (cs.reach[d]) bytes += 8ull * tally_table_len(m - d, kp.q);
+  if (bytes > BO_CRASH_TABLE_MAX_BYTES)
+    return fail(BO_ERR_UNSUPPORTED,
+                std::string(mode_traits(kp.mode)->name) + ": the threshold tables of the reachable " +
+                    (kp.mode == BO_MODE_CRASH_TALLY ? "live counts" : "pool sizes") +
+                    " exceed the 512 MiB limit (BO_CRASH_TABLE_MAX_BYTES): schedule fewer crashes");
+  return BO_OK;
+}
+
+// A Byzantine-family plan: the strategy words and the honest plane.
+static void plan_byz_family(const bo_trials_cfg *cfg, const std::vector<uint32_t> &live, uint32_t nbyz,
+                            benor::KParams &kp, std::vector<uint64_t> *honest) {
+  kp.byz_n = nbyz;
+  kp.byz_strategy = cfg->byz_strategy;
+  kp.byz_one = cfg->byz_one;
+  if (!honest) return;
+  honest->assign(kp.W, 0ull);
+  for (uint32_t c = 0; c < kp.m; ++c)
+    if (cfg->faulty[live[c]] == 0u) (*honest)[c >> 6] |= 1ull << (c & 63u);
+}
+
 static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std::vector<uint4> &plane,
-                     benor::KParams &kp, bool live_run = false, CrashPlan *crash = nullptr) {
+                     benor::KParams &kp, bool live_run = false, PlanTables *tables = nullptr) {
   if (!cfg) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
   if (cfg->N < 1 || cfg->N > BO_MAX_N) return fail(BO_ERR_UNSUPPORTED, "N must be in [1, 4096]");
   if (cfg->k_max < 1 || cfg->k_max > BO_MAX_K) return fail(BO_ERR_INVALID_ARGUMENT, "k_max must be in [1, 1024]");
-  if (cfg->mode != BO_MODE_LOCKSTEP && cfg->mode != BO_MODE_RANDOM_DELIVERY && cfg->mode != BO_MODE_EVENT &&
-      cfg->mode != BO_MODE_RANDOM_TALLY && cfg->mode != BO_MODE_RANDOM_TALLY3 && cfg->mode != BO_MODE_CRASH_TALLY &&
-      cfg->mode != BO_MODE_CRASH_PARTIAL && cfg->mode != BO_MODE_CRASH_SUBSET && cfg->mode != BO_MODE_BYZ_TALLY &&
-      cfg->mode != BO_MODE_BYZ_RULE_B && cfg->mode != BO_MODE_BYZ_COIN && cfg->mode != BO_MODE_BYZ_RULE_B_COIN &&
-      cfg->mode != BO_MODE_SCHED_TALLY && cfg->mode != BO_MODE_SCHED_RULE_B)
-    return fail(BO_ERR_UNSUPPORTED, "unknown delivery mode");
-  // BO_MODE_SCHED_TALLY and BO_MODE_SCHED_RULE_B: BO_MODE_BYZ_COIN's and BO_MODE_BYZ_RULE_B_COIN's configuration and
-  // validation; the strategy names the scheduler's aim, and the plan keeps its mode at b = 0 and at coin_common = 0
-  const bool sched_mode = cfg->mode == BO_MODE_SCHED_TALLY || cfg->mode == BO_MODE_SCHED_RULE_B;
-  // BO_MODE_BYZ_COIN and BO_MODE_BYZ_RULE_B_COIN: their parent modes' configuration and validation; the crash_window word is coin_common
-  const bool coin_mode = cfg->mode == BO_MODE_BYZ_COIN || cfg->mode == BO_MODE_BYZ_RULE_B_COIN || sched_mode;
-  const bool rule_b = cfg->mode == BO_MODE_BYZ_RULE_B || cfg->mode == BO_MODE_BYZ_RULE_B_COIN ||
-                      cfg->mode == BO_MODE_SCHED_RULE_B;   // BO_MODE_BYZ_TALLY's configuration and validation, another rule
-  const bool byz_mode = cfg->mode == BO_MODE_BYZ_TALLY || cfg->mode == BO_MODE_BYZ_COIN || rule_b || sched_mode;
-  const bool crash_mode = cfg->mode == BO_MODE_CRASH_TALLY || cfg->mode == BO_MODE_CRASH_PARTIAL ||
-                          cfg->mode == BO_MODE_CRASH_SUBSET;
-  const bool random_mode = cfg->mode == BO_MODE_RANDOM_DELIVERY || cfg->mode == BO_MODE_RANDOM_TALLY ||
-                           cfg->mode == BO_MODE_RANDOM_TALLY3 || crash_mode || byz_mode;
+  const ModeTraits *mode = mode_traits(cfg->mode);
+  if (!mode) return fail(BO_ERR_UNSUPPORTED, "unknown delivery mode");
+  const bool byz_mode = mode->is(benor::kModeByz), coin_mode = mode->is(benor::kModeCoin);
   if (cfg->init_mode != BO_INIT_RANDOM && cfg->init_mode != BO_INIT_FIXED)
     return fail(BO_ERR_INVALID_ARGUMENT, "unknown init_mode");
   if (!cfg->faulty) return fail(BO_ERR_INVALID_ARGUMENT, "faulty is NULL");
   if (cfg->init_mode == BO_INIT_FIXED && !cfg->init) return fail(BO_ERR_INVALID_ARGUMENT, "init is NULL");
-  // BO_MODE_BYZ_TALLY and BO_MODE_BYZ_RULE_B alone read the value of a faulty entry: 1 crashed from
-  // the start, 2 Byzantine (live: it sends); every other mode reads non-zero as faulty.
   if (byz_mode) {
-    for (uint32_t i = 0; i < cfg->N; ++i)
-      if (cfg->faulty[i] > 2u)
-        return fail(BO_ERR_INVALID_ARGUMENT,
-                    cfg->mode == BO_MODE_SCHED_RULE_B    ? "BO_MODE_SCHED_RULE_B: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)"
-                    : cfg->mode == BO_MODE_SCHED_TALLY   ? "BO_MODE_SCHED_TALLY: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)"
-                    : cfg->mode == BO_MODE_BYZ_RULE_B_COIN ? "BO_MODE_BYZ_RULE_B_COIN: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)"
-                    : cfg->mode == BO_MODE_BYZ_COIN      ? "BO_MODE_BYZ_COIN: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)"
-                    : rule_b                             ? "BO_MODE_BYZ_RULE_B: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)"
-                                                         : "BO_MODE_BYZ_TALLY: a faulty entry is 0, 1 (crashed) or 2 (Byzantine)");
-    if (cfg->byz_strategy != BO_BYZ_RANDOM && cfg->byz_strategy != BO_BYZ_OPPOSE && cfg->byz_strategy != BO_BYZ_BALANCE &&
-        cfg->byz_strategy != BO_BYZ_SPLIT)
-      return fail(BO_ERR_INVALID_ARGUMENT,
-                  "byz_strategy must be BO_BYZ_RANDOM, BO_BYZ_OPPOSE, BO_BYZ_BALANCE or BO_BYZ_SPLIT");
-    if (sched_mode && cfg->byz_strategy != BO_BYZ_BALANCE && cfg->byz_strategy != BO_BYZ_SPLIT)
-      return fail(BO_ERR_INVALID_ARGUMENT,
-                  "byz_strategy must be BO_BYZ_BALANCE or BO_BYZ_SPLIT under an adversarial scheduler "
-                  "(BO_MODE_SCHED_TALLY, BO_MODE_SCHED_RULE_B)");
+    const int rc = check_byz_family(cfg, *mode);
+    if (rc) return rc;
   }
   const auto crashed = [&](uint32_t i) { return byz_mode ? cfg->faulty[i] == 1u : cfg->faulty[i] != 0u; };
   uint32_t f = 0, nbyz = 0;
@@ -618,43 +689,21 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   }
   // Lockstep = the reference's admissible inputs: exactly F crash faults
   // (launchNodes.ts:12-13).  Random delivery admits f <= F.
-  if (!random_mode && f != cfg->F)
+  if (!mode->is(benor::kModeRandom) && f != cfg->F)
     return fail(BO_ERR_FAULTY_COUNT, "faultyList doesnt have F faulties");
-  if (random_mode && f > cfg->F)
+  if (mode->is(benor::kModeRandom) && f > cfg->F)
     return fail(BO_ERR_FAULTY_COUNT, "random delivery needs at most F crash-faulty nodes");
   if (f + nbyz > cfg->F)
-    return fail(BO_ERR_FAULTY_COUNT,
-                cfg->mode == BO_MODE_SCHED_RULE_B    ? "BO_MODE_SCHED_RULE_B needs at most F nodes crashed or Byzantine"
-                : cfg->mode == BO_MODE_SCHED_TALLY   ? "BO_MODE_SCHED_TALLY needs at most F nodes crashed or Byzantine"
-                : cfg->mode == BO_MODE_BYZ_RULE_B_COIN ? "BO_MODE_BYZ_RULE_B_COIN needs at most F nodes crashed or Byzantine"
-                : cfg->mode == BO_MODE_BYZ_COIN      ? "BO_MODE_BYZ_COIN needs at most F nodes crashed or Byzantine"
-                : rule_b                             ? "BO_MODE_BYZ_RULE_B needs at most F nodes crashed or Byzantine"
-                                                     : "BO_MODE_BYZ_TALLY needs at most F nodes crashed or Byzantine");
+    return fail(BO_ERR_FAULTY_COUNT, std::string(mode->name) + " needs at most F nodes crashed or Byzantine");
   live.clear();
   for (uint32_t i = 0; i < cfg->N; ++i)
     if (!crashed(i)) live.push_back(i);
   const uint32_t m = (uint32_t)live.size();
-  // Crashes during the run (BO_MODE_CRASH_TALLY, BO_MODE_CRASH_PARTIAL, BO_MODE_CRASH_SUBSET): with
-  // the initially faulty nodes at most F, so every step has a quorum of live senders.
   uint64_t n_crash = 0;
   bool crash_random = false;
-  if (crash_mode) {
-    if (cfg->crash_at) {
-      for (uint32_t c = 0; c < m; ++c) n_crash += cfg->crash_at[live[c]] != 0xFFFFFFFFu ? 1u : 0u;
-    } else if (cfg->crash_count > 0) {
-      if (cfg->crash_window < 1) return fail(BO_ERR_INVALID_ARGUMENT, "crash_count > 0 needs crash_window >= 1");
-      n_crash = cfg->crash_count;
-      crash_random = true;
-    }
-    if ((uint64_t)f + n_crash > cfg->F)
-      return fail(BO_ERR_FAULTY_COUNT,
-                  cfg->mode == BO_MODE_CRASH_TALLY     ? "BO_MODE_CRASH_TALLY needs at most F nodes faulty or scheduled to crash"
-                  : cfg->mode == BO_MODE_CRASH_PARTIAL ? "BO_MODE_CRASH_PARTIAL needs at most F nodes faulty or scheduled to crash"
-                                                       : "BO_MODE_CRASH_SUBSET needs at most F nodes faulty or scheduled to crash");
-    // Partial broadcasts: a cut counts initially-live receivers
-    if (cfg->mode == BO_MODE_CRASH_PARTIAL && cfg->crash_cut != BO_CUT_RANDOM && cfg->crash_cut > m)
-      return fail(BO_ERR_INVALID_ARGUMENT, "crash_cut must be at most the initially-live count N - f, or BO_CUT_RANDOM");
-    // (BO_MODE_CRASH_SUBSET reads the word as crash_reach, a probability in units of 2^-32: every value is one)
+  if (mode->is(benor::kModeCrash)) {
+    const int rc = check_crash_family(cfg, *mode, live, f, n_crash, crash_random);
+    if (rc) return rc;
   }
   kp = benor::KParams{};
   kp.N = cfg->N;
@@ -665,12 +714,13 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   kp.init_mode = cfg->init_mode;
   kp.seed = cfg->seed;
   kp.mode = cfg->mode;
-  // A shared-coin plan whose rounds are never common is its parent mode's plan; otherwise it carries the word.
-  if (coin_mode && !sched_mode && cfg->coin_common == 0u) kp.mode = rule_b ? BO_MODE_BYZ_RULE_B : BO_MODE_BYZ_TALLY;
+  // A shared-coin plan whose rounds are never common is its parent mode's plan (under a scheduler: its own);
+  // otherwise it carries the word.
+  if (coin_mode && cfg->coin_common == 0u) kp.mode = mode->coin_parent;
   if (coin_mode) kp.coin_common = cfg->coin_common;
   kp.q = cfg->N - cfg->F;
-  kp.crash_count = byz_mode ? 0u : cfg->crash_count;   // (BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B: the word is byz_strategy)
-  kp.crash_window = coin_mode ? 0u : cfg->crash_window;   // (BO_MODE_BYZ_COIN, BO_MODE_BYZ_RULE_B_COIN: the word is coin_common)
+  kp.crash_count = byz_mode ? 0u : cfg->crash_count;      // (the Byzantine family: the word is byz_strategy)
+  kp.crash_window = coin_mode ? 0u : cfg->crash_window;   // (the shared-coin modes: the word is coin_common)
   if (cfg->mode == BO_MODE_EVENT && !cfg->crash_at && cfg->crash_count > 0 && cfg->crash_window > 0)
     kp.ev_rstops = std::min<uint32_t>(cfg->crash_count, m);   // per-trial random /stop schedule
   kp.live = live_run && cfg->mode == BO_MODE_EVENT ? 1u : 0u;
@@ -702,68 +752,21 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
     return fail(BO_ERR_UNSUPPORTED, "BO_MODE_RANDOM_TALLY needs an odd quorum N - F: use BO_MODE_RANDOM_DELIVERY");
   if (cfg->mode == BO_MODE_RANDOM_TALLY && kp.init_q)
     return fail(BO_ERR_UNSUPPORTED, "BO_MODE_RANDOM_TALLY takes no \"?\" initial value: use BO_MODE_RANDOM_DELIVERY");
-  // The three-valued mode is a superset: inside that scope it is that mode's plan
-  // (its kernel, its results bit for bit); outside, benor_tally3.hip.
-  // A BO_MODE_CRASH_TALLY plan with an empty schedule is the three-valued mode's plan.
-  if (crash_mode && n_crash == 0) kp.mode = BO_MODE_RANDOM_TALLY3;
+  // The demotions, in this order (the order decides the plan; a shared-coin mode became its parent
+  // above).  A crash-family plan with an empty schedule is the three-valued mode's plan,
+  if (mode->is(benor::kModeCrash) && n_crash == 0) kp.mode = BO_MODE_RANDOM_TALLY3;
   // ... and so is a BO_MODE_BYZ_TALLY plan without a Byzantine node, at every byz_one and strategy
-  // (BO_MODE_BYZ_RULE_B keeps its plan: the rule differs).
-  // (a shared coin keeps its plan at b = 0: mode 4 has no such coin)
+  // (the other rule keeps its plan: the rule differs; a shared coin keeps its plan at b = 0: mode 4
+  // has no such coin; so does a scheduler)
   if (kp.mode == BO_MODE_BYZ_TALLY && nbyz == 0) kp.mode = BO_MODE_RANDOM_TALLY3;
-  if (kp.mode == BO_MODE_BYZ_TALLY || kp.mode == BO_MODE_BYZ_RULE_B || kp.mode == BO_MODE_BYZ_COIN ||
-      kp.mode == BO_MODE_BYZ_RULE_B_COIN || sched_mode) {
-    kp.byz_n = nbyz;
-    kp.byz_strategy = cfg->byz_strategy;
-    kp.byz_one = cfg->byz_one;
-    if (crash) {
-      crash->honest.assign(kp.W, 0ull);
-      for (uint32_t c = 0; c < m; ++c)
-        if (cfg->faulty[live[c]] == 0u) crash->honest[c >> 6] |= 1ull << (c & 63u);
-    }
-  }
+  if (mode_traits(kp.mode)->is(benor::kModeByz)) plan_byz_family(cfg, live, nbyz, kp, tables ? &tables->honest : nullptr);
+  // The three-valued mode is a superset of the two-valued one: inside that scope it is that mode's
+  // plan (its kernel, its results bit for bit); outside, benor_tally3.hip.
   if (kp.mode == BO_MODE_RANDOM_TALLY3 && (kp.q & 1u) && !kp.init_q) kp.mode = BO_MODE_RANDOM_TALLY;
-  if (kp.mode == BO_MODE_CRASH_TALLY || kp.mode == BO_MODE_CRASH_PARTIAL || kp.mode == BO_MODE_CRASH_SUBSET) {
-    CrashPlan local;
-    CrashPlan &cp = crash ? *crash : local;
-    cp.list.clear();
-    kp.cr_random = crash_random ? 1u : 0u;
-    kp.cr_cut = kp.mode == BO_MODE_CRASH_PARTIAL ? cfg->crash_cut : 0u;
-    if (kp.mode == BO_MODE_CRASH_SUBSET) kp.cr_reach = cfg->crash_reach;
-    if (crash_random) {
-      kp.cr_n = (uint32_t)n_crash;
-      cp.reach.assign(kp.cr_n + 1u, 1);            // every m0 - j, j = 0 .. crash_count
-    } else {
-      for (uint32_t c = 0; c < m; ++c) {
-        const uint32_t s = cfg->crash_at[live[c]];
-        if (s != 0xFFFFFFFFu && (uint64_t)s < 2ull * cfg->k_max) cp.list.push_back(s << 12 | c);
-      }
-      std::sort(cp.list.begin(), cp.list.end());
-      kp.cr_n = (uint32_t)cp.list.size();
-      cp.reach.assign(kp.cr_n + 1u, 0);            // m0 minus the cumulative crashes at each distinct step
-      cp.reach[0] = 1;
-      for (uint32_t i = 0; i < kp.cr_n; ++i)
-        if (i + 1u == kp.cr_n || (cp.list[i + 1u] >> 12) != (cp.list[i] >> 12)) cp.reach[i + 1u] = 1;
-      // Partial broadcasts: a receiver's pool is the alive set and the step's crashers that reach
-      // it.  A fixed cut gives all of them or none, live counts of the set above; random cuts
-      // any number of them, so every m0 - j
-      if (kp.mode == BO_MODE_CRASH_PARTIAL && kp.cr_cut == BO_CUT_RANDOM) cp.reach.assign(kp.cr_n + 1u, 1);
-      // A random subset: any number of a step's crashers may reach a receiver, every m0 - j (at reach
-      // 0 and UINT32_MAX too: one rule for the mode)
-      if (kp.mode == BO_MODE_CRASH_SUBSET) cp.reach.assign(kp.cr_n + 1u, 1);
-    }
-    uint64_t bytes = 0;
-    for (uint32_t d = 0; d <= kp.cr_n; ++d)
-      if (cp.reach[d]) bytes += 8ull * tally_table_len(m - d, kp.q);
-    if (bytes > BO_CRASH_TABLE_MAX_BYTES)
-      return fail(BO_ERR_UNSUPPORTED,
-                  kp.mode == BO_MODE_CRASH_TALLY
-                      ? "BO_MODE_CRASH_TALLY: the threshold tables of the reachable live counts exceed "
-                        "the 512 MiB limit (BO_CRASH_TABLE_MAX_BYTES): schedule fewer crashes"
-                  : kp.mode == BO_MODE_CRASH_PARTIAL
-                      ? "BO_MODE_CRASH_PARTIAL: the threshold tables of the reachable pool sizes exceed "
-                        "the 512 MiB limit (BO_CRASH_TABLE_MAX_BYTES): schedule fewer crashes"
-                      : "BO_MODE_CRASH_SUBSET: the threshold tables of the reachable pool sizes exceed "
-                        "the 512 MiB limit (BO_CRASH_TABLE_MAX_BYTES): schedule fewer crashes");
+  if (mode_traits(kp.mode)->is(benor::kModeCrash)) {
+    CrashSchedule local;
+    const int rc = plan_crash_family(cfg, live, n_crash, crash_random, kp, tables ? tables->crash : local);
+    if (rc) return rc;
   }
   benor::plan_geometry(kp);   // after init_q: the kernel choice depends on the round-1 vote parity
   return BO_OK;
@@ -787,14 +790,39 @@ int bo_kernel_for(const bo_trials_cfg *cfg, int *kernel_out) {
   return BO_OK;
 }
 
+// A count-level plan's device tables: one buffer of sections, each at the next 8-byte-aligned offset in
+// the order they are added (the kernels rely on the order and the alignment).  add: `bytes` from `src`,
+// the section at least `min_bytes` long; it returns the section's offset.  upload allocates once and
+// copies every non-empty section from where it lies (the crash family's tables may reach 512 MiB: no
+// second host copy).
+struct TableUpload {
+  struct Section {
+    const void *src;
+    size_t bytes, offset;
+  };
+  std::vector<Section> sections;
+  size_t total = 0;
+  size_t add(const void *src, size_t bytes, size_t min_bytes = 0u) {
+    sections.push_back({src, bytes, total});
+    total += (std::max(bytes, min_bytes) + 7u) & ~size_t(7);
+    return sections.back().offset;
+  }
+  hipError_t upload(unsigned char **dev) const {
+    hipError_t e = hipMalloc(dev, total);
+    for (const Section &s : sections)
+      if (e == hipSuccess && s.bytes) e = hipMemcpy(*dev + s.offset, s.src, s.bytes, hipMemcpyHostToDevice);
+    return e;
+  }
+};
+
 static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_run) {
   if (!cfg || !out) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
   *out = nullptr;
   std::vector<uint32_t> live;
   std::vector<uint4> plane;
   benor::KParams kp0;
-  CrashPlan crash;
-  int rc = plan_host(cfg, live, plane, kp0, live_run, &crash);
+  PlanTables tables;
+  int rc = plan_host(cfg, live, plane, kp0, live_run, &tables);
   if (rc) return rc;
   int dev = 0;
   rc = check_device(&dev);
@@ -831,70 +859,66 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
     if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "plan upload"); }
     kp.live_ids = pl->d_live;
     kp.init_plane = pl->d_init;
-    if (cfg->mode == BO_MODE_EVENT && kp.variant == 5) {
-      // one wave per trial, each with a pool of ev_cap messages: as many
-      // concurrent trials as CUs, within ~4 GiB of pools
+    if (cfg->mode == BO_MODE_EVENT) {
       std::vector<int8_t> ix(cfg->N, 0);
       if (cfg->init_mode == BO_INIT_FIXED)
         for (uint32_t i = 0; i < cfg->N; ++i) ix[i] = cfg->init[i];
-      std::vector<uint64_t> stops;
-      if (cfg->crash_at)
-        for (uint32_t i = 0; i < cfg->N; ++i)
-          if (cfg->crash_at[i] != 0xFFFFFFFFu) stops.push_back(((uint64_t)cfg->crash_at[i] << 12) | i);
-      std::sort(stops.begin(), stops.end());
       int cus = 256;
       (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-      const uint64_t slot = (uint64_t)kp.ev_stride * 4u;
-      uint64_t slots = std::max<uint64_t>(1u, std::min<uint64_t>((uint64_t)cus, (4ull << 30) / slot));
-      if (live_run) slots = 1u;                      // a live run is one trial
-      kp.ev_lanes = slots;
+      const uint64_t slot = (uint64_t)kp.ev_stride * 4u;   // scratch bytes of a trial
+      std::vector<uint64_t> stops;
+      if (kp.variant == 5) {
+        // one wave per trial, each with a pool of ev_cap messages: as many
+        // concurrent trials as CUs, within ~4 GiB of pools
+        if (cfg->crash_at)
+          for (uint32_t i = 0; i < cfg->N; ++i)
+            if (cfg->crash_at[i] != 0xFFFFFFFFu) stops.push_back(((uint64_t)cfg->crash_at[i] << 12) | i);
+        std::sort(stops.begin(), stops.end());
+        kp.ev_lanes = std::max<uint64_t>(1u, std::min<uint64_t>((uint64_t)cus, (4ull << 30) / slot));
+        if (live_run) kp.ev_lanes = 1u;                // a live run is one trial
+      } else {
+        // scratch: one slice per lane, at most ~4 GiB
+        // Lanes per CU: the mode is bound by the latency of per-lane scratch
+        // accesses, so fewer lanes whose slices stay cache-resident beat full
+        // occupancy: 512 per CU for slices up to 4 KiB (N <= 12), else 256
+        // (tools/ev_sweep.sh, BENOR_EVENT_LANES_PER_CU overrides).
+        uint64_t per_cu = benor::knob_u32("BENOR_EVENT_LANES_PER_CU", slot <= 4096u ? 512u : 256u);
+        if (per_cu < 256u) per_cu = 256u;
+        uint64_t lanes = (uint64_t)cus * per_cu;
+        const uint64_t fit = (4ull << 30) / slot;
+        if (fit < lanes) lanes = fit;
+        lanes = lanes / 256u * 256u;
+        if (lanes < 256u) lanes = 256u;
+        kp.ev_lanes = lanes;
+      }
       e = hipMalloc(&pl->d_init_x, cfg->N);
       if (e == hipSuccess) e = hipMemcpy(pl->d_init_x, ix.data(), cfg->N, hipMemcpyHostToDevice);
-      if (e == hipSuccess && !stops.empty()) {
+      if (e == hipSuccess && !stops.empty()) {         // one wave per trial: the sorted /stop schedule
         e = hipMalloc(&pl->d_stops, sizeof(uint64_t) * stops.size());
         if (e == hipSuccess)
           e = hipMemcpy(pl->d_stops, stops.data(), sizeof(uint64_t) * stops.size(), hipMemcpyHostToDevice);
       }
-      if (e == hipSuccess) e = hipMalloc(&pl->d_scratch, slots * slot);
+      if (e == hipSuccess && kp.variant != 5 && cfg->crash_at) {   // one lane per trial: crash_at as it is
+        e = hipMalloc(&pl->d_crash, sizeof(uint32_t) * cfg->N);
+        if (e == hipSuccess) e = hipMemcpy(pl->d_crash, cfg->crash_at, sizeof(uint32_t) * cfg->N, hipMemcpyHostToDevice);
+      }
+      if (e == hipSuccess) e = hipMalloc(&pl->d_scratch, kp.ev_lanes * slot);
       if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "event-mode scratch"); }
       kp.init_x = pl->d_init_x;
       kp.ev_stops = pl->d_stops;
       kp.ev_nstops = (uint32_t)stops.size();
-      kp.scratch = pl->d_scratch;
-    } else if (cfg->mode == BO_MODE_EVENT) {
-      std::vector<int8_t> ix(cfg->N, 0);
-      if (cfg->init_mode == BO_INIT_FIXED)
-        for (uint32_t i = 0; i < cfg->N; ++i) ix[i] = cfg->init[i];
-      // scratch: one slice per lane, at most ~4 GiB
-      const uint64_t stride_bytes = (uint64_t)kp.ev_stride * 4u;
-      int cus = 256;
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-      // Lanes per CU: the mode is bound by the latency of per-lane scratch
-      // accesses, so fewer lanes whose slices stay cache-resident beat full
-      // occupancy: 512 per CU for slices up to 4 KiB (N <= 12), else 256
-      // (tools/ev_sweep.sh, BENOR_EVENT_LANES_PER_CU overrides).
-      uint64_t per_cu = benor::knob_u32("BENOR_EVENT_LANES_PER_CU", stride_bytes <= 4096u ? 512u : 256u);
-      if (per_cu < 256u) per_cu = 256u;
-      uint64_t lanes = (uint64_t)cus * per_cu;
-      const uint64_t fit = (4ull << 30) / stride_bytes;
-      if (fit < lanes) lanes = fit;
-      lanes = lanes / 256u * 256u;
-      if (lanes < 256u) lanes = 256u;
-      kp.ev_lanes = lanes;
-      e = hipMalloc(&pl->d_init_x, cfg->N);
-      if (e == hipSuccess) e = hipMemcpy(pl->d_init_x, ix.data(), cfg->N, hipMemcpyHostToDevice);
-      if (e == hipSuccess && cfg->crash_at) {
-        e = hipMalloc(&pl->d_crash, sizeof(uint32_t) * cfg->N);
-        if (e == hipSuccess) e = hipMemcpy(pl->d_crash, cfg->crash_at, sizeof(uint32_t) * cfg->N, hipMemcpyHostToDevice);
-      }
-      if (e == hipSuccess) e = hipMalloc(&pl->d_scratch, lanes * stride_bytes);
-      if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "event-mode scratch"); }
-      kp.init_x = pl->d_init_x;
       kp.crash_at = pl->d_crash;
       kp.scratch = pl->d_scratch;
-    } else if (kp.variant == 9 || kp.variant == 10 || (kp.variant >= 14 && kp.variant <= 17)) {
-      // BO_MODE_RANDOM_TALLY, BO_MODE_RANDOM_TALLY3, BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B and their shared-coin modes:
-      // the whole table HG(m, K, q), K = 0..m: at most ~3.7 * 10^6 thresholds (30 MB) at m = 4096
+    } else if (benor::variant_sched(kp.variant)) {
+      // An adversarial scheduler: the honest plane alone -- the scheduler's counts are a closed form
+      TableUpload up;
+      const size_t o_plane = up.add(tables.honest.data(), sizeof(uint64_t) * tables.honest.size());
+      e = up.upload(&pl->d_tally);
+      if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "honest plane upload"); }
+      kp.byz_plane = reinterpret_cast<const unsigned long long *>(pl->d_tally + o_plane);
+    } else if (benor::variant_count_level(kp.variant) && !benor::variant_crash(kp.variant)) {
+      // The two- and three-valued modes and the Byzantine family: the whole table HG(m, K, q), K = 0..m: at most
+      // ~3.7 * 10^6 thresholds (30 MB) at m = 4096
       std::vector<uint32_t> off(m + 2u, 0u);
       std::vector<uint64_t> thr;
       std::vector<double> w;
@@ -903,40 +927,26 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
         (void)tally_row(m, kp.q, K, thr, w);
       }
       off[m + 1u] = (uint32_t)thr.size();
-      const size_t off_bytes = (sizeof(uint32_t) * off.size() + 7u) & ~size_t(7);
-      const size_t thr_bytes = sizeof(uint64_t) * std::max<size_t>(thr.size(), 1u);
       // ... and, with Byzantine senders, the Binomial thresholds and the honest plane behind it
-      const bool byz = kp.variant >= 14 && kp.variant <= 17;
+      const bool byz = benor::variant_byz(kp.variant);
       std::vector<uint64_t> lie;
       if (byz && !benor::byz_heard(kp)) byz_row(kp.byz_n, kp.byz_one, lie);   // (BALANCE, SPLIT, b = 0: no thresholds)
-      const size_t lie_bytes = sizeof(uint64_t) * lie.size();
-      const size_t plane_bytes = byz ? sizeof(uint64_t) * crash.honest.size() : 0u;
-      e = hipMalloc(&pl->d_tally, off_bytes + thr_bytes + lie_bytes + plane_bytes);
-      if (e == hipSuccess) e = hipMemcpy(pl->d_tally, off.data(), sizeof(uint32_t) * off.size(), hipMemcpyHostToDevice);
-      if (e == hipSuccess && !thr.empty())
-        e = hipMemcpy(pl->d_tally + off_bytes, thr.data(), sizeof(uint64_t) * thr.size(), hipMemcpyHostToDevice);
-      if (e == hipSuccess && lie_bytes)
-        e = hipMemcpy(pl->d_tally + off_bytes + thr_bytes, lie.data(), lie_bytes, hipMemcpyHostToDevice);
-      if (e == hipSuccess && plane_bytes)
-        e = hipMemcpy(pl->d_tally + off_bytes + thr_bytes + lie_bytes, crash.honest.data(), plane_bytes,
-                      hipMemcpyHostToDevice);
+      TableUpload up;
+      const size_t o_off = up.add(off.data(), sizeof(uint32_t) * off.size());
+      const size_t o_thr = up.add(thr.data(), sizeof(uint64_t) * thr.size(), sizeof(uint64_t));
+      const size_t o_lie = up.add(lie.data(), sizeof(uint64_t) * lie.size());
+      const size_t o_plane = up.add(tables.honest.data(), byz ? sizeof(uint64_t) * tables.honest.size() : 0u);
+      e = up.upload(&pl->d_tally);
       if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "tally table upload"); }
-      kp.tally_off = reinterpret_cast<const uint32_t *>(pl->d_tally);
-      kp.tally_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + off_bytes);
+      kp.tally_off = reinterpret_cast<const uint32_t *>(pl->d_tally + o_off);
+      kp.tally_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + o_thr);
       if (byz) {
-        if (lie_bytes) kp.byz_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + off_bytes + thr_bytes);
-        kp.byz_plane = reinterpret_cast<const unsigned long long *>(pl->d_tally + off_bytes + thr_bytes + lie_bytes);
+        if (!lie.empty()) kp.byz_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + o_lie);
+        kp.byz_plane = reinterpret_cast<const unsigned long long *>(pl->d_tally + o_plane);
       }
-    } else if (kp.variant >= 18 && kp.variant <= 21) {
-      // BO_MODE_SCHED_TALLY, BO_MODE_SCHED_RULE_B: the honest plane alone -- the scheduler's counts are a closed form
-      const size_t plane_bytes = sizeof(uint64_t) * crash.honest.size();
-      e = hipMalloc(&pl->d_tally, plane_bytes);
-      if (e == hipSuccess) e = hipMemcpy(pl->d_tally, crash.honest.data(), plane_bytes, hipMemcpyHostToDevice);
-      if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "honest plane upload"); }
-      kp.byz_plane = reinterpret_cast<const unsigned long long *>(pl->d_tally);
-    } else if (kp.variant == 11 || kp.variant == 12 || kp.variant == 13) {
-      // BO_MODE_CRASH_TALLY, BO_MODE_CRASH_PARTIAL, BO_MODE_CRASH_SUBSET: one table per reachable live count (pool
-      // size), and their directory
+    } else if (benor::variant_crash(kp.variant)) {
+      // The crash family: one table per reachable live count (pool size), and their directory
+      const CrashSchedule &crash = tables.crash;
       std::vector<benor::CrashDir> dir(kp.cr_n + 1u);
       std::vector<uint32_t> off;
       std::vector<uint64_t> thr;
@@ -957,24 +967,17 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
         }
         off.push_back((uint32_t)(thr.size() - base));   // the md + 2nd offset: the last row's end
       }
-      const size_t dir_bytes = sizeof(benor::CrashDir) * dir.size();
-      const size_t off_bytes = (sizeof(uint32_t) * off.size() + 7u) & ~size_t(7);
-      const size_t list_bytes = (sizeof(uint32_t) * crash.list.size() + 7u) & ~size_t(7);
-      e = hipMalloc(&pl->d_tally, dir_bytes + off_bytes + list_bytes + sizeof(uint64_t) * std::max<size_t>(thr.size(), 1u));
-      if (e == hipSuccess) e = hipMemcpy(pl->d_tally, dir.data(), dir_bytes, hipMemcpyHostToDevice);
-      if (e == hipSuccess)
-        e = hipMemcpy(pl->d_tally + dir_bytes, off.data(), sizeof(uint32_t) * off.size(), hipMemcpyHostToDevice);
-      if (e == hipSuccess && !crash.list.empty())
-        e = hipMemcpy(pl->d_tally + dir_bytes + off_bytes, crash.list.data(), sizeof(uint32_t) * crash.list.size(),
-                      hipMemcpyHostToDevice);
-      if (e == hipSuccess && !thr.empty())
-        e = hipMemcpy(pl->d_tally + dir_bytes + off_bytes + list_bytes, thr.data(), sizeof(uint64_t) * thr.size(),
-                      hipMemcpyHostToDevice);
+      TableUpload up;
+      const size_t o_dir = up.add(dir.data(), sizeof(benor::CrashDir) * dir.size());
+      const size_t o_off = up.add(off.data(), sizeof(uint32_t) * off.size());
+      const size_t o_list = up.add(crash.list.data(), sizeof(uint32_t) * crash.list.size());
+      const size_t o_thr = up.add(thr.data(), sizeof(uint64_t) * thr.size(), sizeof(uint64_t));
+      e = up.upload(&pl->d_tally);
       if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "crash tally table upload"); }
-      kp.cr_dir = reinterpret_cast<const benor::CrashDir *>(pl->d_tally);
-      kp.tally_off = reinterpret_cast<const uint32_t *>(pl->d_tally + dir_bytes);
-      kp.cr_list = crash.list.empty() ? nullptr : reinterpret_cast<const uint32_t *>(pl->d_tally + dir_bytes + off_bytes);
-      kp.tally_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + dir_bytes + off_bytes + list_bytes);
+      kp.cr_dir = reinterpret_cast<const benor::CrashDir *>(pl->d_tally + o_dir);
+      kp.tally_off = reinterpret_cast<const uint32_t *>(pl->d_tally + o_off);
+      kp.cr_list = crash.list.empty() ? nullptr : reinterpret_cast<const uint32_t *>(pl->d_tally + o_list);
+      kp.tally_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + o_thr);
     }
   }
   *out = pl;
@@ -1014,13 +1017,8 @@ int bo_plan_kernel(const bo_plan *pl) {
 // unit: the work they stand in for).
 uint64_t bo_plan_popc_words_per_node_round(const bo_plan *pl) {
   if (!pl) return 0;
-  uint64_t counts = 4ull;
-  if (pl->kp.mode != BO_MODE_RANDOM_DELIVERY && pl->kp.mode != BO_MODE_RANDOM_TALLY &&
-      pl->kp.mode != BO_MODE_RANDOM_TALLY3 && pl->kp.mode != BO_MODE_CRASH_TALLY &&
-      pl->kp.mode != BO_MODE_CRASH_PARTIAL && pl->kp.mode != BO_MODE_CRASH_SUBSET &&
-      pl->kp.mode != BO_MODE_BYZ_TALLY && pl->kp.mode != BO_MODE_BYZ_RULE_B && pl->kp.mode != BO_MODE_BYZ_COIN &&
-      pl->kp.mode != BO_MODE_BYZ_RULE_B_COIN && pl->kp.mode != BO_MODE_SCHED_TALLY && pl->kp.mode != BO_MODE_SCHED_RULE_B)
-    counts = ((pl->kp.m - pl->kp.init_q) & 1u) ? 2ull : 3ull;
+  const bool random = mode_traits(pl->kp.mode)->is(benor::kModeRandom);
+  const uint64_t counts = random ? 4ull : ((pl->kp.m - pl->kp.init_q) & 1u) ? 2ull : 3ull;
   return counts * ((pl->kp.m + 31ull) / 32ull);
 }
 
@@ -1287,6 +1285,22 @@ struct StateScratch {
 };
 thread_local StateScratch t_scratch;
 
+// Host-side initial states (node.ts:21-26) of a validated configuration, N entries; live entries are
+// overwritten by the kernel.
+void initial_states(const bo_trials_cfg *cfg, bo_node_state *st) {
+  // (the Byzantine family: a Byzantine node is alive and has no protocol state; no kernel writes its entry)
+  const bool byz_mode = mode_traits(cfg->mode)->is(benor::kModeByz);
+  for (uint32_t i = 0; i < cfg->N; ++i) {
+    const bool f = cfg->faulty[i] != 0;
+    const bool byz = byz_mode && cfg->faulty[i] == 2u;
+    st[i].killed = f && !byz ? 1 : 0;
+    st[i].x = f ? -1 : (cfg->init_mode == BO_INIT_FIXED ? cfg->init[i] : -1);
+    st[i].decided = f ? -1 : 0;
+    st[i].pad = 0;
+    st[i].k = f ? -1 : 0;
+  }
+}
+
 int run_states_lockstep(const bo_trials_cfg *cfg, uint64_t trial, bo_node_state *nodes_out, uint32_t *rounds_out) {
   std::vector<uint32_t> live;
   std::vector<uint4> plane;
@@ -1312,16 +1326,7 @@ int run_states_lockstep(const bo_trials_cfg *cfg, uint64_t trial, bo_node_state 
     sc.device = dev;
   }
   sc.h.assign(bytes, 0);
-  // host-side initial states (node.ts:21-26); live entries are overwritten by the kernel
-  bo_node_state *st = reinterpret_cast<bo_node_state *>(sc.h.data() + o_st);
-  for (uint32_t i = 0; i < N; ++i) {
-    const bool f = cfg->faulty[i] != 0;
-    st[i].killed = f ? 1 : 0;
-    st[i].x = f ? -1 : (cfg->init_mode == BO_INIT_FIXED ? cfg->init[i] : -1);
-    st[i].decided = f ? -1 : 0;
-    st[i].pad = 0;
-    st[i].k = f ? -1 : 0;
-  }
+  initial_states(cfg, reinterpret_cast<bo_node_state *>(sc.h.data() + o_st));
   if (m) std::memcpy(sc.h.data() + o_live, live.data(), sizeof(uint32_t) * m);
   if (!plane.empty()) std::memcpy(sc.h.data() + o_init, plane.data(), sizeof(uint4) * plane.size());
   HIP_TRY(hipMemcpy(sc.d, sc.h.data(), bytes, hipMemcpyHostToDevice));
@@ -1343,25 +1348,6 @@ int run_states_lockstep(const bo_trials_cfg *cfg, uint64_t trial, bo_node_state 
 }
 }  // namespace
 
-namespace {
-// Host-side initial states (node.ts:21-26); live entries are overwritten by the kernel.
-void initial_states(const bo_trials_cfg *cfg, std::vector<bo_node_state> &st) {
-  st.resize(cfg->N);
-  for (uint32_t i = 0; i < cfg->N; ++i) {
-    const bool f = cfg->faulty[i] != 0;
-    // (BO_MODE_BYZ_TALLY, BO_MODE_BYZ_RULE_B: a Byzantine node is alive and has no protocol state; no kernel writes its entry)
-    const bool byz = (cfg->mode == BO_MODE_BYZ_TALLY || cfg->mode == BO_MODE_BYZ_RULE_B || cfg->mode == BO_MODE_BYZ_COIN ||
-                      cfg->mode == BO_MODE_BYZ_RULE_B_COIN || cfg->mode == BO_MODE_SCHED_TALLY ||
-                      cfg->mode == BO_MODE_SCHED_RULE_B) && cfg->faulty[i] == 2u;
-    st[i].killed = f && !byz ? 1 : 0;
-    st[i].x = f ? -1 : (cfg->init_mode == BO_INIT_FIXED ? cfg->init[i] : -1);
-    st[i].decided = f ? -1 : 0;
-    st[i].pad = 0;
-    st[i].k = f ? -1 : 0;
-  }
-}
-}  // namespace
-
 int bo_run_trial_states(const bo_trials_cfg *cfg, uint64_t trial, bo_node_state *nodes_out, uint32_t *rounds_out) {
   if (!cfg || !nodes_out) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
   if (cfg->mode == BO_MODE_LOCKSTEP) return run_states_lockstep(cfg, trial, nodes_out, rounds_out);
@@ -1369,8 +1355,8 @@ int bo_run_trial_states(const bo_trials_cfg *cfg, uint64_t trial, bo_node_state 
   int rc = bo_plan_create(cfg, &pl);
   if (rc) return rc;
   const uint32_t N = cfg->N, H = bo_hist_len(cfg->k_max);
-  std::vector<bo_node_state> st;
-  initial_states(cfg, st);
+  std::vector<bo_node_state> st(N);
+  initial_states(cfg, st.data());
   bo_node_state *d_st = nullptr;
   uint64_t *d_h = nullptr;
   uint32_t *d_r = nullptr;
@@ -1484,9 +1470,7 @@ int wg_launch(LiveSlot *sl, const bo_trials_cfg *cfg, bool live, WgRun &run) {
   }
   unsigned char *const h = sl->hp;
   std::memset(h, 0, o_pool);
-  std::vector<bo_node_state> st;
-  initial_states(cfg, st);
-  std::memcpy(h + o_st, st.data(), sizeof(bo_node_state) * N);
+  initial_states(cfg, reinterpret_cast<bo_node_state *>(h + o_st));
   if (m) std::memcpy(h + o_live, ids.data(), sizeof(uint32_t) * m);
   std::memcpy(h + o_ix, cfg->init, N);
   if (!stops.empty()) std::memcpy(h + o_stops, stops.data(), sizeof(uint64_t) * stops.size());

@@ -384,26 +384,27 @@ using ByzKernel = void (*)(KParams);
 static ByzKernel byz_entry(const KParams &p) {
   const bool heard = byz_heard(p);
   switch (p.variant) {
-    case 14u: return heard ? benor_tally_heard_kernel<RuleRef, CoinLocal> : benor_tally_byz_kernel<RuleRef, CoinLocal>;
-    case 15u: return heard ? benor_tally_heard_kernel<RuleB, CoinLocal> : benor_tally_byz_kernel<RuleB, CoinLocal>;
-    case 16u: return heard ? benor_tally_heard_kernel<RuleRef, CoinShared> : benor_tally_byz_kernel<RuleRef, CoinShared>;
-    default: return heard ? benor_tally_heard_kernel<RuleB, CoinShared> : benor_tally_byz_kernel<RuleB, CoinShared>;
+    case byz_variant(BO_MODE_BYZ_TALLY): return heard ? benor_tally_heard_kernel<RuleRef, CoinLocal> : benor_tally_byz_kernel<RuleRef, CoinLocal>;
+    case byz_variant(BO_MODE_BYZ_RULE_B): return heard ? benor_tally_heard_kernel<RuleB, CoinLocal> : benor_tally_byz_kernel<RuleB, CoinLocal>;
+    case byz_variant(BO_MODE_BYZ_COIN): return heard ? benor_tally_heard_kernel<RuleRef, CoinShared> : benor_tally_byz_kernel<RuleRef, CoinShared>;
+    case byz_variant(BO_MODE_BYZ_RULE_B_COIN): return heard ? benor_tally_heard_kernel<RuleB, CoinShared> : benor_tally_byz_kernel<RuleB, CoinShared>;
+    default: return nullptr;
   }
 }
 
 // Workgroups of the kernel that one CU holds at once (registers and LDS; 0 = unknown).
-int byz_blocks_per_cu(const KParams &p) { return blocks_per_cu(byz_entry(p), p); }
+int byz_blocks_per_cu(const KParams &p) { return variant_byz(p.variant) ? blocks_per_cu(byz_entry(p), p) : 0; }
 
-// Variants 14 to 17.  Variant 14 alone needs a Byzantine node; the others run without one too (byz_n = 0: no
-// thresholds, none in LDS).  Variants 16 and 17 need coin_common != 0 (0 is the parent mode's plan).
+// The Byzantine variants.  BO_MODE_BYZ_TALLY's alone needs a Byzantine node; the others run without one too (byz_n = 0:
+// no thresholds, none in LDS).  The shared-coin ones need coin_common != 0 (0 is the parent mode's plan).
 hipError_t launch_tally_byz(const KParams &plan, int grid, hipStream_t s) {
   const KParams p = state_launch(plan, byz_state_bytes(plan.W));
-  const bool shared = p.variant == 16u || p.variant == 17u;
+  const bool shared = variant_shared_coin(p.variant);
   const bool heard = byz_heard(p);                 // BO_BYZ_BALANCE, BO_BYZ_SPLIT: no thresholds, none in LDS
   const bool no_thr = heard || p.byz_n == 0u;
-  if (!p.tally_off || !p.tally_thr || !p.byz_plane || (no_thr ? p.byz_lds != 0u : !p.byz_thr) || p.W > kMaxW ||
-      (p.byz_n == 0u && p.variant == 14u) || (shared && p.coin_common == 0u) || p.byz_n > p.m - p.q ||
-      plan.wave_bytes < byz_wave_bytes(p.W, p.tally_cap) ||
+  if (!variant_byz(p.variant) || !p.tally_off || !p.tally_thr || !p.byz_plane || (no_thr ? p.byz_lds != 0u : !p.byz_thr) ||
+      p.W > kMaxW || (p.byz_n == 0u && p.variant == byz_variant(BO_MODE_BYZ_TALLY)) || (shared && p.coin_common == 0u) ||
+      p.byz_n > p.m - p.q || plan.wave_bytes < byz_wave_bytes(p.W, p.tally_cap) ||
       plan.lds_bytes < p.hist_bytes + kWavesPerBlock * plan.wave_bytes + (p.byz_lds ? 8u * p.byz_n : 0u))
     return hipErrorInvalidValue;
   return launch_lds(byz_entry(p), p, grid, s);

@@ -184,22 +184,23 @@ __global__ void __launch_bounds__(256, 8) benor_tally_sched_kernel(KParams p) {
 using SchedKernel = void (*)(KParams);
 static SchedKernel sched_entry(const KParams &p) {
   switch (p.variant) {
-    case 18u: return benor_tally_sched_kernel<RuleRef, CoinLocal>;
-    case 19u: return benor_tally_sched_kernel<RuleB, CoinLocal>;
-    case 20u: return benor_tally_sched_kernel<RuleRef, CoinShared>;
-    default: return benor_tally_sched_kernel<RuleB, CoinShared>;
+    case sched_variant(BO_MODE_SCHED_TALLY, false): return benor_tally_sched_kernel<RuleRef, CoinLocal>;
+    case sched_variant(BO_MODE_SCHED_RULE_B, false): return benor_tally_sched_kernel<RuleB, CoinLocal>;
+    case sched_variant(BO_MODE_SCHED_TALLY, true): return benor_tally_sched_kernel<RuleRef, CoinShared>;
+    case sched_variant(BO_MODE_SCHED_RULE_B, true): return benor_tally_sched_kernel<RuleB, CoinShared>;
+    default: return nullptr;
   }
 }
 
 // Workgroups of the kernel that one CU holds at once (registers and LDS; 0 = unknown).
-int sched_blocks_per_cu(const KParams &p) { return blocks_per_cu(sched_entry(p), p); }
+int sched_blocks_per_cu(const KParams &p) { return variant_sched(p.variant) ? blocks_per_cu(sched_entry(p), p) : 0; }
 
-// Variants 18 to 21.  All run without a Byzantine node too (byz_n = 0: crash-only adversarial scheduling);
-// variants 20 and 21 need coin_common != 0, variants 18 and 19 have every coin local.
+// The scheduler's variants.  All run without a Byzantine node too (byz_n = 0: crash-only adversarial scheduling);
+// the shared-coin ones need coin_common != 0, the others have every coin local.
 hipError_t launch_tally_sched(const KParams &plan, int grid, hipStream_t s) {
   const KParams p = state_launch(plan, byz_state_bytes(plan.W));
-  const bool shared = p.variant == 20u || p.variant == 21u;
-  if (p.variant < 18u || p.variant > 21u || !p.byz_plane || p.W == 0u || p.W > kMaxW || p.q > p.m ||
+  const bool shared = variant_shared_coin(p.variant);
+  if (!variant_sched(p.variant) || !p.byz_plane || p.W == 0u || p.W > kMaxW || p.q > p.m ||
       (p.byz_strategy != BO_BYZ_BALANCE && p.byz_strategy != BO_BYZ_SPLIT) || shared != (p.coin_common != 0u) ||
       p.byz_n > p.m - p.q || plan.wave_bytes < byz_wave_bytes(p.W, 0u) ||
       plan.lds_bytes < p.hist_bytes + kWavesPerBlock * plan.wave_bytes)

@@ -1,0 +1,25 @@
+"""The delivery modes' traits table and the count-level variant predicates
+(csrc/benor_modes.h): the one place the host asks which family a mode or a
+kernel variant belongs to.  tests/modes_check.cpp, a host program over that
+header, holds the same facts written out by hand and compares; it is built
+with the address and undefined-behaviour sanitizers and run as it is.
+"""
+import os
+import shutil
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "ben-or-consensus-algorithm_amd", "csrc")
+
+
+def test_modes_on_the_host(tmp_path):
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    exe = tmp_path / "modes_check"
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=undefined", "-I", CSRC, "-I", os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "tests", "modes_check.cpp"), "-o", str(exe)], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    # 14 modes x 10 facts and 6 values that are no mode, 40 variants x 7, the variant functions
+    assert int(r.stdout.split()[0]) >= 14 * 10 + 6 + 40 * 7 + 8 and " 0 failures" in r.stdout, r.stdout
