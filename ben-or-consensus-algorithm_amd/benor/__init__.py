@@ -148,6 +148,7 @@ EXPORTED_SYMBOLS = (
     "bo_mfma_peak", "bo_consensus_start_sched", "bo_plan_check",
     "bo_consensus_start_live", "bo_consensus_wait", "bo_live_stop_events", "bo_get_states", "bo_consensus_poll",
     "bo_tally_cdf", "bo_byz_cdf",
+    "bo_lumped_check", "bo_lumped_run", "bo_lumped_trial", "bo_binom_half_cdf",
 )
 
 
@@ -170,6 +171,17 @@ class TrialsCfgC(ctypes.Structure):
                 ("seed", ctypes.c_uint64), ("faulty", ctypes.POINTER(ctypes.c_uint8)),
                 ("init", ctypes.POINTER(ctypes.c_int8)), ("crash_at", ctypes.POINTER(ctypes.c_uint32)),
                 ("crash_count", ctypes.c_uint32), ("crash_window", ctypes.c_uint32)]
+
+
+class LumpedCfgC(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in ("N", "F", "f", "b", "byz_even", "rule", "strategy", "coin_common", "k_max",
+                                               "init_mode", "init0", "init1", "initq", "reserved")] + \
+               [("seed", ctypes.c_uint64)]
+
+
+class LumpedStateC(ctypes.Structure):
+    _fields_ = [("a", ctypes.c_uint32 * 2), ("dec", ctypes.c_uint8 * 2), ("pad", ctypes.c_uint8 * 2),
+                ("rounds", ctypes.c_uint32)]
 
 
 def _crash_array(N, crash_at):
@@ -234,6 +246,11 @@ def lib() -> ctypes.CDLL:
     L.bo_tally_cdf.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P(ctypes.c_uint32),
                                P(ctypes.c_uint64), ctypes.c_uint32, P(ctypes.c_uint32)]
     L.bo_byz_cdf.argtypes = [ctypes.c_uint32, ctypes.c_uint32, P(ctypes.c_uint64), ctypes.c_uint32, P(ctypes.c_uint32)]
+    L.bo_lumped_check.argtypes = [P(LumpedCfgC)]
+    L.bo_lumped_run.argtypes = [P(LumpedCfgC), ctypes.c_uint64, ctypes.c_uint64, P(ctypes.c_uint64)]
+    L.bo_lumped_trial.argtypes = [P(LumpedCfgC), ctypes.c_uint64, P(LumpedStateC)]
+    L.bo_binom_half_cdf.argtypes = [ctypes.c_uint32, P(ctypes.c_uint32), P(ctypes.c_uint64), ctypes.c_uint32,
+                                    P(ctypes.c_uint32)]
     L.bo_last_error.restype = ctypes.c_char_p
     L.bo_abi_version.restype = ctypes.c_int
     L.bo_kernel_version.restype = ctypes.c_char_p
@@ -710,6 +727,90 @@ def byz_cdf(b: int, byz_one: int) -> list[int]:
     n = ctypes.c_uint32()
     _check(lib().bo_byz_cdf(b, byz_one, thr, b, ctypes.byref(n)))
     return [int(v) for v in thr[:n.value]]
+
+
+# ------------------------------------------------------------------ the lumped (class-level) chain
+LUMPED_MAX_N = 1 << 24
+
+
+def byz_even(faulty: Sequence, byzantine: Sequence | None = None) -> int:
+    """The Byzantine nodes at an even compact index, as bo_lumped_cfg.byz_even counts them: compact indices number
+    the live nodes in ascending node id.  `faulty` marks the crashed nodes (an int entry 2 a Byzantine one, as modes
+    8 to 13 read it), `byzantine` the Byzantine ones: a mode-12 configuration maps to its lumped one through
+    f = the crashed, b = the Byzantine, and this."""
+    n, c = 0, 0
+    for i, v in enumerate(faulty):
+        byz = (type(v) is int and v == 2) or (byzantine is not None and bool(byzantine[i]))
+        if v and not byz:
+            continue                                # crashed: no compact index
+        if byz and c % 2 == 0:
+            n += 1
+        c += 1
+    return n
+
+
+class LumpedPlan:
+    """Many independent trials of the adversarial scheduler's class-level chain (bo_lumped_*):
+    modes 12 and 13 with nodes replaced by the two receiver parities, N up to 2**24.  rule 0 is mode 12's, 1 mode 13's;
+    byz_strategy BYZ_BALANCE or BYZ_SPLIT; initial_values None (random) or the counts (init0, init1, initq) of the
+    honest nodes that start at 0, 1 and "?".  Validation needs no device."""
+
+    def __init__(self, N: int, F: int, *, f: int = 0, b: int = 0, byz_even: int = 0, rule: int = 0,
+                 byz_strategy: int = BYZ_BALANCE, coin_common: int = 0, seed: int = 0, k_max: int = DEFAULT_K_MAX,
+                 initial_values: Sequence[int] | None = None):
+        words = dict(N=N, F=F, f=f, b=b, byz_even=byz_even, rule=rule, strategy=byz_strategy, coin_common=coin_common,
+                     k_max=k_max)
+        init = (0, 0, 0) if initial_values is None else tuple(initial_values)
+        if len(init) != 3:
+            raise ValueError("initial_values holds three counts: the honest nodes that start at 0, 1 and '?'")
+        words.update(init0=init[0], init1=init[1], initq=init[2])
+        for name, v in words.items():
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 0xFFFFFFFF:
+                raise ValueError(f"{name} is an unsigned 32-bit word, got {v!r}")
+        if not 0 <= seed < 1 << 64:
+            raise ValueError("seed is an unsigned 64-bit word")
+        self.N, self.F, self.k_max, self.seed = N, F, k_max, seed
+        self._cfg = LumpedCfgC(init_mode=BO_INIT_RANDOM if initial_values is None else BO_INIT_FIXED, reserved=0,
+                               seed=seed, **words)
+        _check(lib().bo_lumped_check(ctypes.byref(self._cfg)))
+
+    @property
+    def hist_len(self) -> int:
+        return hist_len(self.k_max)
+
+    def run(self, trial_begin: int, trial_count: int):
+        import numpy as np
+
+        h = np.zeros(self.hist_len, dtype=np.uint64)
+        _check(lib().bo_lumped_run(ctypes.byref(self._cfg), trial_begin, trial_count,
+                                   h.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        return h
+
+    def trial(self, trial: int) -> dict:
+        """One trial's final state: {"a": (a_0, a_1), "dec": (dec_0, dec_1), "rounds": R or 0}."""
+        st = LumpedStateC()
+        _check(lib().bo_lumped_trial(ctypes.byref(self._cfg), trial, ctypes.byref(st)))
+        return {"a": (int(st.a[0]), int(st.a[1])), "dec": (bool(st.dec[0]), bool(st.dec[1])), "rounds": int(st.rounds)}
+
+
+def lumped_trials(N: int, F: int, trial_begin: int, trial_count: int, **kw):
+    """The histogram of trials [trial_begin, trial_begin + trial_count) of a LumpedPlan(N, F, **kw)."""
+    return LumpedPlan(N, F, **kw).run(trial_begin, trial_count)
+
+
+def lumped_trial(N: int, F: int, trial: int, **kw) -> dict:
+    """LumpedPlan(N, F, **kw).trial(trial)."""
+    return LumpedPlan(N, F, **kw).trial(trial)
+
+
+def binom_half_cdf(k: int) -> tuple[int, list[int]]:
+    """The thresholds of Binomial(2**k, 1/2), 7 <= k <= 24, that the lumped chain searches (bo_binom_half_cdf; host
+    only): (lo, thresholds).  A 64-bit draw u gives the count lo + #{j : thresholds[j] <= u}."""
+    cap = 1 << 16                                   # k = 24 holds about 37 000: 9.1 standard deviations either side
+    thr = (ctypes.c_uint64 * cap)()
+    lo, n = ctypes.c_uint32(), ctypes.c_uint32()
+    _check(lib().bo_binom_half_cdf(k, ctypes.byref(lo), thr, cap, ctypes.byref(n)))
+    return int(lo.value), list(thr[:n.value])
 
 
 def kernel_version() -> str:

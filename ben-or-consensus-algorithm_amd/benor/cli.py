@@ -19,6 +19,8 @@
                                                                           # ... with a shared coin in every round
     python -m benor.cli trials --N 64 --F 20 --mode byz --crashed 0 --byzantine 0 --byz-strategy split --delivery adversarial
                                                                           # an adversarial scheduler, no Byzantine node
+    python -m benor.cli trials --N 16777216 --F 9000 --mode byz --crashed 0 --byz-strategy balance --delivery adversarial --level class
+                                                                          # ... at the level of classes: N up to 2**24
     python -m benor.cli sweep --N 64,128,...,4096 --steps 32 --trials 2**30 --out sweep.csv
                                                                           # C5 phase diagram
     python -m benor.cli sweep --cells 4096:0,4096:1984 --per-cell 4793490  # two cells of it
@@ -45,7 +47,9 @@ adversarial scheduler's modes, whose rows add a delivery column) cross every (N,
 b = floor(beta (F - f)) Byzantine nodes, beta = i / S for i = 0..S (`--byz-steps S`),
 placed as `trials` places them: the first f nodes crashed, the next b Byzantine.
 `--cells` then also takes N:F:b.  Their rows add b, mode, byz_strategy,
-byz_one_word and coin_common_word.
+byz_one_word and coin_common_word.  `--level class` (with `--delivery adversarial`) runs
+`trials` and `sweep` on the lumped chain (benor.LumpedPlan): the same
+placement, N up to 2**24, a `level` field or column; `--level node` is the default.
 """
 from __future__ import annotations
 
@@ -130,6 +134,26 @@ def check_delivery(a) -> bool:
     return True
 
 
+def check_level(a, adversarial: bool) -> bool:
+    """--level of `trials` and `sweep`: whether the adversarial scheduler runs at the level of classes (the lumped
+    chain, DESIGN §4.3.12: N up to 2**24).  Its argument errors need no device."""
+    if a.level != "class":
+        return False
+    if not adversarial:
+        raise SystemExit("--level class needs --mode byz or --mode byzb with --delivery adversarial")
+    return True
+
+
+def lumped_words(a, benor, crashed: int, b: int) -> dict:
+    """LumpedPlan's words for the placement `trials` and `sweep` use: the first `crashed` nodes crashed, the next b
+    Byzantine -- the compact indices 0 .. b - 1, ceil(b / 2) of them even."""
+    words = dict(f=crashed, b=b, byz_even=(b + 1) // 2, rule=1 if a.mode == "byzb" else 0,
+                 byz_strategy=benor.BYZ_BALANCE if a.byz_strategy == "balance" else benor.BYZ_SPLIT)
+    if a.coin_common is not None:
+        words["coin_common"] = benor.reach_word(a.coin_common)
+    return words
+
+
 def byz_mode(a, benor) -> int:
     """BO_MODE_* of --mode byz / byzb: with --delivery adversarial the scheduler's mode, else with --coin-common
     the shared-coin mode."""
@@ -150,6 +174,8 @@ def cmd_trials(a) -> int:
             "byzb": benor.BO_MODE_BYZ_RULE_B}[a.mode]
     crashed = a.F if a.crashed is None else a.crashed            # the first f nodes (start.ts:7-18 placement)
     adversarial = check_delivery(a)
+    if check_level(a, adversarial):
+        return trials_class(a, benor, crashed)
     sched = {}
     if a.mode in ("crash", "partial", "subset"):                  # crashes during the run, in steps
         if a.crash_at and a.crash_count:
@@ -215,6 +241,29 @@ def cmd_trials(a) -> int:
     return 0
 
 
+def trials_class(a, benor, crashed: int) -> int:
+    """`trials --level class`: the batch on the lumped chain, the row of the node level plus a level field."""
+    if not 0.0 <= a.byz_one <= 1.0:
+        raise SystemExit("--byz-one is a probability in [0, 1]")
+    if a.coin_common is not None and not 0.0 <= a.coin_common <= 1.0:
+        raise SystemExit("--coin-common is a probability in [0, 1]")
+    if not 0 <= a.byzantine <= a.N - crashed:
+        raise SystemExit("--byzantine counts live nodes: 0 .. N - crashed")
+    words = lumped_words(a, benor, crashed, a.byzantine)
+    plan = benor.LumpedPlan(a.N, a.F, seed=a.seed, k_max=a.k_max, **words)
+    t0 = time.perf_counter()
+    h = plan.run(a.begin, a.trials)
+    dt = time.perf_counter() - t0
+    row = summarize(h, a.N, a.F, a.k_max)
+    row.update(m=a.N - crashed, mode=a.mode, crashed=crashed, hist=[int(v) for v in h], byzantine=a.byzantine,
+               byz_even=words["byz_even"], byz_strategy=a.byz_strategy)
+    if a.coin_common is not None:
+        row.update(coin_common=a.coin_common, coin_common_word=words["coin_common"])
+    row.update(delivery=a.delivery, level=a.level, seconds=dt)
+    print(json.dumps(row))
+    return 0
+
+
 def byz_grid(cells, steps: int, crashed: int = 0):
     """Every (N, F) cell crossed with b = floor(beta (F - crashed)), beta = i / steps, i = 0..steps."""
     if steps < 1:
@@ -255,6 +304,7 @@ def sweep_byz_cells(a):
 def cmd_sweep(a) -> int:
     byz = a.mode in ("byz", "byzb")
     adversarial = check_delivery(a)
+    level_class = check_level(a, adversarial)
     if not byz and (a.coin_common is not None or a.byz_steps is not None or a.byz_strategy is not None or
                     a.byz_one is not None):
         raise SystemExit("--byz-steps / --byz-strategy / --byz-one / --coin-common need --mode byz or --mode byzb")
@@ -299,7 +349,8 @@ def cmd_sweep(a) -> int:
     if byz:
         rows, elapsed = run_sweep(cells, per_cell, a.seed, a.k_max, a.streams, rank, world, a.progress,
                                   mode=a.mode, crashed=byz_crashed, byz=dict(sched, strategy_name=a.byz_strategy),
-                                  delivery="adversarial" if adversarial else "random")
+                                  delivery="adversarial" if adversarial else "random",
+                                  level="class" if level_class else "node")
     elif a.mode == "tally3":
         crashed = 0 if a.crashed is None else a.crashed
         bad = [f"{N}:{F}" for (N, F) in cells if crashed > F]
@@ -331,7 +382,7 @@ def rows_csv(rows: list[dict]) -> str:
 
 
 def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progress=False, mode="lockstep",
-              crashed=None, byz=None, delivery="random"):
+              crashed=None, byz=None, delivery="random", level="node"):
     """The sweep's GPU work on the current device: (rows, seconds).  Under
     torch.distributed (world > 1) each cell's trials are split over the ranks
     and the histograms merged by one all-reduce.  mode "lockstep": F crashed
@@ -341,7 +392,8 @@ def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progre
     Byzantine; `byz` holds byz_one and byz_strategy (words), strategy_name for the
     rows, and with coin_common the shared-coin modes' word; `delivery` "adversarial"
     runs them under the adversarial scheduler (byz_strategy balance or split), and
-    the rows then add a delivery column."""
+    the rows then add a delivery column; `level` "class" runs those on the lumped chain
+    (benor.LumpedPlan: N up to 2**24; blocking launches, cell after cell) and adds a level column."""
     import torch
 
     import benor
@@ -360,6 +412,8 @@ def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progre
     # groups of a launch) overlap the next cell's launches instead of idling CUs.
     if delivery not in ("random", "adversarial") or (delivery == "adversarial" and mode not in ("byz", "byzb")):
         raise ValueError("delivery is 'random', or 'adversarial' with mode 'byz' or 'byzb'")
+    if level not in ("node", "class") or (level == "class" and delivery != "adversarial"):
+        raise ValueError("level is 'node', or 'class' with delivery 'adversarial'")
     if mode == "lockstep":
         if crashed is not None:
             raise ValueError("crashed needs mode 'tally3' (lockstep crashes exactly F nodes per cell)")
@@ -386,10 +440,15 @@ def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progre
                    ("byz", True): benor.BO_MODE_BYZ_COIN, ("byzb", True): benor.BO_MODE_BYZ_RULE_B_COIN}[mode, coin]
         if delivery == "adversarial":
             bo_mode = benor.BO_MODE_SCHED_TALLY if mode == "byz" else benor.BO_MODE_SCHED_RULE_B
-        plans = [benor.TrialsPlan(N, F, [i < crashed for i in range(N)], seed=seed ^ (N << 20) ^ F ^ (b << 44),
-                                  k_max=k_max, mode=bo_mode,
-                                  byzantine=[crashed <= i < crashed + b for i in range(N)], **byz)
-                 for (N, F, b) in cells]
+        if level == "class":                     # the same placement: compact indices 0 .. b - 1 Byzantine
+            plans = [benor.LumpedPlan(N, F, f=crashed, b=b, byz_even=(b + 1) // 2, rule=1 if mode == "byzb" else 0,
+                                      byz_strategy=byz["byz_strategy"], coin_common=byz.get("coin_common", 0),
+                                      seed=seed ^ (N << 20) ^ F ^ (b << 44), k_max=k_max) for (N, F, b) in cells]
+        else:
+            plans = [benor.TrialsPlan(N, F, [i < crashed for i in range(N)], seed=seed ^ (N << 20) ^ F ^ (b << 44),
+                                      k_max=k_max, mode=bo_mode,
+                                      byzantine=[crashed <= i < crashed + b for i in range(N)], **byz)
+                     for (N, F, b) in cells]
     else:
         raise ValueError(f"mode must be 'lockstep', 'tally3', 'byz' or 'byzb': {mode!r}")
     H = plans[0].hist_len
@@ -399,7 +458,10 @@ def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progre
         s.wait_stream(stream)                      # the zeroed histograms
     b, n = strong_range(0, per_cell, rank, world)
     for ci, plan in enumerate(plans):
-        plan.launch(b, n, hists[ci].data_ptr(), streams[ci % len(streams)].cuda_stream)
+        if level == "class":
+            hists[ci] = torch.from_numpy(plan.run(b, n).astype(np.int64)).to(hists.device)
+        else:
+            plan.launch(b, n, hists[ci].data_ptr(), streams[ci % len(streams)].cuda_stream)
         if rank == 0 and progress:
             print(f"[{ci + 1}/{len(cells)}] N={cells[ci][0]} F={cells[ci][1]} queued", file=sys.stderr, flush=True)
     for s in streams[1:]:
@@ -413,8 +475,10 @@ def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progre
                        coin_common_word=byz.get("coin_common", 0))
             if delivery == "adversarial":
                 row.update(delivery=delivery)
+            if level == "class":
+                row.update(level=level)
     elapsed = time.perf_counter() - t0
-    for plan in plans:
+    for plan in plans if level == "node" else ():
         plan.check()                               # device-side capacity invariants of every cell
     return rows, elapsed
 
@@ -470,6 +534,9 @@ def main(argv=None) -> int:
                    help="byz, byzb: who composes a receiver's inbox: random (a uniform draw of N - F of the live senders) "
                         "or adversarial (a scheduler picks the N - F messages and the lies, BO_MODE_SCHED_TALLY and "
                         "BO_MODE_SCHED_RULE_B; needs --byz-strategy balance or split, allows --byzantine 0)")
+    t.add_argument("--level", choices=["node", "class"], default="node",
+                   help="byz, byzb with --delivery adversarial: node (one bit per node, N <= 4096) or class (the lumped "
+                        "chain over the two receiver parities, N <= 2**24; the same law, another random stream)")
     t.add_argument("--coin-common", type=float, default=None,
                    help="byz, byzb: a shared coin (BO_MODE_BYZ_COIN, BO_MODE_BYZ_RULE_B_COIN): the probability in [0, 1] "
                         "that a round's coin is common to all honest nodes (0: the mode without it)")
@@ -493,6 +560,9 @@ def main(argv=None) -> int:
     w.add_argument("--byz-one", type=float, default=None, help="byz, byzb: as in `trials` (default 0.5)")
     w.add_argument("--coin-common", type=float, default=None, help="byz, byzb: as in `trials`")
     w.add_argument("--delivery", choices=["random", "adversarial"], default="random", help="byz, byzb: as in `trials`")
+    w.add_argument("--level", choices=["node", "class"], default="node",
+                   help="byz, byzb with --delivery adversarial: node (one bit per node, N <= 4096) or class (the lumped "
+                        "chain over the two receiver parities, N <= 2**24; the same law, another random stream)")
     w.add_argument("--out", default=None)
     w.add_argument("--progress", action="store_true")
     a = ap.parse_args(argv)

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "benor.h"
+#include "benor_lumped.h"
 #include "benor_mfma_sched.h"
 #include "benor_mfma_strip.h"
 #include "benor_modes.h"
@@ -27,6 +28,7 @@ constexpr uint32_t kStreamReach = 9u;      // BO_MODE_CRASH_SUBSET: whether cras
 constexpr uint32_t kStreamLie = 10u;       // BO_MODE_BYZ_TALLY: a receiver's Binomial count of Byzantine messages that carry 1
 constexpr uint32_t kStreamHeard = 11u;     // ... BO_BYZ_BALANCE / BO_BYZ_SPLIT: how many of a receiver's messages are Byzantine (selection sampling)
 constexpr uint32_t kStreamCommonCoin = 12u; // BO_MODE_BYZ_COIN, BO_MODE_BYZ_RULE_B_COIN: a round's shared coin, keyed by trial and round
+// (13: lumped::kStreamBinom, benor_lumped.h -- the class-level chain's Binomial(n, 1/2) words)
 
 constexpr int kWavesPerBlock = 4;          // 256-thread workgroups, one trial per wave
 
@@ -260,6 +262,23 @@ int byz_blocks_per_cu(const KParams &p);
 hipError_t launch_tally_byz(const KParams &p, int grid_blocks, hipStream_t stream);
 int sched_blocks_per_cu(const KParams &p);        // benor_tally_sched.hip: under an adversarial scheduler
 hipError_t launch_tally_sched(const KParams &p, int grid_blocks, hipStream_t stream);
+
+// The class-level chain of the adversarial scheduler (bo_lumped_*, benor_lumped.hip): one lane
+// per trial, no KParams -- the chain has no planes, no live map and no BO_MAX_N.
+constexpr int kLumpedBlock = 256;                  // lanes (trials in flight) per workgroup
+struct LumpedParams {
+  lumped::Shape s;
+  uint32_t rule;                                   // 0: RuleRef, 1: RuleB
+  uint32_t coin_common;                            // 0: every coin local (the entries without stream 12)
+  uint32_t k_max, hist_len;
+  uint32_t init_mode, init0, init1;                // BO_INIT_FIXED: the honest nodes at 0 and at 1 (the rest "?")
+  uint64_t seed, trial_begin, trial_count;
+  unsigned long long *hist;                        // [hist_len] (device, accumulated)
+  bo_lumped_state *state_out;                      // (device) or nullptr; only with trial_count == 1
+  lumped::TableDir tables;                         // device pointers
+};
+int lumped_blocks_per_cu(const LumpedParams &p);   // resident workgroups per CU (0 = unknown)
+hipError_t launch_lumped(const LumpedParams &p, int grid_blocks, hipStream_t stream);
 
 // Event level for kMaxEventN < N <= BO_MAX_N (benor_event_big.hip): one wave per trial.
 // The wave-per-trial event kernel keeps its message pool in LDS when it is at

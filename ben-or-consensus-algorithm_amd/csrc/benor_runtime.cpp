@@ -540,6 +540,193 @@ int bo_byz_cdf(uint32_t b, uint32_t byz_one, uint64_t *thr_out, uint32_t cap, ui
   return BO_OK;
 }
 
+// ------------------------------------------ Binomial(2^k, 1/2) thresholds (host)
+// The lumped API's table of one k (include/benor.h).  n = 2^k, mode n / 2.  Weights by
+// the ratio recurrence pmf(x - 1) / pmf(x) = x / (n - x + 1) downward from the mode
+// (weight 1) over the window W = ceil(5 sqrt(n)) below it -- by Hoeffding the mass
+// beyond is under 2^-72 of the total, less than one unit of a threshold.  The law is
+// symmetric, so the total is twice the sum below the mode plus the mode's weight; the
+// lower half's running sums start at the far tail (small terms first), and the upper
+// half is the mirror image: CDF(x) = 1 - CDF(n - 1 - x), thr = 2^64 - ceil(.).  lgamma
+// is not used: at n = 2^24 it leaves eight digits.
+static void binom_half_row(uint32_t k, uint32_t &lo, std::vector<uint64_t> &thr) {
+  const uint32_t n = 1u << k, mode = n >> 1;
+  uint32_t W = (uint32_t)std::ceil(5.0 * std::sqrt((double)n)) + 1u;
+  if (W > mode) W = mode;
+  std::vector<long double> w(W + 1u);              // w[d]: the weight of x = mode - d
+  w[0] = 1.0L;
+  for (uint32_t d = 1; d <= W; ++d) {
+    const uint32_t x = mode - d + 1u;              // pmf(x - 1) = pmf(x) * x / (n - x + 1)
+    w[d] = w[d - 1u] * (long double)x / (long double)(n - x + 1u);
+  }
+  long double below = 0.0L;
+  for (uint32_t d = W; d >= 1u; --d) below += w[d];
+  const long double total = 2.0L * below + w[0];
+  std::vector<long double> cdf(W);                 // cdf[i] = CDF(mode - W + i), i < W: x below the mode
+  long double run = 0.0L;
+  for (uint32_t i = 0; i < W; ++i) {
+    run += w[W - i];
+    cdf[i] = run / total;
+  }
+  thr.clear();
+  lo = 0u;
+  bool any = false;
+  for (uint32_t i = 0; i < W; ++i) {               // the lower half: floor(CDF 2^64) < 2^63
+    const uint64_t t = (uint64_t)std::floor(std::ldexp(cdf[i], 64));
+    if (!any && t == 0u) continue;
+    if (!any) lo = mode - W + i, any = true;
+    thr.push_back(t);
+  }
+  if (!any) lo = mode;
+  for (uint32_t i = W; i-- > 0u;) {                // x = n - 1 - (mode - W + i) = mode, mode + 1, ..
+    const uint64_t c = (uint64_t)std::ceil(std::ldexp(cdf[i], 64));
+    if (c <= 1u) break;                            // saturated from here on
+    thr.push_back(0u - c);
+  }
+}
+
+int bo_binom_half_cdf(uint32_t k, uint32_t *lo_out, uint64_t *thr_out, uint32_t cap, uint32_t *n_out) {
+  if (!lo_out || !n_out) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (k < benor::lumped::kTableMinK || k > benor::lumped::kTableMaxK)
+    return fail(BO_ERR_INVALID_ARGUMENT, "bo_binom_half_cdf needs 7 <= k <= 24");
+  uint32_t lo = 0;
+  std::vector<uint64_t> thr;
+  binom_half_row(k, lo, thr);
+  if (thr.size() > cap || !thr_out) return fail(BO_ERR_INVALID_ARGUMENT, "bo_binom_half_cdf: thr_out is too short for the table");
+  *lo_out = lo;
+  *n_out = (uint32_t)thr.size();
+  std::memcpy(thr_out, thr.data(), sizeof(uint64_t) * thr.size());
+  return BO_OK;
+}
+
+// ------------------------------------------------------------- lumped API
+// The adversarial scheduler at the level of classes (include/benor.h):
+// validation is benor_lumped.h's, the kernel benor_lumped.hip's.  The tables of every
+// k are built once per process and uploaded once per device; they are never freed
+// (about 1 MB; freeing device memory while the process exits can race the runtime's teardown).
+namespace {
+struct LumpedTables {
+  std::vector<uint64_t> thr;
+  std::vector<uint32_t> dir;                       // off[kTables + 1], then lo[kTables]
+};
+
+const LumpedTables *lumped_tables() {
+  static const LumpedTables tables = [] {
+    LumpedTables t;
+    std::vector<uint32_t> off{0u}, lo;
+    std::vector<uint64_t> row;
+    for (uint32_t k = benor::lumped::kTableMinK; k <= benor::lumped::kTableMaxK; ++k) {
+      uint32_t l = 0;
+      binom_half_row(k, l, row);
+      t.thr.insert(t.thr.end(), row.begin(), row.end());
+      off.push_back((uint32_t)t.thr.size());
+      lo.push_back(l);
+    }
+    t.dir = off;
+    t.dir.insert(t.dir.end(), lo.begin(), lo.end());
+    return t;
+  }();
+  return &tables;
+}
+
+struct LumpedDevice {
+  int device;
+  unsigned char *d;                                // thr, then dir
+};
+std::mutex g_lumped_mu;
+std::vector<LumpedDevice> g_lumped_dev;
+
+int lumped_device_tables(int dev, benor::lumped::TableDir &out) {
+  const LumpedTables &t = *lumped_tables();
+  const size_t thr_bytes = sizeof(uint64_t) * t.thr.size(), dir_bytes = sizeof(uint32_t) * t.dir.size();
+  std::lock_guard<std::mutex> lock(g_lumped_mu);
+  unsigned char *d = nullptr;
+  for (const LumpedDevice &e : g_lumped_dev)
+    if (e.device == dev) d = e.d;
+  if (!d) {
+    HIP_TRY(hipMalloc(&d, thr_bytes + dir_bytes));
+    hipError_t e = hipMemcpy(d, t.thr.data(), thr_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + thr_bytes, t.dir.data(), dir_bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(d);
+      return hip_fail(e, "lumped tables upload");
+    }
+    g_lumped_dev.push_back({dev, d});
+  }
+  out.thr = reinterpret_cast<const uint64_t *>(d);
+  out.off = reinterpret_cast<const uint32_t *>(d + thr_bytes);
+  out.lo = out.off + benor::lumped::kTables + 1u;
+  return BO_OK;
+}
+
+int lumped_check(const bo_lumped_cfg *cfg) {
+  if (!cfg) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
+  const char *msg = "";
+  const int rc = benor::lumped::check(*cfg, &msg);
+  return rc ? fail(rc, msg) : BO_OK;
+}
+
+// Trials [begin, begin + count) added into hist (host); `state`: the one trial's final state.
+int lumped_launch(const bo_lumped_cfg *cfg, uint64_t begin, uint64_t count, uint64_t *hist, bo_lumped_state *state) {
+  int rc = lumped_check(cfg);
+  if (rc) return rc;
+  if (!hist && !state) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (count == 0u) return BO_OK;
+  int dev = 0;
+  rc = check_device(&dev);
+  if (rc) return rc;
+  benor::LumpedParams p;
+  std::memset(&p, 0, sizeof p);
+  p.s = benor::lumped::shape_of(*cfg);
+  p.rule = cfg->rule, p.coin_common = cfg->coin_common, p.k_max = cfg->k_max, p.hist_len = bo_hist_len(cfg->k_max);
+  p.init_mode = cfg->init_mode, p.init0 = cfg->init0, p.init1 = cfg->init1;
+  p.seed = cfg->seed;
+  rc = lumped_device_tables(dev, p.tables);
+  if (rc) return rc;
+  const uint32_t H = p.hist_len;
+  const size_t o_state = sizeof(uint64_t) * H;
+  unsigned char *d = nullptr;
+  HIP_TRY(hipMalloc(&d, o_state + sizeof(bo_lumped_state)));
+  p.hist = reinterpret_cast<unsigned long long *>(d);
+  p.state_out = state ? reinterpret_cast<bo_lumped_state *>(d + o_state) : nullptr;
+  hipError_t e = hipMemset(d, 0, o_state + sizeof(bo_lumped_state));
+  int cus = 0;
+  if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  int per_cu = (int)benor::knob_u32("BENOR_BLOCKS_PER_CU", 0u);
+  if (per_cu < 1) per_cu = benor::lumped_blocks_per_cu(p);
+  if (per_cu < 1) per_cu = 8;
+  for (uint64_t done = 0; e == hipSuccess && done < count; done += benor::kMaxTrialsPerLaunch) {
+    p.trial_begin = begin + done;
+    p.trial_count = std::min<uint64_t>(count - done, benor::kMaxTrialsPerLaunch);
+    const uint64_t want = (p.trial_count + benor::kLumpedBlock - 1u) / benor::kLumpedBlock;
+    const int grid = (int)std::min<uint64_t>(want, (uint64_t)std::max(1, cus) * per_cu);
+    e = benor::launch_lumped(p, grid, nullptr);
+  }
+  std::vector<uint64_t> h(H);
+  bo_lumped_state st;
+  if (e == hipSuccess) e = hipMemcpy(h.data(), d, o_state, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && state) e = hipMemcpy(&st, d + o_state, sizeof st, hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  if (e != hipSuccess) return hip_fail(e, "bo_lumped_run");
+  if (hist)
+    for (uint32_t i = 0; i < H; ++i) hist[i] += h[i];
+  if (state) *state = st;
+  return BO_OK;
+}
+}  // namespace
+
+int bo_lumped_check(const bo_lumped_cfg *cfg) { return lumped_check(cfg); }
+
+int bo_lumped_run(const bo_lumped_cfg *cfg, uint64_t trial_begin, uint64_t trial_count, uint64_t *hist_host) {
+  if (!hist_host) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
+  return lumped_launch(cfg, trial_begin, trial_count, hist_host, nullptr);
+}
+
+int bo_lumped_trial(const bo_lumped_cfg *cfg, uint64_t trial, bo_lumped_state *out) {
+  if (!out) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
+  return lumped_launch(cfg, trial, 1, nullptr, out);
+}
+
 // -------------------------------------------------------------- batch API
 // Validation and kernel planning of a trial configuration, host only: the
 // live-node map, the fixed-init plane and the KParams shape (no device fields).

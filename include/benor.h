@@ -636,6 +636,109 @@ int bo_tally_cdf(uint32_t m, uint32_t q, uint32_t K, uint32_t *lo_out,
  * number of Byzantine messages that carry 1, B1 = #{ j : thr[j] <= u }. */
 int bo_byz_cdf(uint32_t b, uint32_t byz_one, uint64_t *thr_out, uint32_t cap, uint32_t *n_out);
 
+/* ---- lumped API: the adversarial scheduler at the level of classes ----
+ *
+ * SCHED_TALLY and SCHED_RULE_B with nodes replaced by classes.  Under the adversarial
+ * scheduler a step's (c0, c1) takes one value per parity of the receiver's compact index,
+ * and every honest receiver of one parity applies the same rule to the same counts.  So in
+ * every round a whole parity class proposes, adopts or decides the same value, or takes the
+ * round's common coin, or each member takes its own local coin and the number of ones is
+ * Binomial(h_pi, 1/2).  A trial is a Markov chain on (a_0, a_1, dec_0, dec_1): a_pi = the
+ * honest nodes of parity pi with x = 1, dec_pi = the sticky decided flag of parity pi.  No
+ * faulty[] array, no per-node state, no BO_MAX_N: N up to 2^24, one trial per lane, a cost
+ * per trial-round that does not depend on N.  This is no BO_MODE_* and no BO_KERNEL_*:
+ * bo_trials_cfg, the modes 0..13 and the variants 0..21 are as they were.
+ *
+ * A configuration: N, F, f crashed and b Byzantine nodes, byz_even of the Byzantine nodes at
+ * an even compact index (compact indices: the m = N - f live nodes in ascending node id),
+ * the rule (0: the reference's, SCHED_TALLY's; 1: Protocol B, SCHED_RULE_B's), the strategy
+ * (BO_BYZ_BALANCE or BO_BYZ_SPLIT), coin_common, k_max, the seed and the initial values.
+ * Derived: q = N - F, h_0 = ceil(m / 2) - byz_even, h_1 = floor(m / 2) - (b - byz_even),
+ * h = h_0 + h_1 (>= q >= 1).
+ *
+ * Round r, for pi in {0, 1}:
+ *   R-phase.  The honest class sizes (H0, H1, Hq): in round 1 the initial values'; later
+ *     H1 = a_0 + a_1, H0 = h - H1, Hq = 0.  Parity pi's counts are SCHED_TALLY's closed form
+ *     for a receiver c with c & 1 = pi -- push(pi) under SPLIT, even() under BALANCE, with
+ *     (q, H0, H1, Hq, b) -- and it proposes by the rule's R-step: the reference's 0 if c0 > c1,
+ *     1 if c1 > c0, else "?"; Protocol B's 0 if 2 c0 > N + F, 1 if 2 c1 > N + F, else "?".  Its
+ *     h_pi members all propose alike.
+ *   P-phase.  The class sizes are those of the two proposals, weighted by h_pi; the counts
+ *     are the same closed forms; the rule's P-step follows (the reference's: c0 > F decides 0,
+ *     else c1 > F decides 1, else the strict majority, else the coin; Protocol B's: the strict
+ *     majority v with c_v > F is adopted, and decided iff 2 c_v > N + F, else the coin).  A
+ *     parity that adopts or decides v gets a_pi = v h_pi, and dec_pi sticks on a deciding
+ *     count.  If a parity with h_pi > 0 takes the coin, the round's stream-12 block is read
+ *     exactly as BYZ_COIN reads it (coin_common == 0 draws none; common iff coin_common ==
+ *     UINT32_MAX or out[0] < coin_common, the bit out[1] & 1): in a common round with bit v,
+ *     a_pi = v h_pi; otherwise a_pi ~ Binomial(h_pi, 1/2), drawn as below.
+ *   Halting and outcome.  The trial stops after the round in which dec_pi holds for every
+ *     parity with h_pi > 0, or after k_max rounds.  K = a_0 + a_1 of the h honest nodes hold 1;
+ *     the bins are those of every batch mode, over bo_hist_len(k_max).
+ * Initial values: BO_INIT_RANDOM draws H1 ~ Binomial(h, 1/2), H0 = h - H1, Hq = 0;
+ * BO_INIT_FIXED gives the three counts init0 + init1 + initq = h.  Only the totals matter:
+ * round 1's proposals do not read a node's own x, and every x is rewritten in its P-phase.
+ *
+ * The Binomial(n, 1/2) draw (Philox stream 13), exact up to the rounding of 64-bit
+ * thresholds.  n = the sum of 2^k over its set bits, and the draw is the sum of independent
+ * B_k ~ Binomial(2^k, 1/2) over them.  The set bits are taken in ascending k; the j-th set
+ * bit (j = 0, 1, ..) uses the j-th 64-bit word of the draw.  Parity pi's draw in round r reads
+ * the Philox4x32-10 blocks ctr = {trial_lo, trial_hi, 16 pi + (j >> 1), r | 13 << 24}, key =
+ * seed; word j is out[1] << 32 | out[0] for even j and out[3] << 32 | out[2] for odd j (stream
+ * 5's convention).  n < 2^25 has at most 25 set bits: 13 blocks, below 16.  The initial draw
+ * is parity 0's with n = h and r = 0.  No word is used twice, and the word of a clear bit is
+ * never drawn.  From a word u: for k <= 6, B_k = popcount(u & (2^(2^k) - 1)) (the whole word
+ * at k = 6); for 7 <= k <= 24, B_k = lo_k + #{ i : thr_k[i] <= u }, the table of
+ * bo_binom_half_cdf.
+ *
+ * The law over histograms is that of SCHED_TALLY / SCHED_RULE_B for the same (N, F, f, b,
+ * placement parity) with thresholds rounded at 2^-64; the random stream, and so each seed's
+ * outcome, differs -- unless no local coin and no random start is drawn (fixed initial
+ * values with coin_common == UINT32_MAX: stream 12 is shared, no stream-13 word is read),
+ * where every trial's bins and round count are those modes'.  Not modelled: per-node
+ * states, the network API, the strategies BO_BYZ_RANDOM and BO_BYZ_OPPOSE, random delivery. */
+typedef struct bo_lumped_cfg {
+    uint32_t N, F;            /* network size, 1..2^24; fault parameter, F < N (quorum N-F) */
+    uint32_t f, b;            /* crashed from the start; Byzantine; f + b <= F */
+    uint32_t byz_even;        /* the Byzantine nodes at an even compact index: <= min(b, ceil(m/2)), b - byz_even <= floor(m/2) */
+    uint32_t rule;            /* 0: the reference's rule (SCHED_TALLY), 1: Protocol B (SCHED_RULE_B) */
+    uint32_t strategy;        /* BO_BYZ_BALANCE or BO_BYZ_SPLIT */
+    uint32_t coin_common;     /* the probability, in units of 2^-32, that a round's coin is common (0: never, UINT32_MAX: certainly) */
+    uint32_t k_max;           /* round cap, 1..BO_MAX_K */
+    uint32_t init_mode;       /* BO_INIT_RANDOM: H1 ~ Binomial(h, 1/2); BO_INIT_FIXED: the three counts below */
+    uint32_t init0, init1, initq;   /* BO_INIT_FIXED: honest nodes that start at 0, 1 and "?"; their sum is h */
+    uint32_t reserved;        /* not read */
+    uint64_t seed;            /* Philox4x32-10 key */
+} bo_lumped_cfg;
+
+typedef struct bo_lumped_state {
+    uint32_t a[2];            /* honest nodes of even / odd compact index with x = 1 at the end */
+    uint8_t dec[2];           /* whether that parity has decided (0 for a parity without an honest node) */
+    uint8_t pad[2];
+    uint32_t rounds;          /* the round in which every parity had decided, 0 if k_max ran out first */
+} bo_lumped_state;
+
+/* Validate a configuration.  Host only, no device needed; the error text names what is wrong. */
+int bo_lumped_check(const bo_lumped_cfg *cfg);
+
+/* Run global trial ids [trial_begin, trial_begin + trial_count) and ADD their outcomes into
+ * hist_host (bo_hist_len(k_max) uint64).  Blocking, on the current device.  A trial's outcome
+ * depends on its id alone: not on the launch split, the grid or the lane that ran it. */
+int bo_lumped_run(const bo_lumped_cfg *cfg, uint64_t trial_begin, uint64_t trial_count, uint64_t *hist_host);
+
+/* The final state of one trial, from a one-trial launch. */
+int bo_lumped_trial(const bo_lumped_cfg *cfg, uint64_t trial, bo_lumped_state *out);
+
+/* The thresholds of Binomial(2^k, 1/2), 7 <= k <= 24: thr_out[i] = min(2^64 - 1,
+ * floor(CDF(lo + i) * 2^64)), trimmed to the counts whose threshold is neither 0 nor
+ * saturated (*lo_out = the first of them, *n_out their number; BO_ERR_INVALID_ARGUMENT if
+ * cap is short or k is outside 7..24).  Built by the pmf's ratio recurrence outward from
+ * the mode in long double, the lower half summed from the tail and normalised by the
+ * symmetric total, the upper half its mirror image 2^64 - ceil(.).  A draw u (uniform 64
+ * bits) gives the count lo + #{ i : thr[i] <= u }.  Exactly what bo_lumped_run uploads.
+ * Host only, no device needed. */
+int bo_binom_half_cdf(uint32_t k, uint32_t *lo_out, uint64_t *thr_out, uint32_t cap, uint32_t *n_out);
+
 /* ---- diagnostics ---- */
 
 /* Time the v_bcnt_u32_b32 peak microbenchmark: returns popcount words/s

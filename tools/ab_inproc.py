@@ -76,6 +76,16 @@ draws; rounds per trial differ by design, so compare node_rounds_per_s:
     python tools/ab_inproc.py --rounds 5 --reps 3 --shapes "1024,204,100000,0" --variants \
         "m11=mode:byzb,byzantine:16,byz_strategy:split,coin_common:all;m13=mode:byzb,byzantine:16,byz_strategy:split,coin_common:all,delivery:adversarial"
 
+`level:class` on such a line runs the scheduler at the level of classes (benor.LumpedPlan, the lumped chain of
+DESIGN §4.3.12: same law, another random stream, any N up to 2**24).  Its launches are the blocking bo_lumped_run,
+so its time per launch includes that call's allocation and read-back; every line reports ns_per_trial_round, the
+figure to compare across levels.  Alone it times sizes the node level cannot hold:
+
+    python tools/ab_inproc.py --rounds 5 --reps 3 --shapes "4096,819,200000,0" --variants \
+        "m13=mode:byzb,byzantine:16,byz_strategy:balance,delivery:adversarial;cls=mode:byzb,byzantine:16,byz_strategy:balance,delivery:adversarial,level:class"
+    python tools/ab_inproc.py --rounds 5 --reps 3 --shapes "16777216,3355443,1000000,0" --variants \
+        "cls=mode:byzb,byzantine:16,byz_strategy:balance,delivery:adversarial,level:class"
+
 Every line also reports
 the live node-rounds per second its launches represent (bench.py node_rounds)
 and the rounds a trial ran on average (k_max for an undecided one),
@@ -118,7 +128,7 @@ def main():
         shapes.append((v[0], v[1], v[2], v[3] if len(v) > 3 else v[1]))
     modes = {name: env.pop("mode", None) for name, env in variants}   # `mode` is no environment variable
     scheds = {name: {k: env.pop(k) for k in ("crash_count", "crash_window", "crash_at", "crash_cut", "crash_reach",
-                                             "byzantine", "byz_one", "byz_strategy", "coin_common", "delivery")
+                                             "byzantine", "byz_one", "byz_strategy", "coin_common", "delivery", "level")
                      if k in env}
               for name, env in variants}                              # ... nor is the crash schedule
     knobs = sorted({k for _, env in variants for k in env})
@@ -135,13 +145,17 @@ def main():
     bad = sorted({v for v in modes.values() if v is not None and v not in mode_ids})
     if bad:
         ap.error(f"mode must be one of {sorted(mode_ids)}: {bad}")
-    byz_keys = ("byzantine", "byz_one", "byz_strategy", "coin_common", "delivery")
+    byz_keys = ("byzantine", "byz_one", "byz_strategy", "coin_common", "delivery", "level")
     if any(any(k in sc for k in byz_keys) != (modes[name] in ("byz", "byzb")) for name, sc in scheds.items()):
         ap.error("byzantine / byz_one / byz_strategy go with mode:byz or mode:byzb, and they with them")
     if any(sc.get("delivery", "random") not in ("random", "adversarial") for sc in scheds.values()):
         ap.error("delivery is random or adversarial")
     if any(sc.get("delivery") == "adversarial" and sc.get("byz_strategy") not in ("balance", "split") for sc in scheds.values()):
         ap.error("delivery:adversarial needs byz_strategy:balance or byz_strategy:split")
+    if any(sc.get("level", "node") not in ("node", "class") for sc in scheds.values()):
+        ap.error("level is node or class")
+    if any(sc.get("level") == "class" and sc.get("delivery") != "adversarial" for sc in scheds.values()):
+        ap.error("level:class needs delivery:adversarial")
     if any(any(k not in byz_keys for k in sc) and modes[name] not in ("crash", "partial", "subset")
            for name, sc in scheds.items()):
         ap.error("crash_count / crash_window / crash_at need mode:crash, mode:partial or mode:subset")
@@ -180,6 +194,24 @@ def main():
     import numpy as np
     import torch
 
+    class ClassLevel:
+        """A LumpedPlan behind TrialsPlan's launch: blocking, its histograms kept on the host until take()."""
+
+        def __init__(self, name, N, F, f):
+            kw = schedule(name, N, f)
+            self.plan = benor.LumpedPlan(N, F, f=f, b=sum(kw["byzantine"]), byz_even=(sum(kw["byzantine"]) + 1) // 2,
+                                         rule=1 if modes[name] == "byzb" else 0, byz_strategy=kw["byz_strategy"],
+                                         coin_common=kw.get("coin_common", 0), seed=0x5EED + N, k_max=32)
+            self.hist_len = self.plan.hist_len
+            self.host = np.zeros(self.hist_len, dtype=np.uint64)
+
+        def launch(self, begin, count, hist_ptr, stream_ptr):
+            self.host += self.plan.run(begin, count)
+
+        def take(self):
+            h, self.host = self.host, np.zeros(self.hist_len, dtype=np.uint64)
+            return torch.from_numpy(h.astype(np.int64)).cuda()
+
     sys.path.insert(0, ROOT)
     from bench import node_rounds
 
@@ -202,6 +234,8 @@ def main():
             if scheds[name].get("delivery") == "adversarial":
                 mode = benor.BO_MODE_SCHED_TALLY if modes[name] == "byz" else benor.BO_MODE_SCHED_RULE_B
             key = (mode, tuple(sorted(scheds[name].items())))
+            if key not in plans and scheds[name].get("level") == "class":
+                plans[key] = ClassLevel(name, N, F, f)
             if key not in plans:
                 plans[key] = benor.TrialsPlan(N, F, [i < f for i in range(N)], seed=0x5EED + N, k_max=32, mode=mode,
                                               **schedule(name, N, f))
@@ -211,6 +245,9 @@ def main():
             set_env(env)
             plans[name].launch(0, max(1, T // 10), h.data_ptr(), st.cuda_stream)
         torch.cuda.synchronize()
+        for plan in plans.values():
+            if isinstance(plan, ClassLevel):
+                plan.take()
         nxt = T
         for rnd in range(a.rounds):
             order = variants[rnd % len(variants):] + variants[:rnd % len(variants)]
@@ -225,6 +262,8 @@ def main():
                 e1.record(st)
                 torch.cuda.synchronize()
                 ms = e0.elapsed_time(e1) / a.reps
+                if isinstance(plans[name], ClassLevel):
+                    h += plans[name].take()
                 times.setdefault((N, F, T, f, name), []).append(ms)
                 nr, tr = node_rounds(h.cpu().numpy().astype(np.uint64), N - f, 32)
                 work.setdefault((N, F, T, f, name), []).append(nr / a.reps / (ms * 1e-3))
@@ -239,6 +278,9 @@ def main():
                               "median_vs_first": statistics.median(t) / base,
                               "trials_per_s": T / (statistics.median(t) * 1e-3),
                               "us_per_trial": statistics.median(t) * 1e3 / T, **scheds[name],
+                              "ns_per_trial_round": statistics.median(t) * 1e6 / T / statistics.median(length[(N, F, T, f, name)]),
+                              "ns_per_trial_round_min": min(t) * 1e6 / T / statistics.median(length[(N, F, T, f, name)]),
+                              "ns_per_trial_round_max": max(t) * 1e6 / T / statistics.median(length[(N, F, T, f, name)]),
                               "node_rounds_per_s": statistics.median(work[(N, F, T, f, name)]),
                               "rounds_per_trial": statistics.median(length[(N, F, T, f, name)]),
                               "kernel_version": benor.kernel_version()}), flush=True)
