@@ -149,6 +149,8 @@ EXPORTED_SYMBOLS = (
     "bo_consensus_start_live", "bo_consensus_wait", "bo_live_stop_events", "bo_get_states", "bo_consensus_poll",
     "bo_tally_cdf", "bo_byz_cdf",
     "bo_lumped_check", "bo_lumped_run", "bo_lumped_trial", "bo_binom_half_cdf",
+    "bo_rule_protocol_a", "bo_rule_protocol_b", "bo_plan_create_rule", "bo_run_trial_states_rule", "bo_plan_rule",
+    "bo_lumped_check_rule", "bo_lumped_run_rule", "bo_lumped_trial_rule",
 )
 
 
@@ -182,6 +184,63 @@ class LumpedCfgC(ctypes.Structure):
 class LumpedStateC(ctypes.Structure):
     _fields_ = [("a", ctypes.c_uint32 * 2), ("dec", ctypes.c_uint8 * 2), ("pad", ctypes.c_uint8 * 2),
                 ("rounds", ctypes.c_uint32)]
+
+
+class Rule(ctypes.Structure):
+    """bo_rule: a threshold rule on a receiver's counts (c0, c1), three words (include/benor.h).
+    With v the value of the strictly larger count: propose v iff 2 c_v > propose_gt2; adopt v iff c_v > adopt_gt and
+    decide iff also 2 c_v > decide_gt2, else the coin.  The library validates the words."""
+    _fields_ = [("propose_gt2", ctypes.c_uint32), ("adopt_gt", ctypes.c_uint32), ("decide_gt2", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+    @property
+    def words(self) -> tuple:
+        return (int(self.propose_gt2), int(self.adopt_gt), int(self.decide_gt2))
+
+    def __eq__(self, other):
+        return isinstance(other, Rule) and self.words == other.words and self.reserved == other.reserved
+
+    def __hash__(self):
+        return hash((self.words, int(self.reserved)))
+
+    def __repr__(self):
+        return "Rule(propose_gt2=%d, adopt_gt=%d, decide_gt2=%d)" % self.words
+
+
+def _rule(thresholds) -> Rule:
+    """thresholds=: a Rule, or its three words (propose_gt2, adopt_gt, decide_gt2)."""
+    if isinstance(thresholds, Rule):
+        return thresholds
+    words = tuple(thresholds)
+    if len(words) != 3:
+        raise ValueError("thresholds is a benor.Rule or its three words (propose_gt2, adopt_gt, decide_gt2)")
+    for name, v in zip(("propose_gt2", "adopt_gt", "decide_gt2"), words):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 0xFFFFFFFF:
+            raise ValueError(f"{name} is an unsigned 32-bit word, got {v!r}")
+    return Rule(*words, 0)
+
+
+def rule_check(thresholds) -> Rule:
+    """The library's validation of a rule's words, without a plan (bo_lumped_check_rule on a one-node
+    configuration, whose own words are valid; host only).  Returns the Rule."""
+    rule = _rule(thresholds)
+    one = LumpedCfgC(N=1, F=0, strategy=BYZ_BALANCE, k_max=1)
+    _check(lib().bo_lumped_check_rule(ctypes.byref(one), ctypes.byref(rule)))
+    return rule
+
+
+def rule_protocol_a(N: int, F: int) -> Rule:
+    """Ben-Or's crash-tolerant Protocol A (N > 2F) as a threshold rule: (N, 0, 2F) (bo_rule_protocol_a; host only)."""
+    r = Rule()
+    _check(lib().bo_rule_protocol_a(N, F, ctypes.byref(r)))
+    return r
+
+
+def rule_protocol_b(N: int, F: int) -> Rule:
+    """Protocol B, BO_MODE_BYZ_RULE_B's rule, as a threshold rule: (N + F, F, N + F) (bo_rule_protocol_b; host only)."""
+    r = Rule()
+    _check(lib().bo_rule_protocol_b(N, F, ctypes.byref(r)))
+    return r
 
 
 def _crash_array(N, crash_at):
@@ -251,6 +310,15 @@ def lib() -> ctypes.CDLL:
     L.bo_lumped_trial.argtypes = [P(LumpedCfgC), ctypes.c_uint64, P(LumpedStateC)]
     L.bo_binom_half_cdf.argtypes = [ctypes.c_uint32, P(ctypes.c_uint32), P(ctypes.c_uint64), ctypes.c_uint32,
                                     P(ctypes.c_uint32)]
+    L.bo_rule_protocol_a.argtypes = [ctypes.c_uint32, ctypes.c_uint32, P(Rule)]
+    L.bo_rule_protocol_b.argtypes = [ctypes.c_uint32, ctypes.c_uint32, P(Rule)]
+    L.bo_plan_create_rule.argtypes = [P(TrialsCfgC), P(Rule), P(ctypes.c_void_p)]
+    L.bo_run_trial_states_rule.argtypes = [P(TrialsCfgC), P(Rule), ctypes.c_uint64, P(NodeStateC), ctypes.c_uint32]
+    L.bo_plan_rule.argtypes = [ctypes.c_void_p, P(Rule)]
+    L.bo_plan_rule.restype = ctypes.c_int
+    L.bo_lumped_check_rule.argtypes = [P(LumpedCfgC), P(Rule)]
+    L.bo_lumped_run_rule.argtypes = [P(LumpedCfgC), P(Rule), ctypes.c_uint64, ctypes.c_uint64, P(ctypes.c_uint64)]
+    L.bo_lumped_trial_rule.argtypes = [P(LumpedCfgC), P(Rule), ctypes.c_uint64, P(LumpedStateC)]
     L.bo_last_error.restype = ctypes.c_char_p
     L.bo_abi_version.restype = ctypes.c_int
     L.bo_kernel_version.restype = ctypes.c_char_p
@@ -626,7 +694,9 @@ class TrialsPlan:
                  mode: int = BO_MODE_LOCKSTEP, crash_at: Sequence | None = None, crash_count: int = 0,
                  crash_window: int = 0, crash_cut: int = 0, crash_reach: int | None = None,
                  byzantine: Sequence[bool] | None = None, byz_one: int | None = None,
-                 byz_strategy: int | None = None, coin_common: int | None = None):
+                 byz_strategy: int | None = None, coin_common: int | None = None, thresholds=None):
+        """thresholds: a benor.Rule (or its three words) that replaces Protocol B's rule on a plan of mode 9, 11 or
+        13 (bo_plan_create_rule): rule_protocol_a(N, F) runs Ben-Or's Protocol A there."""
         self.N, self.F, self.k_max, self.seed = N, F, k_max, seed
         self.mode = mode
         self._cfg, self._keep = _trials_cfg(N, F, faulty, seed=seed, k_max=k_max, initial_values=initial_values,
@@ -635,7 +705,11 @@ class TrialsPlan:
                                             byzantine=byzantine, byz_one=byz_one, byz_strategy=byz_strategy,
                                             coin_common=coin_common)
         h = ctypes.c_void_p()
-        _check(lib().bo_plan_create(ctypes.byref(self._cfg), ctypes.byref(h)))
+        if thresholds is None:
+            _check(lib().bo_plan_create(ctypes.byref(self._cfg), ctypes.byref(h)))
+        else:
+            rule = _rule(thresholds)
+            _check(lib().bo_plan_create_rule(ctypes.byref(self._cfg), ctypes.byref(rule), ctypes.byref(h)))
         self._h = h
 
     def __del__(self):
@@ -656,6 +730,15 @@ class TrialsPlan:
     def kernel(self) -> int:
         """BO_KERNEL_* family of this plan's batch launches (bo_plan_kernel)."""
         return lib().bo_plan_kernel(self._h)
+
+    @property
+    def rule(self) -> Rule | None:
+        """The threshold rule that replaces the plan's own (bo_plan_rule), or None."""
+        r = Rule()
+        rc = lib().bo_plan_rule(self._h, ctypes.byref(r))
+        if rc < 0:
+            _check(-rc)
+        return r if rc else None
 
     @property
     def hist_len(self) -> int:
@@ -685,8 +768,10 @@ def run_trial_states(N: int, F: int, faulty: Sequence[bool], *, seed: int = 0, t
                      mode: int = BO_MODE_LOCKSTEP, crash_at: Sequence | None = None, crash_count: int = 0,
                      crash_window: int = 0, crash_cut: int = 0, crash_reach: int | None = None,
                      byzantine: Sequence[bool] | None = None, byz_one: int | None = None,
-                     byz_strategy: int | None = None, coin_common: int | None = None):
-    """Per-node final states of one trial: (rounds, [NodeState dict] * N)."""
+                     byz_strategy: int | None = None, coin_common: int | None = None, thresholds=None):
+    """Per-node final states of one trial: (rounds, [NodeState dict] * N).  thresholds: as TrialsPlan's
+    (bo_run_trial_states_rule; the rounds are then read off the states: k - 1 of the honest nodes if all of them
+    have decided, else 0)."""
     crash_window = _coin_word(mode, crash_window, coin_common)
     crash_cut = _cut_word(crash_cut, crash_reach)
     crash_cut, crash_count = _byz_words(mode, crash_cut, crash_count, byzantine, byz_one, byz_strategy)
@@ -703,6 +788,12 @@ def run_trial_states(N: int, F: int, faulty: Sequence[bool], *, seed: int = 0, t
                      ctypes.cast(init, ctypes.POINTER(ctypes.c_int8)),
                      ctypes.cast(ca, ctypes.POINTER(ctypes.c_uint32)) if ca else None, crash_count, crash_window)
     st = (NodeStateC * max(1, N))()
+    if thresholds is not None:
+        rule = _rule(thresholds)
+        _check(lib().bo_run_trial_states_rule(ctypes.byref(cfg), ctypes.byref(rule), trial, st, N))
+        states = [_state_dict(st[i]) for i in range(N)]
+        ran = [s for s in states if s["k"] is not None]          # the honest nodes
+        return (ran[0]["k"] - 1 if ran and all(s["decided"] for s in ran) else 0), states
     rounds = ctypes.c_uint32(0)
     _check(lib().bo_run_trial_states(ctypes.byref(cfg), trial, st, ctypes.byref(rounds)))
     return int(rounds.value), [_state_dict(st[i]) for i in range(N)]
@@ -757,7 +848,9 @@ class LumpedPlan:
 
     def __init__(self, N: int, F: int, *, f: int = 0, b: int = 0, byz_even: int = 0, rule: int = 0,
                  byz_strategy: int = BYZ_BALANCE, coin_common: int = 0, seed: int = 0, k_max: int = DEFAULT_K_MAX,
-                 initial_values: Sequence[int] | None = None):
+                 initial_values: Sequence[int] | None = None, thresholds=None):
+        """thresholds: a benor.Rule (or its three words) in the place of `rule`, which is then not read
+        (bo_lumped_*_rule)."""
         words = dict(N=N, F=F, f=f, b=b, byz_even=byz_even, rule=rule, strategy=byz_strategy, coin_common=coin_common,
                      k_max=k_max)
         init = (0, 0, 0) if initial_values is None else tuple(initial_values)
@@ -772,7 +865,11 @@ class LumpedPlan:
         self.N, self.F, self.k_max, self.seed = N, F, k_max, seed
         self._cfg = LumpedCfgC(init_mode=BO_INIT_RANDOM if initial_values is None else BO_INIT_FIXED, reserved=0,
                                seed=seed, **words)
-        _check(lib().bo_lumped_check(ctypes.byref(self._cfg)))
+        self.rule = None if thresholds is None else _rule(thresholds)
+        if self.rule is None:
+            _check(lib().bo_lumped_check(ctypes.byref(self._cfg)))
+        else:
+            _check(lib().bo_lumped_check_rule(ctypes.byref(self._cfg), ctypes.byref(self.rule)))
 
     @property
     def hist_len(self) -> int:
@@ -782,14 +879,20 @@ class LumpedPlan:
         import numpy as np
 
         h = np.zeros(self.hist_len, dtype=np.uint64)
-        _check(lib().bo_lumped_run(ctypes.byref(self._cfg), trial_begin, trial_count,
-                                   h.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        hp = h.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        if self.rule is None:
+            _check(lib().bo_lumped_run(ctypes.byref(self._cfg), trial_begin, trial_count, hp))
+        else:
+            _check(lib().bo_lumped_run_rule(ctypes.byref(self._cfg), ctypes.byref(self.rule), trial_begin, trial_count, hp))
         return h
 
     def trial(self, trial: int) -> dict:
         """One trial's final state: {"a": (a_0, a_1), "dec": (dec_0, dec_1), "rounds": R or 0}."""
         st = LumpedStateC()
-        _check(lib().bo_lumped_trial(ctypes.byref(self._cfg), trial, ctypes.byref(st)))
+        if self.rule is None:
+            _check(lib().bo_lumped_trial(ctypes.byref(self._cfg), trial, ctypes.byref(st)))
+        else:
+            _check(lib().bo_lumped_trial_rule(ctypes.byref(self._cfg), ctypes.byref(self.rule), trial, ctypes.byref(st)))
         return {"a": (int(st.a[0]), int(st.a[1])), "dec": (bool(st.dec[0]), bool(st.dec[1])), "rounds": int(st.rounds)}
 
 

@@ -21,6 +21,8 @@
                                                                           # an adversarial scheduler, no Byzantine node
     python -m benor.cli trials --N 16777216 --F 9000 --mode byz --crashed 0 --byz-strategy balance --delivery adversarial --level class
                                                                           # ... at the level of classes: N up to 2**24
+    python -m benor.cli trials --N 64 --F 20 --mode byzb --crashed 0 --byz-strategy split --delivery adversarial --rule a
+                                                                          # Ben-Or's Protocol A under the scheduler (--rule b, --rule P:A:D)
     python -m benor.cli sweep --N 64,128,...,4096 --steps 32 --trials 2**30 --out sweep.csv
                                                                           # C5 phase diagram
     python -m benor.cli sweep --cells 4096:0,4096:1984 --per-cell 4793490  # two cells of it
@@ -50,6 +52,8 @@ placed as `trials` places them: the first f nodes crashed, the next b Byzantine.
 byz_one_word and coin_common_word.  `--level class` (with `--delivery adversarial`) runs
 `trials` and `sweep` on the lumped chain (benor.LumpedPlan): the same
 placement, N up to 2**24, a `level` field or column; `--level node` is the default.
+`--rule a|b|P:A:D` (with `--mode byzb`, at either delivery and level) replaces Protocol B's rule
+by a threshold rule of three words (a: Protocol A) and adds a `rule` field or column.
 """
 from __future__ import annotations
 
@@ -144,6 +148,35 @@ def check_level(a, adversarial: bool) -> bool:
     return True
 
 
+def check_rule(a):
+    """--rule of `trials` and `sweep`: None, "a" or "b" (Protocol A's or Protocol B's words at each
+    shape's (N, F)), or the three words (P, A, D).  It replaces Protocol B's rule, so it goes with --mode byzb, at
+    either --delivery and --level.  Its argument errors need no device."""
+    if a.rule is None:
+        return None
+    if a.mode != "byzb":
+        raise SystemExit("--rule needs --mode byzb (it replaces Protocol B's rule)")
+    if a.rule in ("a", "b"):
+        return a.rule
+    parts = a.rule.split(":")
+    if len(parts) != 3 or not all(p.isdigit() for p in parts):
+        raise SystemExit("--rule is a, b or three words P:A:D (propose_gt2:adopt_gt:decide_gt2)")
+    import benor
+
+    return benor.rule_check(tuple(int(p) for p in parts)).words     # the library's check of the words
+
+
+def rule_of(rule, benor, N: int, F: int):
+    """The benor.Rule of a checked --rule at a shape."""
+    if rule == "a":
+        return benor.rule_protocol_a(N, F)
+    return benor.rule_protocol_b(N, F) if rule == "b" else benor.Rule(*rule, 0)
+
+
+def rule_text(rule) -> str:
+    return rule if isinstance(rule, str) else ":".join(str(w) for w in rule)
+
+
 def lumped_words(a, benor, crashed: int, b: int) -> dict:
     """LumpedPlan's words for the placement `trials` and `sweep` use: the first `crashed` nodes crashed, the next b
     Byzantine -- the compact indices 0 .. b - 1, ceil(b / 2) of them even."""
@@ -174,8 +207,9 @@ def cmd_trials(a) -> int:
             "byzb": benor.BO_MODE_BYZ_RULE_B}[a.mode]
     crashed = a.F if a.crashed is None else a.crashed            # the first f nodes (start.ts:7-18 placement)
     adversarial = check_delivery(a)
+    rule = check_rule(a)
     if check_level(a, adversarial):
-        return trials_class(a, benor, crashed)
+        return trials_class(a, benor, crashed, rule)
     sched = {}
     if a.mode in ("crash", "partial", "subset"):                  # crashes during the run, in steps
         if a.crash_at and a.crash_count:
@@ -214,6 +248,8 @@ def cmd_trials(a) -> int:
         raise SystemExit("--byzantine needs --mode byz or --mode byzb")
     elif a.coin_common is not None:
         raise SystemExit("--coin-common needs --mode byz or --mode byzb")
+    if rule is not None:                                          # a threshold rule on mode byzb's plan
+        sched["thresholds"] = rule_of(rule, benor, a.N, a.F)
     plan = benor.TrialsPlan(a.N, a.F, [i < crashed for i in range(a.N)], seed=a.seed, k_max=a.k_max, mode=mode,
                             **sched)
     t0 = time.perf_counter()
@@ -236,13 +272,16 @@ def cmd_trials(a) -> int:
             row.update(coin_common=a.coin_common, coin_common_word=sched["coin_common"])
         if adversarial:
             row.update(delivery=a.delivery)
+        if rule is not None:
+            row.update(rule=rule_text(rule), rule_words=list(sched["thresholds"].words))
     row["seconds"] = dt
     print(json.dumps(row))
     return 0
 
 
-def trials_class(a, benor, crashed: int) -> int:
-    """`trials --level class`: the batch on the lumped chain, the row of the node level plus a level field."""
+def trials_class(a, benor, crashed: int, rule=None) -> int:
+    """`trials --level class`: the batch on the lumped chain, the row of the node level plus a level field (and with
+    --rule its rule fields)."""
     if not 0.0 <= a.byz_one <= 1.0:
         raise SystemExit("--byz-one is a probability in [0, 1]")
     if a.coin_common is not None and not 0.0 <= a.coin_common <= 1.0:
@@ -250,7 +289,8 @@ def trials_class(a, benor, crashed: int) -> int:
     if not 0 <= a.byzantine <= a.N - crashed:
         raise SystemExit("--byzantine counts live nodes: 0 .. N - crashed")
     words = lumped_words(a, benor, crashed, a.byzantine)
-    plan = benor.LumpedPlan(a.N, a.F, seed=a.seed, k_max=a.k_max, **words)
+    thresholds = None if rule is None else rule_of(rule, benor, a.N, a.F)
+    plan = benor.LumpedPlan(a.N, a.F, seed=a.seed, k_max=a.k_max, thresholds=thresholds, **words)
     t0 = time.perf_counter()
     h = plan.run(a.begin, a.trials)
     dt = time.perf_counter() - t0
@@ -259,7 +299,10 @@ def trials_class(a, benor, crashed: int) -> int:
                byz_even=words["byz_even"], byz_strategy=a.byz_strategy)
     if a.coin_common is not None:
         row.update(coin_common=a.coin_common, coin_common_word=words["coin_common"])
-    row.update(delivery=a.delivery, level=a.level, seconds=dt)
+    row.update(delivery=a.delivery, level=a.level)
+    if rule is not None:
+        row.update(rule=rule_text(rule), rule_words=list(plan.rule.words))
+    row.update(seconds=dt)
     print(json.dumps(row))
     return 0
 
@@ -305,6 +348,7 @@ def cmd_sweep(a) -> int:
     byz = a.mode in ("byz", "byzb")
     adversarial = check_delivery(a)
     level_class = check_level(a, adversarial)
+    rule = check_rule(a)
     if not byz and (a.coin_common is not None or a.byz_steps is not None or a.byz_strategy is not None or
                     a.byz_one is not None):
         raise SystemExit("--byz-steps / --byz-strategy / --byz-one / --coin-common need --mode byz or --mode byzb")
@@ -350,7 +394,7 @@ def cmd_sweep(a) -> int:
         rows, elapsed = run_sweep(cells, per_cell, a.seed, a.k_max, a.streams, rank, world, a.progress,
                                   mode=a.mode, crashed=byz_crashed, byz=dict(sched, strategy_name=a.byz_strategy),
                                   delivery="adversarial" if adversarial else "random",
-                                  level="class" if level_class else "node")
+                                  level="class" if level_class else "node", rule=rule)
     elif a.mode == "tally3":
         crashed = 0 if a.crashed is None else a.crashed
         bad = [f"{N}:{F}" for (N, F) in cells if crashed > F]
@@ -382,7 +426,7 @@ def rows_csv(rows: list[dict]) -> str:
 
 
 def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progress=False, mode="lockstep",
-              crashed=None, byz=None, delivery="random", level="node"):
+              crashed=None, byz=None, delivery="random", level="node", rule=None):
     """The sweep's GPU work on the current device: (rows, seconds).  Under
     torch.distributed (world > 1) each cell's trials are split over the ranks
     and the histograms merged by one all-reduce.  mode "lockstep": F crashed
@@ -393,7 +437,9 @@ def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progre
     rows, and with coin_common the shared-coin modes' word; `delivery` "adversarial"
     runs them under the adversarial scheduler (byz_strategy balance or split), and
     the rows then add a delivery column; `level` "class" runs those on the lumped chain
-    (benor.LumpedPlan: N up to 2**24; blocking launches, cell after cell) and adds a level column."""
+    (benor.LumpedPlan: N up to 2**24; blocking launches, cell after cell) and adds a level column.  `rule` (mode
+    "byzb"): "a", "b" or three words, a threshold rule in the place of Protocol B's on every cell's plan (the presets
+    at the cell's own (N, F)); the rows then add a rule column."""
     import torch
 
     import benor
@@ -414,6 +460,8 @@ def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progre
         raise ValueError("delivery is 'random', or 'adversarial' with mode 'byz' or 'byzb'")
     if level not in ("node", "class") or (level == "class" and delivery != "adversarial"):
         raise ValueError("level is 'node', or 'class' with delivery 'adversarial'")
+    if rule is not None and mode != "byzb":
+        raise ValueError("rule needs mode 'byzb' (it replaces Protocol B's rule)")
     if mode == "lockstep":
         if crashed is not None:
             raise ValueError("crashed needs mode 'tally3' (lockstep crashes exactly F nodes per cell)")
@@ -440,14 +488,18 @@ def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progre
                    ("byz", True): benor.BO_MODE_BYZ_COIN, ("byzb", True): benor.BO_MODE_BYZ_RULE_B_COIN}[mode, coin]
         if delivery == "adversarial":
             bo_mode = benor.BO_MODE_SCHED_TALLY if mode == "byz" else benor.BO_MODE_SCHED_RULE_B
+        def thresholds(N, F):                    # (no keyword at all without a rule: the plans are what they were)
+            return {} if rule is None else {"thresholds": rule_of(rule, benor, N, F)}
+
         if level == "class":                     # the same placement: compact indices 0 .. b - 1 Byzantine
             plans = [benor.LumpedPlan(N, F, f=crashed, b=b, byz_even=(b + 1) // 2, rule=1 if mode == "byzb" else 0,
                                       byz_strategy=byz["byz_strategy"], coin_common=byz.get("coin_common", 0),
-                                      seed=seed ^ (N << 20) ^ F ^ (b << 44), k_max=k_max) for (N, F, b) in cells]
+                                      seed=seed ^ (N << 20) ^ F ^ (b << 44), k_max=k_max, **thresholds(N, F))
+                     for (N, F, b) in cells]
         else:
             plans = [benor.TrialsPlan(N, F, [i < crashed for i in range(N)], seed=seed ^ (N << 20) ^ F ^ (b << 44),
                                       k_max=k_max, mode=bo_mode,
-                                      byzantine=[crashed <= i < crashed + b for i in range(N)], **byz)
+                                      byzantine=[crashed <= i < crashed + b for i in range(N)], **byz, **thresholds(N, F))
                      for (N, F, b) in cells]
     else:
         raise ValueError(f"mode must be 'lockstep', 'tally3', 'byz' or 'byzb': {mode!r}")
@@ -477,6 +529,8 @@ def run_sweep(cells, per_cell, seed, k_max, streams_n=4, rank=0, world=1, progre
                 row.update(delivery=delivery)
             if level == "class":
                 row.update(level=level)
+            if rule is not None:
+                row.update(rule=rule_text(rule))
     elapsed = time.perf_counter() - t0
     for plan in plans if level == "node" else ():
         plan.check()                               # device-side capacity invariants of every cell
@@ -540,6 +594,11 @@ def main(argv=None) -> int:
     t.add_argument("--coin-common", type=float, default=None,
                    help="byz, byzb: a shared coin (BO_MODE_BYZ_COIN, BO_MODE_BYZ_RULE_B_COIN): the probability in [0, 1] "
                         "that a round's coin is common to all honest nodes (0: the mode without it)")
+    rule_help = ("byzb: a threshold rule in the place of Protocol B's (DESIGN §4.3.13): a (Ben-Or's crash-tolerant "
+                 "Protocol A, the words (N, 0, 2F)), b (Protocol B's own words, (N + F, F, N + F)) or three words "
+                 "P:A:D -- propose v iff 2 c_v > P, adopt v iff c_v > A, decide iff also 2 c_v > D; at either "
+                 "--delivery and --level")
+    t.add_argument("--rule", default=None, help=rule_help)
     w = sub.add_parser("sweep", help="C5 decision-round phase diagram")
     w.add_argument("--N", default="64,128,256,512,1024,2048,4096")
     w.add_argument("--steps", type=int, default=32)
@@ -563,6 +622,7 @@ def main(argv=None) -> int:
     w.add_argument("--level", choices=["node", "class"], default="node",
                    help="byz, byzb with --delivery adversarial: node (one bit per node, N <= 4096) or class (the lumped "
                         "chain over the two receiver parities, N <= 2**24; the same law, another random stream)")
+    w.add_argument("--rule", default=None, help=rule_help + " (a and b: at every cell's own (N, F))")
     w.add_argument("--out", default=None)
     w.add_argument("--progress", action="store_true")
     a = ap.parse_args(argv)

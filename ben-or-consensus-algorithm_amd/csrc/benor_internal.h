@@ -194,6 +194,10 @@ struct KParams {
   // variants 16, 17, 20 and 21: the probability, in units of 2^-32, that a round's coin is common to the honest
   // nodes (bo_trials_cfg::coin_common, never 0 here; UINT32_MAX: every round)
   uint32_t coin_common;
+  // a Protocol B plan (variants 15, 17, 19 and 21) whose rule is replaced by a threshold rule (bo_plan_create_rule,
+  // benor_rule.h): rule_on picks the RuleT entries, which read the three words; 0: the plan's own rule
+  uint32_t rule_on;
+  bo_rule rule;
 };
 
 constexpr uint32_t kTimelineWords = 12;
@@ -268,7 +272,7 @@ hipError_t launch_tally_sched(const KParams &p, int grid_blocks, hipStream_t str
 constexpr int kLumpedBlock = 256;                  // lanes (trials in flight) per workgroup
 struct LumpedParams {
   lumped::Shape s;
-  uint32_t rule;                                   // 0: RuleRef, 1: RuleB
+  uint32_t rule;                                   // 0: RuleRef, 1: RuleB, 2: RuleT (the words of `thresholds`)
   uint32_t coin_common;                            // 0: every coin local (the entries without stream 12)
   uint32_t k_max, hist_len;
   uint32_t init_mode, init0, init1;                // BO_INIT_FIXED: the honest nodes at 0 and at 1 (the rest "?")
@@ -276,6 +280,7 @@ struct LumpedParams {
   unsigned long long *hist;                        // [hist_len] (device, accumulated)
   bo_lumped_state *state_out;                      // (device) or nullptr; only with trial_count == 1
   lumped::TableDir tables;                         // device pointers
+  bo_rule thresholds;                              // rule 2 (bo_lumped_*_rule): the threshold rule's words (last: the fields above keep their offsets)
 };
 int lumped_blocks_per_cu(const LumpedParams &p);   // resident workgroups per CU (0 = unknown)
 hipError_t launch_lumped(const LumpedParams &p, int grid_blocks, hipStream_t stream);

@@ -4,7 +4,8 @@
 // applies the same rule to the same counts, so a trial is a Markov chain on
 // (a_0, a_1, dec_0, dec_1): a_pi the honest nodes of parity pi with x = 1, dec_pi the
 // parity's sticky decided flag.  This header is that chain on scalars -- the scheduler's
-// two closed forms, both rules' R- and P-steps, one round, the outcome bins -- with the
+// two closed forms, both rules' R- and P-steps (and the threshold rule of benor_rule.h as
+// a third rule type, bo_lumped_*_rule), one round, the outcome bins -- with the
 // Binomial(n, 1/2) draw over a source of 64-bit words and the validation of a
 // configuration.  Plain C++17 over benor.h, no HIP: benor_lumped.hip runs it one trial
 // per lane, the runtime validates with it, and tests/lumped_check.cpp checks it on the
@@ -14,6 +15,7 @@
 #include <stdint.h>
 
 #include "benor.h"
+#include "benor_rule.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define BENOR_LUMPED_HD __host__ __device__ inline
@@ -92,6 +94,15 @@ struct RuleB {                                     // Ben-Or's Protocol B, t = F
   }
 };
 
+struct RuleT {                                     // a threshold rule of three runtime words (benor_rule.h)
+  static constexpr uint32_t kRule = 2u;
+  bo_rule t;
+  BENOR_LUMPED_HD uint32_t r(uint32_t c0, uint32_t c1, uint32_t, uint32_t) const { return rule::r_step(t, c0, c1); }
+  BENOR_LUMPED_HD uint32_t p(uint32_t c0, uint32_t c1, uint32_t, uint32_t, bool &decided) const {
+    return rule::p_step(t, c0, c1, decided);
+  }
+};
+
 // ---- a configuration's derived sizes
 struct Shape {
   uint32_t N, F, q, nb;       // q = N - F, nb = b
@@ -122,14 +133,15 @@ struct State {
 // What a coin state says: 0 not drawn, 1 every node its own coin, 2 | v the round is common with bit v.
 // `src.common(r)` answers 1 or 2 | v for round r; `src.binom(n, pi, r)` draws Binomial(n, 1/2) from parity
 // pi's words of round r.  Neither is called unless a parity with a node takes the coin.
-// Returns whether every parity that has a node has decided.
+// Returns whether every parity that has a node has decided.  `rule`: the rule's object -- empty for the two
+// compile-time rules, whose r and p are static, the words for RuleT.
 template <class Rule, class Src>
-BENOR_LUMPED_HD bool round(const Shape &s, uint32_t r, State &st, Src &src) {
+BENOR_LUMPED_HD bool round(const Rule &rule, const Shape &s, uint32_t r, State &st, Src &src) {
   const uint32_t Hq = s.hh - st.H0 - st.H1;
   uint32_t P0 = 0u, P1 = 0u;                       // R-phase: a parity's h_pi members all propose alike
   for (uint32_t pi = 0u; pi < 2u; ++pi) {
     const Counts c = counts(s.strategy, pi, s.q, st.H0, st.H1, Hq, s.nb);
-    const uint32_t prop = Rule::r(c.c0, c.c1, s.N, s.F);
+    const uint32_t prop = rule.r(c.c0, c.c1, s.N, s.F);
     P0 += prop == 0u ? s.h[pi] : 0u;
     P1 += prop == 1u ? s.h[pi] : 0u;
   }
@@ -139,7 +151,7 @@ BENOR_LUMPED_HD bool round(const Shape &s, uint32_t r, State &st, Src &src) {
   for (uint32_t pi = 0u; pi < 2u; ++pi) {
     const Counts c = counts(s.strategy, pi, s.q, P0, P1, Pq, s.nb);
     bool decided;
-    act[pi] = Rule::p(c.c0, c.c1, s.N, s.F, decided);
+    act[pi] = rule.p(c.c0, c.c1, s.N, s.F, decided);
     if (s.h[pi] != 0u && decided) st.dec |= 1u << pi;   // sticky
     take = take || (s.h[pi] != 0u && act[pi] == kNone);
   }
@@ -153,6 +165,10 @@ BENOR_LUMPED_HD bool round(const Shape &s, uint32_t r, State &st, Src &src) {
   st.H1 = st.a[0] + st.a[1];
   st.H0 = s.hh - st.H1;
   return ((st.dec & 1u) != 0u || s.h[0] == 0u) && ((st.dec & 2u) != 0u || s.h[1] == 0u);
+}
+template <class Rule, class Src>
+BENOR_LUMPED_HD bool round(const Shape &s, uint32_t r, State &st, Src &src) {
+  return round(Rule{}, s, r, st, src);
 }
 
 // ---- the outcome (trial_end's bins, benor_tally_common.h)
@@ -208,8 +224,9 @@ struct TableDir {
 };
 
 // ---- validation (host and device need none of each other)
-// BO_OK, or the error code with *msg set to a text that names what is wrong.
-inline int check(const bo_lumped_cfg &c, const char **msg) {
+// BO_OK, or the error code with *msg set to a text that names what is wrong.  `own_rule`: the configuration runs
+// the rule it names (c.rule); the bo_lumped_*_rule entries carry a threshold rule instead and do not read the word.
+inline int check(const bo_lumped_cfg &c, const char **msg, bool own_rule = true) {
   const char *dummy;
   if (!msg) msg = &dummy;
   *msg = "";
@@ -226,7 +243,7 @@ inline int check(const bo_lumped_cfg &c, const char **msg) {
            BO_ERR_INVALID_ARGUMENT;
   if (c.strategy != BO_BYZ_BALANCE && c.strategy != BO_BYZ_SPLIT)
     return *msg = "bo_lumped: strategy must be BO_BYZ_BALANCE or BO_BYZ_SPLIT", BO_ERR_INVALID_ARGUMENT;
-  if (c.rule > 1u) return *msg = "bo_lumped: rule must be 0 (the reference's) or 1 (Protocol B)", BO_ERR_INVALID_ARGUMENT;
+  if (own_rule && c.rule > 1u) return *msg = "bo_lumped: rule must be 0 (the reference's) or 1 (Protocol B)", BO_ERR_INVALID_ARGUMENT;
   if (c.k_max < 1u || c.k_max > BO_MAX_K) return *msg = "bo_lumped: k_max must be 1 .. 1024", BO_ERR_INVALID_ARGUMENT;
   if (c.init_mode != BO_INIT_RANDOM && c.init_mode != BO_INIT_FIXED)
     return *msg = "bo_lumped: init_mode must be BO_INIT_RANDOM or BO_INIT_FIXED", BO_ERR_INVALID_ARGUMENT;

@@ -1,8 +1,9 @@
 // benor_lumped.hip -- the adversarial scheduler at the level of classes (bo_lumped_*,
 // include/benor.h).
 //
-// One trial loop, a template over the rule (lumped::RuleRef, lumped::RuleB) and over the
-// coin a P-phase takes (CoinLocal, CoinShared): four entries.  The chain itself -- the
+// One trial loop, a template over the rule (lumped::RuleRef, lumped::RuleB, and
+// lumped::RuleT, the threshold rule of three runtime words behind bo_lumped_*_rule,
+// DESIGN §4.3.13) and over the coin a P-phase takes (CoinLocal, CoinShared): six entries.  The chain itself -- the
 // scheduler's closed forms, the rules on scalars, a round, the outcome bins, the
 // Binomial(n, 1/2) draw -- is benor_lumped.h, shared with the host; this file supplies
 // the words: Philox stream 12 for a round's common coin, stream 13 for the Binomial draws.
@@ -79,6 +80,8 @@ __global__ void __launch_bounds__(kLumpedBlock) benor_lumped_kernel(LumpedParams
   __syncthreads();
 
   const Shape s = p.s;
+  Rule rule{};                                     // (empty for the compile-time rules)
+  if constexpr (Rule::kRule == lumped::RuleT::kRule) rule.t = p.thresholds;
   Source<Coin> src{p.tables, (uint32_t)p.seed, (uint32_t)(p.seed >> 32), p.coin_common, 0u, 0u};
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -102,7 +105,7 @@ __global__ void __launch_bounds__(kLumpedBlock) benor_lumped_kernel(LumpedParams
   if (live) start();
   while (live) {
     ++r;
-    const bool all_dec = lumped::round<Rule>(s, r, st, src);
+    const bool all_dec = lumped::round(rule, s, r, st, src);
     if (all_dec || r == p.k_max) {
       bool violation;
       const uint32_t bin = lumped::outcome_bin(st.a[0] + st.a[1], s.hh, all_dec, r, violation);
@@ -132,6 +135,8 @@ __global__ void __launch_bounds__(kLumpedBlock) benor_lumped_kernel(LumpedParams
 using LumpedKernel = void (*)(LumpedParams);
 LumpedKernel lumped_entry(const LumpedParams &p) {
   const bool shared = p.coin_common != 0u;
+  if (p.rule == lumped::RuleT::kRule)
+    return shared ? benor_lumped_kernel<lumped::RuleT, CoinShared> : benor_lumped_kernel<lumped::RuleT, CoinLocal>;
   if (p.rule == lumped::RuleB::kRule)
     return shared ? benor_lumped_kernel<lumped::RuleB, CoinShared> : benor_lumped_kernel<lumped::RuleB, CoinLocal>;
   return shared ? benor_lumped_kernel<lumped::RuleRef, CoinShared> : benor_lumped_kernel<lumped::RuleRef, CoinLocal>;
@@ -147,7 +152,8 @@ int lumped_blocks_per_cu(const LumpedParams &p) {
 }
 
 hipError_t launch_lumped(const LumpedParams &p, int grid, hipStream_t s) {
-  if (p.rule > 1u || p.s.hh == 0u || p.s.q == 0u || p.s.hh < p.s.q || p.s.N > lumped::kMaxN || p.k_max == 0u ||
+  if (p.rule > lumped::RuleT::kRule || (p.rule == lumped::RuleT::kRule && rule::check(p.thresholds, nullptr) != BO_OK) ||
+      p.s.hh == 0u || p.s.q == 0u || p.s.hh < p.s.q || p.s.N > lumped::kMaxN || p.k_max == 0u ||
       p.hist_len != (p.k_max + 1u) * 3u + 1u || !p.hist || !p.tables.thr || !p.tables.off || !p.tables.lo ||
       (p.state_out && p.trial_count != 1u) || grid < 1)
     return hipErrorInvalidValue;

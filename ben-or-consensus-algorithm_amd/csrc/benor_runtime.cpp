@@ -659,16 +659,27 @@ int lumped_device_tables(int dev, benor::lumped::TableDir &out) {
   return BO_OK;
 }
 
-int lumped_check(const bo_lumped_cfg *cfg) {
-  if (!cfg) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
+// A threshold rule's words (benor_rule.h).
+int rule_check(const bo_rule *rule) {
+  if (!rule) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
   const char *msg = "";
-  const int rc = benor::lumped::check(*cfg, &msg);
+  const int rc = benor::rule::check(*rule, &msg);
   return rc ? fail(rc, msg) : BO_OK;
 }
 
+// `rule`: NULL for the configuration's own rule (cfg->rule), else the threshold rule that replaces it.
+int lumped_check(const bo_lumped_cfg *cfg, const bo_rule *rule = nullptr) {
+  if (!cfg) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
+  const char *msg = "";
+  const int rc = benor::lumped::check(*cfg, &msg, rule == nullptr);
+  if (rc) return fail(rc, msg);
+  return rule ? rule_check(rule) : BO_OK;
+}
+
 // Trials [begin, begin + count) added into hist (host); `state`: the one trial's final state.
-int lumped_launch(const bo_lumped_cfg *cfg, uint64_t begin, uint64_t count, uint64_t *hist, bo_lumped_state *state) {
-  int rc = lumped_check(cfg);
+int lumped_launch(const bo_lumped_cfg *cfg, const bo_rule *rule, uint64_t begin, uint64_t count, uint64_t *hist,
+                  bo_lumped_state *state) {
+  int rc = lumped_check(cfg, rule);
   if (rc) return rc;
   if (!hist && !state) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
   if (count == 0u) return BO_OK;
@@ -678,7 +689,9 @@ int lumped_launch(const bo_lumped_cfg *cfg, uint64_t begin, uint64_t count, uint
   benor::LumpedParams p;
   std::memset(&p, 0, sizeof p);
   p.s = benor::lumped::shape_of(*cfg);
-  p.rule = cfg->rule, p.coin_common = cfg->coin_common, p.k_max = cfg->k_max, p.hist_len = bo_hist_len(cfg->k_max);
+  p.rule = rule ? benor::lumped::RuleT::kRule : cfg->rule;
+  if (rule) p.thresholds = *rule;
+  p.coin_common = cfg->coin_common, p.k_max = cfg->k_max, p.hist_len = bo_hist_len(cfg->k_max);
   p.init_mode = cfg->init_mode, p.init0 = cfg->init0, p.init1 = cfg->init1;
   p.seed = cfg->seed;
   rc = lumped_device_tables(dev, p.tables);
@@ -719,13 +732,41 @@ int bo_lumped_check(const bo_lumped_cfg *cfg) { return lumped_check(cfg); }
 
 int bo_lumped_run(const bo_lumped_cfg *cfg, uint64_t trial_begin, uint64_t trial_count, uint64_t *hist_host) {
   if (!hist_host) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
-  return lumped_launch(cfg, trial_begin, trial_count, hist_host, nullptr);
+  return lumped_launch(cfg, nullptr, trial_begin, trial_count, hist_host, nullptr);
 }
 
 int bo_lumped_trial(const bo_lumped_cfg *cfg, uint64_t trial, bo_lumped_state *out) {
   if (!out) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
-  return lumped_launch(cfg, trial, 1, nullptr, out);
+  return lumped_launch(cfg, nullptr, trial, 1, nullptr, out);
 }
+
+// ... with a threshold rule in the place of cfg->rule, which is not read
+int bo_lumped_check_rule(const bo_lumped_cfg *cfg, const bo_rule *rule) {
+  if (!rule) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
+  return lumped_check(cfg, rule);
+}
+
+int bo_lumped_run_rule(const bo_lumped_cfg *cfg, const bo_rule *rule, uint64_t trial_begin, uint64_t trial_count,
+                       uint64_t *hist_host) {
+  if (!rule || !hist_host) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
+  return lumped_launch(cfg, rule, trial_begin, trial_count, hist_host, nullptr);
+}
+
+int bo_lumped_trial_rule(const bo_lumped_cfg *cfg, const bo_rule *rule, uint64_t trial, bo_lumped_state *out) {
+  if (!rule || !out) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
+  return lumped_launch(cfg, rule, trial, 1, nullptr, out);
+}
+
+// The presets (benor_rule.h).
+static int rule_preset(bool b, uint32_t N, uint32_t F, bo_rule *out) {
+  if (!out) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (!benor::rule::preset_fits(N, F))
+    return fail(BO_ERR_INVALID_ARGUMENT, "bo_rule: N + F and 2 F must be at most 2^31 - 1");
+  *out = b ? benor::rule::protocol_b(N, F) : benor::rule::protocol_a(N, F);
+  return BO_OK;
+}
+int bo_rule_protocol_a(uint32_t N, uint32_t F, bo_rule *out) { return rule_preset(false, N, F, out); }
+int bo_rule_protocol_b(uint32_t N, uint32_t F, bo_rule *out) { return rule_preset(true, N, F, out); }
 
 // -------------------------------------------------------------- batch API
 // Validation and kernel planning of a trial configuration, host only: the
@@ -1002,7 +1043,19 @@ struct TableUpload {
   }
 };
 
-static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_run) {
+// A threshold rule replaces Protocol B's rule on the plans of the three modes that run it; the
+// plan is otherwise the mode's own, word for word.  Host only: the argument errors need no device.
+static int check_rule_base(const bo_trials_cfg *cfg, const bo_rule *rule) {
+  if (!cfg || !rule) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (cfg->mode != BO_MODE_BYZ_RULE_B && cfg->mode != BO_MODE_BYZ_RULE_B_COIN && cfg->mode != BO_MODE_SCHED_RULE_B)
+    return fail(BO_ERR_INVALID_ARGUMENT,
+                "a threshold rule needs mode BO_MODE_BYZ_RULE_B, BO_MODE_BYZ_RULE_B_COIN or BO_MODE_SCHED_RULE_B "
+                "(the plan whose rule it replaces)");
+  return rule_check(rule);
+}
+
+// `rule`: NULL, or the threshold rule that replaces the plan's own (checked by check_rule_base).
+static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_run, const bo_rule *rule = nullptr) {
   if (!cfg || !out) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
   *out = nullptr;
   std::vector<uint32_t> live;
@@ -1011,6 +1064,7 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
   PlanTables tables;
   int rc = plan_host(cfg, live, plane, kp0, live_run, &tables);
   if (rc) return rc;
+  if (rule) kp0.rule_on = 1u, kp0.rule = *rule;     // (the variant, the geometry and the tables are the base plan's)
   int dev = 0;
   rc = check_device(&dev);
   if (rc) return rc;
@@ -1172,6 +1226,20 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
 }
 
 int bo_plan_create(const bo_trials_cfg *cfg, bo_plan **out) { return plan_create_impl(cfg, out, false); }
+
+int bo_plan_create_rule(const bo_trials_cfg *cfg, const bo_rule *rule, bo_plan **out) {
+  if (!out) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
+  *out = nullptr;
+  const int rc = check_rule_base(cfg, rule);
+  return rc ? rc : plan_create_impl(cfg, out, false, rule);
+}
+
+int bo_plan_rule(const bo_plan *pl, bo_rule *out) {
+  if (!pl) return -BO_ERR_INVALID_ARGUMENT;
+  if (!pl->kp.rule_on) return 0;
+  if (out) *out = pl->kp.rule;
+  return 1;
+}
 
 void bo_plan_destroy(bo_plan *pl) {
   if (!pl) return;
@@ -1535,11 +1603,11 @@ int run_states_lockstep(const bo_trials_cfg *cfg, uint64_t trial, bo_node_state 
 }
 }  // namespace
 
-int bo_run_trial_states(const bo_trials_cfg *cfg, uint64_t trial, bo_node_state *nodes_out, uint32_t *rounds_out) {
-  if (!cfg || !nodes_out) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (cfg->mode == BO_MODE_LOCKSTEP) return run_states_lockstep(cfg, trial, nodes_out, rounds_out);
+// One trial's per-node states through a plan of its own; `rule`: NULL, or the threshold rule that replaces the plan's.
+static int run_states_plan(const bo_trials_cfg *cfg, const bo_rule *rule, uint64_t trial, bo_node_state *nodes_out,
+                           uint32_t *rounds_out) {
   bo_plan *pl = nullptr;
-  int rc = bo_plan_create(cfg, &pl);
+  int rc = plan_create_impl(cfg, &pl, false, rule);
   if (rc) return rc;
   const uint32_t N = cfg->N, H = bo_hist_len(cfg->k_max);
   std::vector<bo_node_state> st(N);
@@ -1566,6 +1634,21 @@ int bo_run_trial_states(const bo_trials_cfg *cfg, uint64_t trial, bo_node_state 
   if (rounds & 0x80000000u) return fail(BO_ERR_INTERNAL, "event-level message pool filled up: the run stopped early");
   if (rounds_out) *rounds_out = rounds;
   return BO_OK;
+}
+
+int bo_run_trial_states(const bo_trials_cfg *cfg, uint64_t trial, bo_node_state *nodes_out, uint32_t *rounds_out) {
+  if (!cfg || !nodes_out) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (cfg->mode == BO_MODE_LOCKSTEP) return run_states_lockstep(cfg, trial, nodes_out, rounds_out);
+  return run_states_plan(cfg, nullptr, trial, nodes_out, rounds_out);
+}
+
+int bo_run_trial_states_rule(const bo_trials_cfg *cfg, const bo_rule *rule, uint64_t trial, bo_node_state *nodes_out,
+                             uint32_t n) {
+  if (!nodes_out) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
+  const int rc = check_rule_base(cfg, rule);
+  if (rc) return rc;
+  if (n < cfg->N) return fail(BO_ERR_INVALID_ARGUMENT, "bo_run_trial_states_rule: nodes_out holds fewer than N entries");
+  return run_states_plan(cfg, rule, trial, nodes_out, nullptr);
 }
 
 // ------------------------------------------------------------ live runs

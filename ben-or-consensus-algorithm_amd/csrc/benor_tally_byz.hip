@@ -6,8 +6,10 @@
 // (RuleRef, RuleB) and over the coin a P-phase takes (CoinLocal, CoinShared; all four
 // in benor_tally_common.h): variant 14 runs <RuleRef, CoinLocal>, variant 15 <RuleB,
 // CoinLocal>, and variants 16 and 17 the same two rules with <CoinShared>, the shared
-// coin of BO_MODE_BYZ_COIN and BO_MODE_BYZ_RULE_B_COIN.  Everything
-// else in this comment holds for all of them.
+// coin of BO_MODE_BYZ_COIN and BO_MODE_BYZ_RULE_B_COIN.  A plan of
+// variant 15 or 17 whose rule is replaced by a threshold rule (bo_plan_create_rule,
+// KParams::rule_on) runs the same two loops with <RuleT, CoinLocal> or
+// <RuleT, CoinShared>.  Everything else in this comment holds for all of them.
 //
 // The model is benor_tally3.hip's with b of the m live nodes Byzantine: they send
 // at every step and lie, they never receive.  The h = m - b honest nodes run the
@@ -95,6 +97,7 @@ __global__ void __launch_bounds__(256, 6) benor_tally_byz_kernel(KParams p) {
   const uint32_t k0 = (uint32_t)p.seed, k1 = (uint32_t)(p.seed >> 32);
   const uint64_t waves_total = (uint64_t)gridDim.x * kWavesPerBlock;
   Coin coin = make_coin<Coin>(p);
+  const Rule rl = make_rule<Rule>(p);             // (empty for the compile-time rules)
 
   // What the Byzantine senders say at a step with honest class sizes (H0, H1): true if every
   // receiver has a B1 of its own, else B1u for all of them.
@@ -158,7 +161,7 @@ __global__ void __launch_bounds__(256, 6) benor_tally_byz_kernel(KParams p) {
             draw3_lane(one_table, p.tally_cap, 0u, m, q, H0 + nb - B1, H1 + B1, k0, k1, tlo, thi, c, r, 0u, u,
                        (hp >> lane) & 1ull, c0, c1);
           }
-          Rule::r(c0, c1, N, F, hp, p0, p1);
+          rl.r(c0, c1, N, F, hp, p0, p1);
         }
         if (lane == 0) P0[j] = p0, P1[j] = p1;
       }
@@ -190,7 +193,7 @@ __global__ void __launch_bounds__(256, 6) benor_tally_byz_kernel(KParams p) {
                      c1);
         }
         bool decided;
-        const uint64_t x1 = Rule::p(c0, c1, N, F, hp, k0, k1, tlo, thi, j, r, decided, coin);
+        const uint64_t x1 = rl.p(c0, c1, N, F, hp, k0, k1, tlo, thi, j, r, decided, coin);
         if (mine && decided) dec |= 1ull << j;     // sticky
         undecided = undecided || (mine && !((dec >> j) & 1ull));
         if (lane == 0) X1[j] = (X1[j] & ~hp) | x1;                       // a Byzantine node's bit is never written
@@ -277,6 +280,7 @@ __global__ void __launch_bounds__(256, 6) benor_tally_heard_kernel(KParams p) {
   const uint32_t k0 = (uint32_t)p.seed, k1 = (uint32_t)(p.seed >> 32);
   const uint64_t waves_total = (uint64_t)gridDim.x * kWavesPerBlock;
   Coin coin = make_coin<Coin>(p);
+  const Rule rl = make_rule<Rule>(p);             // (empty for the compile-time rules)
 
   for (uint64_t t = (uint64_t)blockIdx.x * kWavesPerBlock + wv; t < p.trial_count; t += waves_total) {
     const uint64_t trial = p.trial_begin + t;
@@ -314,7 +318,7 @@ __global__ void __launch_bounds__(256, 6) benor_tally_heard_kernel(KParams p) {
           const uint32_t nB = Hq != 0u ? heard_byz(Hq, nb, rest, k0, k1, tlo, thi, c, r, 0u) : rest;
           const uint32_t l1 = heard_lies(strategy, c, h0, h1, nB);
           const uint32_t c0 = h0 + nB - l1, c1 = h1 + l1;
-          Rule::r(c0, c1, N, F, hp, p0, p1);
+          rl.r(c0, c1, N, F, hp, p0, p1);
         }
         if (lane == 0) P0[j] = p0, P1[j] = p1;
       }
@@ -342,7 +346,7 @@ __global__ void __launch_bounds__(256, 6) benor_tally_heard_kernel(KParams p) {
         const uint32_t l1 = heard_lies(strategy, c, h0, h1, nB);
         const uint32_t c0 = h0 + nB - l1, c1 = h1 + l1;
         bool decided;
-        const uint64_t x1 = Rule::p(c0, c1, N, F, hp, k0, k1, tlo, thi, j, r, decided, coin);
+        const uint64_t x1 = rl.p(c0, c1, N, F, hp, k0, k1, tlo, thi, j, r, decided, coin);
         if (mine && decided) dec |= 1ull << j;     // sticky
         undecided = undecided || (mine && !((dec >> j) & 1ull));
         if (lane == 0) X1[j] = (X1[j] & ~hp) | x1;                       // a Byzantine node's bit is never written
@@ -379,10 +383,16 @@ bool byz_thr_in_lds(uint32_t lds_bytes, uint32_t b) {
   return lds_groups_per_cu(lds_bytes + 8u * b) >= without;
 }
 
-// The entry of a plan: its rule and coin by the variant, its loop by the strategy.
+// The entry of a plan: its rule and coin by the variant, its loop by the strategy; a plan whose rule is replaced
+// (rule_on, a Protocol B plan: the launch checks) takes the threshold rule's entry of its coin and loop.
 using ByzKernel = void (*)(KParams);
 static ByzKernel byz_entry(const KParams &p) {
   const bool heard = byz_heard(p);
+  if (p.rule_on) {
+    if (variant_shared_coin(p.variant))
+      return heard ? benor_tally_heard_kernel<RuleT, CoinShared> : benor_tally_byz_kernel<RuleT, CoinShared>;
+    return heard ? benor_tally_heard_kernel<RuleT, CoinLocal> : benor_tally_byz_kernel<RuleT, CoinLocal>;
+  }
   switch (p.variant) {
     case byz_variant(BO_MODE_BYZ_TALLY): return heard ? benor_tally_heard_kernel<RuleRef, CoinLocal> : benor_tally_byz_kernel<RuleRef, CoinLocal>;
     case byz_variant(BO_MODE_BYZ_RULE_B): return heard ? benor_tally_heard_kernel<RuleB, CoinLocal> : benor_tally_byz_kernel<RuleB, CoinLocal>;
@@ -404,7 +414,7 @@ hipError_t launch_tally_byz(const KParams &plan, int grid, hipStream_t s) {
   const bool no_thr = heard || p.byz_n == 0u;
   if (!variant_byz(p.variant) || !p.tally_off || !p.tally_thr || !p.byz_plane || (no_thr ? p.byz_lds != 0u : !p.byz_thr) ||
       p.W > kMaxW || (p.byz_n == 0u && p.variant == byz_variant(BO_MODE_BYZ_TALLY)) || (shared && p.coin_common == 0u) ||
-      p.byz_n > p.m - p.q || plan.wave_bytes < byz_wave_bytes(p.W, p.tally_cap) ||
+      (p.rule_on && (!variant_rule_b(p.variant) || rule::check(p.rule, nullptr) != BO_OK)) || p.byz_n > p.m - p.q || plan.wave_bytes < byz_wave_bytes(p.W, p.tally_cap) ||
       plan.lds_bytes < p.hist_bytes + kWavesPerBlock * plan.wave_bytes + (p.byz_lds ? 8u * p.byz_n : 0u))
     return hipErrorInvalidValue;
   return launch_lds(byz_entry(p), p, grid, s);

@@ -4,8 +4,8 @@
 // here once: the per-wave LDS layouts, the threshold search, the three-class draw
 // in its wave-uniform and its per-lane form, the stream-6 walk whose word order is
 // the bit-exact contract with the oracle, a trial's start and end, the P-phase
-// rule (and both phases of Ben-Or's Byzantine-tolerant rule), the per-node-state
-// write-out, the random schedule, and the host's occupancy query and launch.
+// rule (and both phases of Ben-Or's Byzantine-tolerant rule, and the threshold rule
+// of three runtime words over benor_rule.h), the per-node-state write-out, the random schedule, and the host's occupancy query and launch.
 //
 // The first part, the layouts, is plain C++ that also compiles on the host without
 // HIP (tests/tally_layout_check.cpp sweeps it); the rest is device code.
@@ -95,7 +95,10 @@ BENOR_TALLY_HD uint32_t tally_wave_bytes(uint32_t W, uint32_t cap) { return (((W
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 
+#include <type_traits>
+
 #include "benor_device.h"
+#include "benor_rule.h"
 
 namespace benor {
 
@@ -476,6 +479,40 @@ struct RuleB {                                     // Ben-Or's Protocol B, t = F
     return p_rule_b(c0, c1, N, F, hp, k0, k1, tlo, thi, j, r, decided, coin);
   }
 };
+
+// A threshold rule of three runtime words (bo_rule, benor_rule.h): Protocol A, and Protocol B and
+// the reference's rule again at their words.  The words are KParams::rule's, wave-uniform; the rule itself is
+// benor_rule.h's scalar R- and P-step, wrapped in ballots.  An interface of its own -- an object with the words,
+// made by make_rule -- so that the two compile-time rules above keep theirs and their entries their code.
+struct RuleT {
+  static constexpr bool kNoLiar = true;            // a Protocol B plan with its rule replaced: b = 0 runs here too
+  bo_rule t;
+  __device__ __forceinline__ void r(uint32_t c0, uint32_t c1, uint32_t, uint32_t, uint64_t hp, uint64_t &p0,
+                                    uint64_t &p1) const {
+    const uint32_t prop = rule::r_step(t, c0, c1);
+    p0 = ballot(prop == 0u) & hp;
+    p1 = ballot(prop == 1u) & hp;
+  }
+  template <class Coin>
+  __device__ __forceinline__ uint64_t p(uint32_t c0, uint32_t c1, uint32_t, uint32_t, uint64_t mask, uint32_t k0,
+                                        uint32_t k1, uint32_t tlo, uint32_t thi, uint32_t j, uint32_t r, bool &decided,
+                                        Coin &coin) const {
+    const uint32_t act = rule::p_step(t, c0, c1, decided);
+    const uint64_t take = mask & ballot(act == rule::kNone);
+    uint64_t x1 = ballot(act == 1u) & mask;
+    if (take) x1 |= coin(k0, k1, tlo, thi, j, r, take);
+    return x1;
+  }
+};
+
+// The rule object of a trial loop: empty for the compile-time rules (their r and p are static), the plan's words for RuleT.
+template <class Rule>
+__device__ __forceinline__ Rule make_rule(const KParams &p) {
+  if constexpr (std::is_same_v<Rule, RuleT>)
+    return Rule{bo_rule{uni(p.rule.propose_gt2), uni(p.rule.adopt_gt), uni(p.rule.decide_gt2), 0u}};
+  else
+    return Rule{};
+}
 
 template <class Coin>
 __device__ __forceinline__ Coin make_coin(const KParams &p) {

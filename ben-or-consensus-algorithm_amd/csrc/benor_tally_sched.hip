@@ -2,9 +2,11 @@
 // (BO_MODE_SCHED_TALLY, BO_MODE_SCHED_RULE_B).
 //
 // One trial loop, a template over the rule applied to a receiver's counts (RuleRef,
-// RuleB) and over the coin a P-phase takes (CoinLocal, CoinShared; all four in
+// RuleB, RuleT) and over the coin a P-phase takes (CoinLocal, CoinShared; all five in
 // benor_tally_common.h): variant 18 runs <RuleRef, CoinLocal>, variant 19 <RuleB,
-// CoinLocal>, and variants 20 and 21 the same two rules with <CoinShared>.
+// CoinLocal>, and variants 20 and 21 the same two rules with <CoinShared>.  A plan of
+// variant 19 or 21 whose rule is replaced by a threshold rule (bo_plan_create_rule,
+// KParams::rule_on) runs <RuleT, CoinLocal> or <RuleT, CoinShared>.
 //
 // The model is benor_tally_byz.hip's -- b of the m live nodes Byzantine, the h = m - b
 // honest ones run the rule and alone receive -- except for who is heard: the adversary,
@@ -82,7 +84,7 @@ __device__ __forceinline__ void sched_counts(uint32_t strategy, uint32_t q, uint
   c1 = odd ? o1 : e1;
 }
 
-// Launch bounds: the four entries compile to 47 or 48 VGPRs with no VGPR spill under a bound of
+// Launch bounds: the six entries compile to 47 or 48 VGPRs with no VGPR spill under a bound of
 // eight waves per SIMD -- all a SIMD holds, a workgroup being one wave per SIMD -- so that bound is
 // asked for (SGPR spills, 34 to 80 words, go to VGPR lanes within those 48); LDS allows more than
 // eight workgroups at every W (at W = 64: 8 KiB of planes and the histogram per workgroup).
@@ -109,6 +111,7 @@ __global__ void __launch_bounds__(256, 8) benor_tally_sched_kernel(KParams p) {
   const uint32_t k0 = (uint32_t)p.seed, k1 = (uint32_t)(p.seed >> 32);
   const uint64_t waves_total = (uint64_t)gridDim.x * kWavesPerBlock;
   Coin coin = make_coin<Coin>(p);
+  const Rule rl = make_rule<Rule>(p);             // (empty for the compile-time rules)
 
   for (uint64_t t = (uint64_t)blockIdx.x * kWavesPerBlock + wv; t < p.trial_count; t += waves_total) {
     const uint64_t trial = p.trial_begin + t;
@@ -135,7 +138,7 @@ __global__ void __launch_bounds__(256, 8) benor_tally_sched_kernel(KParams p) {
       sched_counts(strategy, q, H0, H1, h - H0 - H1, nb, lane, c0, c1);   // ("?" starts: round 1 only)
       {
         uint64_t a0, a1;                           // the proposals of a group whose 64 lanes are all honest
-        Rule::r(c0, c1, N, F, ~0ull, a0, a1);
+        rl.r(c0, c1, N, F, ~0ull, a0, a1);
         __builtin_amdgcn_wave_barrier();           // the class sizes are read before P0 takes X0's words
         for (uint32_t w = lane; w < W; w += 64u) {
           const uint64_t hp = HP[w];
@@ -157,7 +160,7 @@ __global__ void __launch_bounds__(256, 8) benor_tally_sched_kernel(KParams p) {
         if (!hp) continue;                         // a group without an honest lane takes no coin
         const bool mine = (hp >> lane) & 1ull;     // this lane's node is honest
         bool decided;
-        const uint64_t x1 = Rule::p(c0, c1, N, F, hp, k0, k1, tlo, thi, j, r, decided, coin);
+        const uint64_t x1 = rl.p(c0, c1, N, F, hp, k0, k1, tlo, thi, j, r, decided, coin);
         if (mine && decided) dec |= 1ull << j;     // sticky
         undecided = undecided || (mine && !((dec >> j) & 1ull));
         if (lane == 0) X1[j] = (X1[j] & ~hp) | x1;                       // a Byzantine node's bit is never written
@@ -180,9 +183,12 @@ __global__ void __launch_bounds__(256, 8) benor_tally_sched_kernel(KParams p) {
 
 }  // namespace
 
-// The entry of a plan: its rule and coin by the variant.
+// The entry of a plan: its rule and coin by the variant; a plan whose rule is replaced (rule_on, a Protocol B
+// plan: the launch checks) takes the threshold rule's entry of its coin.
 using SchedKernel = void (*)(KParams);
 static SchedKernel sched_entry(const KParams &p) {
+  if (p.rule_on)
+    return variant_shared_coin(p.variant) ? benor_tally_sched_kernel<RuleT, CoinShared> : benor_tally_sched_kernel<RuleT, CoinLocal>;
   switch (p.variant) {
     case sched_variant(BO_MODE_SCHED_TALLY, false): return benor_tally_sched_kernel<RuleRef, CoinLocal>;
     case sched_variant(BO_MODE_SCHED_RULE_B, false): return benor_tally_sched_kernel<RuleB, CoinLocal>;
@@ -202,7 +208,7 @@ hipError_t launch_tally_sched(const KParams &plan, int grid, hipStream_t s) {
   const bool shared = variant_shared_coin(p.variant);
   if (!variant_sched(p.variant) || !p.byz_plane || p.W == 0u || p.W > kMaxW || p.q > p.m ||
       (p.byz_strategy != BO_BYZ_BALANCE && p.byz_strategy != BO_BYZ_SPLIT) || shared != (p.coin_common != 0u) ||
-      p.byz_n > p.m - p.q || plan.wave_bytes < byz_wave_bytes(p.W, 0u) ||
+      (p.rule_on && (!variant_rule_b(p.variant) || rule::check(p.rule, nullptr) != BO_OK)) || p.byz_n > p.m - p.q || plan.wave_bytes < byz_wave_bytes(p.W, 0u) ||
       plan.lds_bytes < p.hist_bytes + kWavesPerBlock * plan.wave_bytes)
     return hipErrorInvalidValue;
   return launch_lds(sched_entry(p), p, grid, s);

@@ -241,7 +241,8 @@ enum {
  * is NOT RANDOM_TALLY3's plan, the rule differs: it runs this mode's kernel with
  * every step wave-uniform and no stream-10 or stream-11 word, the same results
  * at every byz_one and strategy (f = F then gives m == q).  Not modelled: what
- * BYZ_TALLY does not model, other rules (Protocol A, Bracha).
+ * BYZ_TALLY does not model, Bracha's protocol.  Other threshold rules, Protocol A
+ * among them, run on this mode's plan through bo_plan_create_rule (below).
  * Batch API only (no network API; `sweep --mode byzb` draws its (N, F, b) diagram). */
 /* BYZ_COIN is BYZ_TALLY word for word, and BYZ_RULE_B_COIN is BYZ_RULE_B word for
  * word, with a shared coin (Rabin's, or its weak form): the word
@@ -738,6 +739,64 @@ int bo_lumped_trial(const bo_lumped_cfg *cfg, uint64_t trial, bo_lumped_state *o
  * bits) gives the count lo + #{ i : thr[i] <= u }.  Exactly what bo_lumped_run uploads.
  * Host only, no device needed. */
 int bo_binom_half_cdf(uint32_t k, uint32_t *lo_out, uint64_t *thr_out, uint32_t cap, uint32_t *n_out);
+
+/* ---- threshold rules: Protocol A and any other rule of three words ----
+ *
+ * The reference's rule, Protocol B and Ben-Or's crash-tolerant Protocol A (N > 2t) are all
+ * threshold rules on a receiver's counts (c0, c1): one rule of three runtime words covers
+ * them.  Let v be the value with the strictly larger count (none on c0 == c1, an empty tally
+ * included):
+ *   R-phase: propose v iff v exists and 2 c_v > propose_gt2; otherwise propose "?".
+ *   P-phase: if v exists and c_v > adopt_gt: x = v, and the node has decided iff also
+ *     2 c_v > decide_gt2 (sticky; x is recomputed every round).  Otherwise x is the node's
+ *     coin, under the mode's coin policy (RANDOM_TALLY3's coin stream; in a common round of a
+ *     shared coin, that round's bit).
+ * Presets:
+ *   Protocol A (bo_rule_protocol_a)  (N, 0, 2F): propose v iff more than N / 2 of the
+ *     messages heard carry v (the reference proposes the bare majority of the N - F heard);
+ *     adopt the strict majority of the proposals, decide on more than F of them.  At most one
+ *     value is proposed in a round by the honest nodes, whatever the scheduler delivers, so
+ *     with b = 0 and N > 2F no trial ends in the last bin.  Not built for Byzantine nodes.
+ *   Protocol B (bo_rule_protocol_b)  (N + F, F, N + F): BYZ_RULE_B's rule at every count.
+ *   (0, 0, 2F): the reference's rule whenever N <= 3F + 1.  Beyond, a receiver can count
+ *     more than F of both values (N = 3F + 2: c0 = c1 = F + 1), where the reference decides 0
+ *     and this rule takes the coin; a rule that prefers 0 there is not modelled.
+ * Every word is at most 2^31 - 1 and reserved is 0; anything else is
+ * BO_ERR_INVALID_ARGUMENT with a text that names the word.
+ *
+ * The _rule entries run an existing mode with Protocol B's rule replaced by the words.
+ * bo_plan_create_rule accepts cfg->mode BO_MODE_BYZ_RULE_B, BO_MODE_BYZ_RULE_B_COIN or
+ * BO_MODE_SCHED_RULE_B only (any other mode: BO_ERR_INVALID_ARGUMENT); the plan is that
+ * mode's plan word for word -- validation, strategies, streams and tables, coin_common
+ * (mode 11 at coin_common == 0 is mode 9's plan), b = 0 valid and no other mode's plan,
+ * per-node states, the histogram layout, bo_plan_launch / bo_plan_run / bo_plan_check --
+ * and bo_plan_kernel reports the base plan's variant (15, 17, 19 or 21); only the rule
+ * differs, and bo_plan_rule tells.  With bo_rule_protocol_b's words every histogram and
+ * state is the plain plan's bit for bit, on kernel entries of their own.
+ * bo_run_trial_states_rule is bo_run_trial_states for such a plan (nodes_out holds n >= N
+ * entries).  The bo_lumped_*_rule entries are bo_lumped_* with the words in the place of
+ * cfg->rule, which is not read.  ABI version and every struct above are unchanged. */
+typedef struct bo_rule {
+    uint32_t propose_gt2;     /* R-phase: propose v iff 2 c_v > propose_gt2 */
+    uint32_t adopt_gt;        /* P-phase: adopt v iff c_v > adopt_gt */
+    uint32_t decide_gt2;      /* ... and decide iff also 2 c_v > decide_gt2 */
+    uint32_t reserved;        /* 0 */
+} bo_rule;
+
+/* The presets above (BO_ERR_INVALID_ARGUMENT if out is NULL or a word would exceed 2^31 - 1).
+ * Host only, no device needed. */
+int bo_rule_protocol_a(uint32_t N, uint32_t F, bo_rule *out);
+int bo_rule_protocol_b(uint32_t N, uint32_t F, bo_rule *out);
+
+int bo_plan_create_rule(const bo_trials_cfg *cfg, const bo_rule *rule, bo_plan **out);
+int bo_run_trial_states_rule(const bo_trials_cfg *cfg, const bo_rule *rule, uint64_t trial, bo_node_state *nodes_out,
+                             uint32_t n);
+/* 1 and the rule (out may be NULL) if the plan runs a replaced rule, else 0; negative error code for a NULL plan. */
+int bo_plan_rule(const bo_plan *plan, bo_rule *out);
+int bo_lumped_check_rule(const bo_lumped_cfg *cfg, const bo_rule *rule);
+int bo_lumped_run_rule(const bo_lumped_cfg *cfg, const bo_rule *rule, uint64_t trial_begin, uint64_t trial_count,
+                       uint64_t *hist_host);
+int bo_lumped_trial_rule(const bo_lumped_cfg *cfg, const bo_rule *rule, uint64_t trial, bo_lumped_state *out);
 
 /* ---- diagnostics ---- */
 

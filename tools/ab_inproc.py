@@ -86,6 +86,14 @@ figure to compare across levels.  Alone it times sizes the node level cannot hol
     python tools/ab_inproc.py --rounds 5 --reps 3 --shapes "16777216,3355443,1000000,0" --variants \
         "cls=mode:byzb,byzantine:16,byz_strategy:balance,delivery:adversarial,level:class"
 
+`rule:a`, `rule:b` or `rule:P:A:D` on a mode:byzb line replaces Protocol B's rule by a threshold rule of three
+runtime words (Protocol A's words (N, 0, 2F), Protocol B's own, or the words given), at either
+delivery and level.  With `rule:b` both sides produce the same outcomes, so next to the same line without it the
+ratio is the cost of runtime thresholds; `rule:a` changes the rounds by design (compare ns_per_trial_round):
+
+    python tools/ab_inproc.py --rounds 5 --reps 3 --shapes "1024,204,100000,0" --variants \
+        "m13=mode:byzb,byzantine:16,byz_strategy:split,delivery:adversarial;thr=mode:byzb,byzantine:16,byz_strategy:split,delivery:adversarial,rule:b;a=mode:byzb,byzantine:16,byz_strategy:split,delivery:adversarial,rule:a"
+
 Every line also reports
 the live node-rounds per second its launches represent (bench.py node_rounds)
 and the rounds a trial ran on average (k_max for an undecided one),
@@ -94,6 +102,7 @@ so variants that change the outcome (a diagnostic cap, a lie strategy) compare p
 import argparse
 import json
 import os
+import re
 import statistics
 import sys
 
@@ -128,7 +137,8 @@ def main():
         shapes.append((v[0], v[1], v[2], v[3] if len(v) > 3 else v[1]))
     modes = {name: env.pop("mode", None) for name, env in variants}   # `mode` is no environment variable
     scheds = {name: {k: env.pop(k) for k in ("crash_count", "crash_window", "crash_at", "crash_cut", "crash_reach",
-                                             "byzantine", "byz_one", "byz_strategy", "coin_common", "delivery", "level")
+                                             "byzantine", "byz_one", "byz_strategy", "coin_common", "delivery", "level",
+                                             "rule")
                      if k in env}
               for name, env in variants}                              # ... nor is the crash schedule
     knobs = sorted({k for _, env in variants for k in env})
@@ -145,7 +155,7 @@ def main():
     bad = sorted({v for v in modes.values() if v is not None and v not in mode_ids})
     if bad:
         ap.error(f"mode must be one of {sorted(mode_ids)}: {bad}")
-    byz_keys = ("byzantine", "byz_one", "byz_strategy", "coin_common", "delivery", "level")
+    byz_keys = ("byzantine", "byz_one", "byz_strategy", "coin_common", "delivery", "level", "rule")
     if any(any(k in sc for k in byz_keys) != (modes[name] in ("byz", "byzb")) for name, sc in scheds.items()):
         ap.error("byzantine / byz_one / byz_strategy go with mode:byz or mode:byzb, and they with them")
     if any(sc.get("delivery", "random") not in ("random", "adversarial") for sc in scheds.values()):
@@ -156,6 +166,10 @@ def main():
         ap.error("level is node or class")
     if any(sc.get("level") == "class" and sc.get("delivery") != "adversarial" for sc in scheds.values()):
         ap.error("level:class needs delivery:adversarial")
+    if any("rule" in sc and modes[name] != "byzb" for name, sc in scheds.items()):
+        ap.error("rule needs mode:byzb (it replaces Protocol B's rule)")
+    if any("rule" in sc and sc["rule"] not in ("a", "b") and not re.fullmatch(r"\d+:\d+:\d+", sc["rule"]) for sc in scheds.values()):
+        ap.error("rule is a, b or three words P:A:D")
     if any(any(k not in byz_keys for k in sc) and modes[name] not in ("crash", "partial", "subset")
            for name, sc in scheds.items()):
         ap.error("crash_count / crash_window / crash_at need mode:crash, mode:partial or mode:subset")
@@ -163,6 +177,15 @@ def main():
         ap.error("crash_cut needs mode:partial")
     if any("crash_reach" in sc and modes[name] != "subset" for name, sc in scheds.items()):
         ap.error("crash_reach needs mode:subset")
+
+    def thresholds(name, N, F):
+        """The `rule` pseudo-variable: Protocol A's or Protocol B's words at the shape, or the three words."""
+        text = scheds[name].get("rule")
+        if text is None:
+            return {}
+        if text in ("a", "b"):
+            return {"thresholds": benor.rule_protocol_a(N, F) if text == "a" else benor.rule_protocol_b(N, F)}
+        return {"thresholds": tuple(int(w) for w in text.split(":"))}
 
     def schedule(name, N, f):
         sc, kw = dict(scheds[name]), {}
@@ -201,7 +224,8 @@ def main():
             kw = schedule(name, N, f)
             self.plan = benor.LumpedPlan(N, F, f=f, b=sum(kw["byzantine"]), byz_even=(sum(kw["byzantine"]) + 1) // 2,
                                          rule=1 if modes[name] == "byzb" else 0, byz_strategy=kw["byz_strategy"],
-                                         coin_common=kw.get("coin_common", 0), seed=0x5EED + N, k_max=32)
+                                         coin_common=kw.get("coin_common", 0), seed=0x5EED + N, k_max=32,
+                                         **thresholds(name, N, F))
             self.hist_len = self.plan.hist_len
             self.host = np.zeros(self.hist_len, dtype=np.uint64)
 
@@ -238,7 +262,7 @@ def main():
                 plans[key] = ClassLevel(name, N, F, f)
             if key not in plans:
                 plans[key] = benor.TrialsPlan(N, F, [i < f for i in range(N)], seed=0x5EED + N, k_max=32, mode=mode,
-                                              **schedule(name, N, f))
+                                              **schedule(name, N, f), **thresholds(name, N, F))
             plans[name] = plans[key]
         h = torch.zeros(plans[variants[0][0]].hist_len, dtype=torch.int64, device="cuda")
         for name, env in variants:                    # warm-up per variant (allocations, code load)
