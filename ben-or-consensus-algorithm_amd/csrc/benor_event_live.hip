@@ -69,7 +69,7 @@ __device__ __forceinline__ uint64_t smix(uint64_t z) {
 // LDS hash slots per batch (a power of two, KParams::ev_hs): four times the
 // batch where LDS allows, else twice -- a wave's slowest lane probes about
 // twice as far at load 1/2 as at 1/4, one LDS round trip per probe
-constexpr uint32_t pow2_ceil(uint32_t v) { uint32_t r = 1u; while (r < v) r <<= 1; return r; }
+// (event_wg_slots, benor_event_sizes.h)
 
 // The control block: the round state the control wave publishes for the next
 // batch, and the batch's reduction words (double-buffered by batch parity:
@@ -1519,36 +1519,18 @@ __global__ void __launch_bounds__(64) benor_event_reg_kernel(KParams p) {
   if (box) __builtin_amdgcn_s_waitcnt(0x0F70);     // the last poll lands before the wave ends
 }
 
-uint32_t event_wg_waves(const KParams &p) {
-  const uint32_t forced = knob_u32("BENOR_LIVE_WAVES", 0u);
-  if (forced == 1u || forced == 3u || forced == 7u || forced == 15u) return forced;
-  if (p.N <= 32u) return 1u;
-  if (p.N <= 128u) return 3u;
-  if (p.N <= 512u) return 7u;
-  return 15u;
-}
+// The sizes are benor_event_sizes.h's (plain C++: tests/event_lds_check.cpp sweeps them on the host).
+static_assert(sizeof(Ctl) == kEventWgCtlBytes, "benor_event_sizes.h sizes the control block");
 
-bool event_wg_lds_pool(const KParams &p) { return (uint64_t)p.ev_cap * 4u <= kEventBigLdsPool; }
+uint32_t event_wg_waves(const KParams &p) { return event_wg_waves_for(p.N, knob_u32("BENOR_LIVE_WAVES", 0u)); }
 
-static uint32_t wg_lds_bytes(const KParams &p, uint32_t W, uint32_t HS) {
-  const uint32_t N = p.N;
-  uint32_t b = ((uint32_t)sizeof(Ctl) + 15u) & ~15u;
-  b += 16u * N + 8u * 64u * 6u + 8u * HS + 8u * 64u + 8u * p.ev_rstops;   // ibox, killed/decided/comp, hash, Floyd set, keys
-  b += 8u * N + 3u * 4u * 64u * W;                                        // smax; bmax, nxt, tvs
-  b += 2u * ((N + 7u) & ~7u) * 2u + ((N + 15u) & ~15u);                   // ks, cidx, xs
-  if (event_wg_lds_pool(p)) b += 4u * p.ev_cap;
-  return b;
-}
+bool event_wg_lds_pool(const KParams &p) { return event_wg_pool_in_lds(p.ev_cap); }
 
-uint32_t event_wg_hash_slots(const KParams &p, uint32_t W) {
-  for (uint32_t f = 8u; f > 2u; f >>= 1) {
-    const uint32_t hs = pow2_ceil(f * 64u * W);
-    if (wg_lds_bytes(p, W, hs) <= 150u * 1024u) return hs;
-  }
-  return pow2_ceil(2u * 64u * W);
-}
+uint32_t event_wg_hash_slots(const KParams &p, uint32_t W) { return event_wg_slots(p.N, W, p.ev_cap, p.ev_rstops); }
 
-uint32_t event_wg_lds_bytes(const KParams &p, uint32_t W) { return wg_lds_bytes(p, W, event_wg_hash_slots(p, W)); }
+uint32_t event_wg_lds_bytes(const KParams &p, uint32_t W) { return event_wg_total_bytes(p.N, W, p.ev_cap, p.ev_rstops); }
+
+bool event_wg_lds_fits(const KParams &p) { return event_wg_fits(p.N, event_wg_waves(p), p.ev_cap, p.ev_rstops); }
 
 template <int W, bool LP, bool ST>
 static hipError_t launch_wg1(KParams p, int grid, hipStream_t s) {
@@ -1579,8 +1561,7 @@ static bool event_one_wave(const KParams &p) {
 
 uint32_t event_reg_regs(const KParams &p) {
   if (p.N > kEventRegMaxN || !event_one_wave(p) || knob_is("BENOR_EVENT_FORM", "wave")) return 0u;
-  const uint32_t need = (p.ev_cap + 63u) / 64u;
-  return need <= 16u ? 16u : (need <= 32u ? 32u : 0u);
+  return event_reg_pool_regs(p.ev_cap);
 }
 
 bool event_wave_form(const KParams &p) { return p.N <= kEventWaveMaxN && event_one_wave(p) && !event_reg_regs(p); }
@@ -1593,7 +1574,7 @@ hipError_t launch_event_wg(const KParams &p, int grid, hipStream_t s) {
   if (const uint32_t regs = event_reg_regs(p)) {
     // the one-register pool mode only where the pool starts there (m N <= 64):
     // compiled in, it slows the array form by 5-8 % (r06-G9, N = 12 and 16)
-    const bool sm = p.m * p.N <= 64u;
+    const bool sm = event_reg_one_register(p.m, p.N);
     if (regs == 16u && sm) hipLaunchKernelGGL((benor_event_reg_kernel<16, true>), dim3(grid), dim3(64), 0, s, p);
     else if (regs == 16u) hipLaunchKernelGGL((benor_event_reg_kernel<16, false>), dim3(grid), dim3(64), 0, s, p);
     else if (sm) hipLaunchKernelGGL((benor_event_reg_kernel<32, true>), dim3(grid), dim3(64), 0, s, p);

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "benor.h"
+#include "benor_event_sizes.h"
 #include "benor_lumped.h"
 #include "benor_mfma_sched.h"
 #include "benor_mfma_strip.h"
@@ -287,8 +288,7 @@ hipError_t launch_lumped(const LumpedParams &p, int grid_blocks, hipStream_t str
 
 // Event level for kMaxEventN < N <= BO_MAX_N (benor_event_big.hip): one wave per trial.
 // The wave-per-trial event kernel keeps its message pool in LDS when it is at
-// most this many bytes (4N^2 + 64 u32: N <= 78).
-constexpr uint64_t kEventBigLdsPool = 96u * 1024u;
+// most kEventBigLdsPool bytes (benor_event_sizes.h: N <= 78).
 bool event_big_lds_pool(const KParams &p);
 uint32_t event_big_lds_bytes(const KParams &p);
 hipError_t launch_event_big(const KParams &p, int grid_blocks, hipStream_t stream);
@@ -308,7 +308,10 @@ uint32_t event_reg_regs(const KParams &p);
 bool event_wave_form(const KParams &p);
 uint32_t event_wave_lds_bytes(const KParams &p);
 bool event_wg_lds_pool(const KParams &p);
-uint32_t event_wg_lds_bytes(const KParams &p, uint32_t waves);
+uint32_t event_wg_lds_bytes(const KParams &p, uint32_t waves);   // sized by benor_event_sizes.h
+// Whether the plan's workgroup fits the device's LDS (kEventWgLdsLimit).  It does at every N of a live run and of
+// an explicit schedule; a random /stop schedule of some 1600 stops at N ~ 4096 does not (8 bytes of keys each).
+bool event_wg_lds_fits(const KParams &p);
 hipError_t launch_event_wg(const KParams &p, int grid_blocks, hipStream_t stream);
 
 // Per-shape launchers, explicitly instantiated in benor_w_*.hip (W = 1..32)

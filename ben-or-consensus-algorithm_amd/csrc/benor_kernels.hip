@@ -636,7 +636,7 @@ void plan_geometry(KParams &p) {
     p.variant = 5;
     p.wave_bytes = 0;
     p.ev_wg = wg ? 1u : 0u;
-    p.ev_cap = 4u * p.N * p.N + 64u;
+    p.ev_cap = event_pool_cap(p.N);
     p.ev_stride = p.ev_cap;                          // u32 messages
     p.lds_bytes = wg ? event_wg_lds_bytes(p, event_wg_waves(p)) : event_big_lds_bytes(p);
     return;
@@ -649,8 +649,8 @@ void plan_geometry(KParams &p) {
     // N <= kMaxEventLdsN: the inbox counters live in LDS, 8N u16 per lane of the
     // 256-lane workgroup (EvBox)
     p.lds_bytes = p.hist_bytes + (p.N <= kMaxEventLdsN ? 256u * 8u * p.N * 2u : 0u);
-    const uint32_t NW = p.N <= 64u ? 1u : 4u;
-    p.ev_cap = 4u * p.N * p.N + 64u;
+    const uint32_t NW = p.N <= kEventLaneOneWordMaxN ? 1u : 4u;
+    p.ev_cap = event_pool_cap(p.N);
     // per-lane scratch (u32 words): pool, inbox window, comp[4][NW] (u64), crash[N] (u64), xs (i8), ks (i16)
     p.ev_stride = (((p.ev_cap + 1u) >> 1) + 1u & ~1u) + p.N * 8u + 8u * NW + 2u * p.N + ((p.N + 3u) & ~3u) / 4u +
                   (p.N + 1u) / 2u;
@@ -810,7 +810,7 @@ hipError_t launch_lockstep(const KParams &p, int grid, hipStream_t s) {
         if (e != hipSuccess) return e;
       }
       hipLaunchKernelGGL((benor_event_kernel<1, true>), dim3(grid), dim3(256), p.lds_bytes, s, p);
-    } else if (p.N <= 64u) {
+    } else if (p.N <= kEventLaneOneWordMaxN) {
       hipLaunchKernelGGL((benor_event_kernel<1, false>), dim3(grid), dim3(256), p.lds_bytes, s, p);
     } else {
       hipLaunchKernelGGL((benor_event_kernel<4, false>), dim3(grid), dim3(256), p.lds_bytes, s, p);

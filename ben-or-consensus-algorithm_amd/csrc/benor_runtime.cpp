@@ -997,6 +997,17 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
     if (rc) return rc;
   }
   benor::plan_geometry(kp);   // after init_q: the kernel choice depends on the round-1 vote parity
+  // The workgroup-batched event kernel holds a random /stop schedule's keys in LDS, 8 bytes a stop: at N near
+  // BO_MAX_N some 1600 of them pass the device's limit, and the launch would fail in hipFuncSetAttribute.  Only a
+  // batch plan under BENOR_EVENT_FORM=wg gets there (a live run and a network start carry no crash_count, and
+  // without the knob such a plan runs the wave-per-trial kernel, whose keys are in global memory): refused here,
+  // not rerouted, since the knob exists to put a plan on this kernel.
+  if (kp.variant == 5u && kp.ev_wg && !benor::event_wg_lds_fits(kp))
+    return fail(BO_ERR_UNSUPPORTED,
+                "event level on the workgroup-batched kernel (BENOR_EVENT_FORM=wg): " + std::to_string(kp.lds_bytes) +
+                    " bytes of LDS exceed the device's " + std::to_string(benor::kEventWgLdsLimit) +
+                    " (N = " + std::to_string(kp.N) + ", " + std::to_string(kp.ev_rstops) +
+                    " random stops at 8 bytes each): schedule fewer stops or run without the knob");
   return BO_OK;
 }
 

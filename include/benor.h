@@ -59,7 +59,10 @@ enum {
  * delivery counts.  Exactly F crash-faulty nodes; N <= 4096 (one lane per
  * trial up to N = 256, one wave per trial above).  Both /stop schedules --
  * explicit (crash_at) and random (crash_count, crash_window) -- work at every
- * N <= 4096. */
+ * N <= 4096.  (Under the validation knob BENOR_EVENT_FORM=wg a batch plan runs
+ * the live runs' workgroup kernel, which keeps a random schedule's keys in
+ * LDS: N near 4096 with more than some 1600 random stops is then refused with
+ * BO_ERR_UNSUPPORTED when the plan is made.) */
 /* RANDOM_TALLY is RANDOM_DELIVERY at the level of counts.  A receiver's rule
  * (node.ts:52-69, :88-113) reads only how many 0s and 1s its inbox holds, and
  * the inbox is a uniform (N-F)-subset of the m = N-f live senders, independent
