@@ -65,15 +65,11 @@ struct KParams {
   uint32_t W;               // u64 words per plane = ceil(m / 64) = receiver groups
   uint32_t G;               // receiver groups per tally block (template parameter); lane and matrix-core kernels: KIND
   uint32_t nblocks;         // ceil(W / G)
-  uint32_t variant;         // 7: matrix-core lockstep, round 1 (benor_mfma.h; the W kernel serves its state
-                            //    launches and the trials it defers),
-                            // 8: packed matrix-core lockstep (2 <= m <= 32, benor_mfma_small.h; the lane kernel
-                            //    serves its state launches),
-                            // 6: lane lockstep (m <= 64), 1: W-specialised lockstep (W <= kMaxWSpecialised = 32),
-                            // 0: blocked lockstep, 2: random delivery, 4 and 5: event level,
-                            // 9..21: the count-level kernels (benor_modes.h: kVar* and the variant_* predicates)
-  uint32_t base_variant;    // variant 7: the popcount kernel (1 W, 0 blocked) that serves the state
-  uint32_t base_G;          //   launches and the deferred trials, and its G
+  uint32_t variant;         // the kernel the plan runs: benor_modes.h, kVarBlocked .. kVarMfmaSmall (0..8) and the
+                            // count-level kVarTally .. (9..21), with the predicates over them; a state launch
+                            // or a short one may run another kernel (launched(), below)
+  uint32_t base_variant;    // kVarMfma: the popcount kernel (kVarW or kVarBlocked) that serves the state launches
+  uint32_t base_G;          //   and the deferred trials, and its G; kVarMfmaSmall: the lane kernel and its KIND
   uint32_t mode;            // BO_MODE_* of the plan: the configuration's, or the mode whose plan it is (the
                             // demotions of plan_host, benor_runtime.cpp; modes and families: benor_modes.h)
   uint32_t q;               // quorum N - F (messages each receiver tallies per phase)
@@ -228,18 +224,32 @@ const char *knob(const char *name);
 uint32_t knob_u32(const char *name, uint32_t dflt);
 bool knob_is(const char *name, const char *value);
 
+// What a launch is (benor_modes.h has the scalar forms).  A state launch writes per-node state (the network API).
+inline bool state_launch(const KParams &p) { return p.node_out || p.rounds_out; }
+inline bool mfma_batch(const KParams &p) { return mfma_batch(p.variant, p.G, p.W, state_launch(p)); }
+inline bool mfma_small_w_batch(const KParams &p) { return mfma_small_w_batch(p.variant, p.G, p.W, state_launch(p)); }
+inline bool mfma_big_batch(const KParams &p) { return mfma_big_batch(p.variant, p.G, p.W, state_launch(p)); }
+inline bool mfma_sure_batch(const KParams &p) { return mfma_sure_batch(p.variant, p.G, p.W, state_launch(p)); }
+inline bool mfma_defers(const KParams &p) { return mfma_defers(p.variant, p.G, p.W, state_launch(p)); }
+
 // The paired KIND 0 matrix-core kernel takes its strip form (benor_mfma.h
 // STRIP) on this plan: W >= 5 and at most 16 live rows in the last 32-row
 // receiver tile, from W = 7 on by the planner's rule (stripf::kPlannedMinW).
 // BENOR_MFMA_STRIP (validation): "0" keeps the 32-row form everywhere, "1"
 // takes the strip at W = 5 and 6 too and changes nothing on other shapes.
 inline bool mfma_strip_form(const KParams &p) {
-  if (p.variant != 7u || p.G != 0u || p.W > 16u || !stripf::eligible(p.W, p.m) || knob_is("BENOR_MFMA_PAIR", "0")) return false;
+  if (!mfma_sure_batch(p) || !stripf::eligible(p.W, p.m) || knob_is("BENOR_MFMA_PAIR", "0")) return false;
   return knob_is("BENOR_MFMA_STRIP", "1") || (stripf::planned(p.W, p.m) && !knob_is("BENOR_MFMA_STRIP", "0"));
 }
 
 // Pick the tally block size G and fill nblocks / LDS sizes.
 void plan_geometry(KParams &p);
+
+// The parameters of the kernel that a launch of `p` really runs: the plan's own kernel, or the kernel that
+// stands in for it on this launch (benor_kernels.hip).  launch_lockstep, lockstep_grid and block_waves start
+// from it; base_kernel is the stand-in itself (the runtime's deferral tail launches it on a trial list).
+KParams base_kernel(const KParams &p);
+KParams launched(const KParams &p);
 
 hipError_t launch_lockstep(const KParams &p, int grid_blocks, hipStream_t stream);
 

@@ -633,7 +633,7 @@ void plan_geometry(KParams &p) {
   if (p.mode == BO_MODE_EVENT && (p.N > kMaxEventN || wg)) {
     p.G = 1;
     p.nblocks = 1;
-    p.variant = 5;
+    p.variant = kVarEventWave;
     p.wave_bytes = 0;
     p.ev_wg = wg ? 1u : 0u;
     p.ev_cap = event_pool_cap(p.N);
@@ -644,7 +644,7 @@ void plan_geometry(KParams &p) {
   if (p.mode == BO_MODE_EVENT) {
     p.G = 1;
     p.nblocks = 1;
-    p.variant = 4;
+    p.variant = kVarEventLane;
     p.wave_bytes = 0;
     // N <= kMaxEventLdsN: the inbox counters live in LDS, 8N u16 per lane of the
     // 256-lane workgroup (EvBox)
@@ -660,7 +660,7 @@ void plan_geometry(KParams &p) {
   if (p.mode == BO_MODE_RANDOM_DELIVERY) {
     p.G = 1;
     p.nblocks = W;
-    p.variant = 2;
+    p.variant = kVarRandom;
     // sampler choice and parameters: oracle_delivery_bernoulli
     const uint32_t e = p.m - p.q, k = p.q <= e ? p.q : e;
     p.rd_a = p.rd_b = 0u;
@@ -702,7 +702,7 @@ void plan_geometry(KParams &p) {
     const bool odd = (p.m & 1u) && (M1 & 1u);        // every vote count odd: no tie, no coin
     p.G = odd ? (p.m > 2u * p.F ? 2u : 1u) : 0u;     // KIND (benor_lane.hip)
     p.nblocks = 1;
-    p.variant = 6;
+    p.variant = kVarLane;
     p.wave_bytes = 128u * 8u + 128u * 16u;          // init-word ring, coin-block ring
     p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
     // Packed matrix-core kernel (benor_mfma_small.h): 2 <= m <= 32, every
@@ -712,7 +712,7 @@ void plan_geometry(KParams &p) {
     if (p.m >= 2u && p.m <= kMaxSmallMfmaM && p.m > p.F && p.init_q == 0u && !knob_is("BENOR_NO_MFMA", "1")) {
       p.base_variant = p.variant;
       p.base_G = p.G;
-      p.variant = 8;
+      p.variant = kVarMfmaSmall;
       p.lds_bytes = p.hist_bytes + kWavesPerBlock * small_wave_words(p.m) * 4u;   // histogram, round lists
     }
     return;
@@ -722,7 +722,7 @@ void plan_geometry(KParams &p) {
   if (W <= (uint32_t)kMaxWSpecialised) {
     p.G = W;
     p.nblocks = 1;
-    p.variant = 1;
+    p.variant = kVarW;
     p.wave_bytes = (tb * WP + 2u * WP) * 8u;            // init ring, final x1 plane, decided bits
   } else {
     // Blocks of G = ceil(W / nb) in 11..22 groups: the fewest padded groups nb * G,
@@ -743,7 +743,7 @@ void plan_geometry(KParams &p) {
     const uint32_t XW = ((G * nb > WP ? G * nb : WP) + 1u) & ~1u;
     p.G = G;
     p.nblocks = nb;
-    p.variant = 0;
+    p.variant = kVarBlocked;
     p.wave_bytes = (tb * WP + XW) * 8u + G * nb * 16u + nb * 256u;   // ring, x1 plane, {p0,p1} plane, decided bits
   }
   // Matrix-core kernel (benor_mfma.h) for round 1 wherever a trial can halt
@@ -759,114 +759,10 @@ void plan_geometry(KParams &p) {
   if (can_halt && (p.m <= kMaxMfmaM || big_ok) && !knob_is("BENOR_NO_MFMA", "1")) {
     p.base_variant = p.variant;
     p.base_G = p.G;
-    p.variant = 7;
-    p.G = sure ? 0u : (p.m > 2u * p.F ? 1u : 2u);
+    p.variant = kVarMfma;
+    p.G = sure ? kKindSure : (p.m > 2u * p.F ? kKindMajority : kKindMinority);
   }
   p.lds_bytes = p.hist_bytes + kWavesPerBlock * p.wave_bytes;
-}
-
-template <int... Is>
-static hipError_t dispatch_w(const KParams &p, int grid, hipStream_t s, std::integer_sequence<int, Is...>) {
-  hipError_t e = hipErrorInvalidValue;
-  (void)((p.W == (uint32_t)(Is + 2) ? (e = launch_w<Is + 2>(p, grid, s), true) : false) || ...);
-  return e;
-}
-
-template <int... Is>
-static hipError_t dispatch_lane(const KParams &p, int grid, hipStream_t s, std::integer_sequence<int, Is...>) {
-  hipError_t e = hipErrorInvalidValue;
-  (void)((p.m == (uint32_t)(Is + 1) ? (e = launch_lane_m<Is + 1>(p, grid, s), true) : false) || ...);
-  return e;
-}
-
-template <int... Is>
-static hipError_t dispatch_mfma_small(const KParams &p, int grid, hipStream_t s, std::integer_sequence<int, Is...>) {
-  hipError_t e = hipErrorInvalidValue;
-  (void)((p.m == (uint32_t)(Is + 2) ? (e = launch_mfma_small_m<Is + 2>(p, grid, s), true) : false) || ...);
-  return e;
-}
-
-template <int... Is>
-static hipError_t dispatch_mfma(const KParams &p, int grid, hipStream_t s, std::integer_sequence<int, Is...>) {
-  hipError_t e = hipErrorInvalidValue;
-  (void)((p.W == (uint32_t)(Is + 2) ? (e = launch_mfma<Is + 2>(p, grid, s), true) : false) || ...);
-  return e;
-}
-
-// W in 33..64: G in 11..22 (plan_geometry)
-template <int... Is>
-static hipError_t dispatch_b(const KParams &p, int grid, hipStream_t s, std::integer_sequence<int, Is...>) {
-  hipError_t e = hipErrorInvalidValue;
-  (void)((p.G == (uint32_t)(Is + 11) ? (e = launch_b<Is + 11>(p, grid, s), true) : false) || ...);
-  return e;
-}
-
-hipError_t launch_lockstep(const KParams &p, int grid, hipStream_t s) {
-  if (p.variant == 4) {
-    if (p.N <= kMaxEventLdsN) {
-      if (p.lds_bytes > 64u * 1024u) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&benor_event_kernel<1, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
-        if (e != hipSuccess) return e;
-      }
-      hipLaunchKernelGGL((benor_event_kernel<1, true>), dim3(grid), dim3(256), p.lds_bytes, s, p);
-    } else if (p.N <= kEventLaneOneWordMaxN) {
-      hipLaunchKernelGGL((benor_event_kernel<1, false>), dim3(grid), dim3(256), p.lds_bytes, s, p);
-    } else {
-      hipLaunchKernelGGL((benor_event_kernel<4, false>), dim3(grid), dim3(256), p.lds_bytes, s, p);
-    }
-    return hipGetLastError();
-  }
-  if (p.variant == 5) return p.ev_wg ? launch_event_wg(p, grid, s) : launch_event_big(p, grid, s);
-  if (p.variant == 6) return dispatch_lane(p, grid, s, std::make_integer_sequence<int, (int)kMaxLaneM>{});
-  if (p.variant == 8 && !small_on_lane(p))
-    return dispatch_mfma_small(p, grid, s, std::make_integer_sequence<int, (int)kMaxSmallMfmaM - 1>{});   // m = 2..32
-  if (p.variant == 8) {                      // state launch or short launch of a packed shape: the lane kernel
-    KParams q = p;
-    q.variant = p.base_variant;
-    q.G = p.base_G;
-    q.lds_bytes = q.hist_bytes + kWavesPerBlock * q.wave_bytes;
-    return launch_lockstep(q, grid, s);
-  }
-  if (variant_count_level(p.variant)) {
-    const CountLevelKernel *k = count_level_kernel(p.variant);
-    return k ? k->launch(p, grid, s) : hipErrorInvalidValue;
-  }
-  if (p.variant == 2 && p.rd_a) return launch_random_bern(p, grid, s);
-  if (p.variant == 2) {                      // Floyd sampler
-    if (p.lds_bytes > 64u * 1024u) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&benor_random_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(benor_random_kernel, dim3(grid), dim3(64 * kWavesPerBlock), p.lds_bytes, s, p);
-    return hipGetLastError();
-  }
-  if (p.variant == 7 && !p.node_out && !p.rounds_out) {
-    if (p.W > 16u) return launch_mfma_big(p, grid, s);                                                        // W = 17..64
-    return dispatch_mfma(p, grid, s, std::make_integer_sequence<int, 15>{});                                  // W = 2..16
-  }
-  if (p.variant == 7) {                      // state launch of a matrix-core shape: its popcount kernel
-    KParams q = p;
-    q.variant = p.base_variant;
-    q.G = p.base_G;
-    return launch_lockstep(q, grid, s);
-  }
-  if (p.variant == 1)
-    return dispatch_w(p, grid, s, std::make_integer_sequence<int, kMaxWSpecialised - 1>{});                    // W = 2..32
-  return dispatch_b(p, grid, s, std::make_integer_sequence<int, 12>{});
-}
-
-// The big-network matrix-core kernel holds 9-33 KB of LDS per wave; its
-// workgroup size is chosen for occupancy (mfma_big_block_waves).  Every other
-// kernel: kWavesPerBlock.
-uint32_t block_waves(const KParams &p) {
-  if (mfma_big_coop(p)) return mfma_coop_block_waves(p);
-  return (p.variant == 7 && p.W > 16u && !p.node_out && !p.rounds_out) ? mfma_big_block_waves(p) : (uint32_t)kWavesPerBlock;
-}
-
-uint64_t defer_units(const KParams &p, int grid) {
-  return mfma_big_coop(p) ? (uint64_t)grid : (uint64_t)grid * block_waves(p);
 }
 
 // A packed-shape launch runs on the lane kernel when it writes per-node
@@ -875,15 +771,106 @@ uint64_t defer_units(const KParams &p, int grid) {
 // (DESIGN §4.2).
 // BENOR_SMALL_MIN_TRIALS overrides the crossover (validation knob).
 bool small_on_lane(const KParams &p) {
-  if (p.node_out || p.rounds_out) return true;
+  if (state_launch(p)) return true;
   return p.trial_count < knob_u32("BENOR_SMALL_MIN_TRIALS", (uint32_t)kSmallMinTrials);
 }
 
-template <int... Is>
-static int dispatch_mfma_blocks(const KParams &p, std::integer_sequence<int, Is...>) {
-  int n = 0;
-  (void)((p.W == (uint32_t)(Is + 2) ? (n = mfma_sure_blocks_per_cu<Is + 2>(p), true) : false) || ...);
-  return n;
+// The kernel that stands in for a matrix-core plan's own: the popcount kernel (W or blocked) planned under
+// kVarMfma, the lane kernel planned under kVarMfmaSmall, with that kernel's LDS plan.  Under kVarMfma the
+// expression is also what plan_geometry left in lds_bytes (it sets the word after the override), so there it
+// changes nothing; under kVarMfmaSmall it replaces the packed kernel's size.
+KParams base_kernel(const KParams &p) {
+  KParams q = p;
+  q.variant = p.base_variant;
+  q.G = p.base_G;
+  q.lds_bytes = q.hist_bytes + kWavesPerBlock * q.wave_bytes;
+  return q;
+}
+
+// The one answer to "which kernel does this launch run": the plan's own, except that a state launch of a
+// matrix-core shape runs its popcount kernel, and a state launch or a short launch of a packed shape the lane
+// kernel.  The result is never a plan with a stand-in of its own, so nobody resolves twice.
+KParams launched(const KParams &p) {
+  if (p.variant == kVarMfma && state_launch(p)) return base_kernel(p);
+  if (p.variant == kVarMfmaSmall && small_on_lane(p)) return base_kernel(p);
+  return p;
+}
+
+// The instantiation whose template argument equals `key`, among first .. first + count - 1: f is a generic
+// lambda called with that value as a std::integral_constant; `none` when no value matches.
+template <int First, typename R, typename F, int... Is>
+static R dispatch_seq(uint32_t key, R none, F f, std::integer_sequence<int, Is...>) {
+  R r = none;
+  (void)((key == (uint32_t)(First + Is) ? (r = f(std::integral_constant<int, First + Is>{}), true) : false) || ...);
+  return r;
+}
+template <int First, int Count, typename R, typename F>
+static R dispatch(uint32_t key, R none, F f) {
+  return dispatch_seq<First>(key, none, f, std::make_integer_sequence<int, Count>{});
+}
+
+static hipError_t launch_event_lane(const KParams &p, int grid, hipStream_t s) {
+  if (p.N <= kMaxEventLdsN) {
+    if (p.lds_bytes > 64u * 1024u) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&benor_event_kernel<1, true>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+      if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((benor_event_kernel<1, true>), dim3(grid), dim3(256), p.lds_bytes, s, p);
+  } else if (p.N <= kEventLaneOneWordMaxN) {
+    hipLaunchKernelGGL((benor_event_kernel<1, false>), dim3(grid), dim3(256), p.lds_bytes, s, p);
+  } else {
+    hipLaunchKernelGGL((benor_event_kernel<4, false>), dim3(grid), dim3(256), p.lds_bytes, s, p);
+  }
+  return hipGetLastError();
+}
+
+static hipError_t launch_random_floyd(const KParams &p, int grid, hipStream_t s) {
+  if (p.lds_bytes > 64u * 1024u) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&benor_random_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(benor_random_kernel, dim3(grid), dim3(64 * kWavesPerBlock), p.lds_bytes, s, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_lockstep(const KParams &plan, int grid, hipStream_t s) {
+  const KParams p = launched(plan);
+  const hipError_t none = hipErrorInvalidValue;
+  if (variant_count_level(p.variant)) {
+    const CountLevelKernel *k = count_level_kernel(p.variant);
+    return k ? k->launch(p, grid, s) : none;
+  }
+  switch (p.variant) {
+    case kVarEventLane: return launch_event_lane(p, grid, s);
+    case kVarEventWave: return p.ev_wg ? launch_event_wg(p, grid, s) : launch_event_big(p, grid, s);
+    case kVarLane:                                                                          // m = 1..64
+      return dispatch<1, (int)kMaxLaneM>(p.m, none, [&](auto m) { return launch_lane_m<decltype(m)::value>(p, grid, s); });
+    case kVarMfmaSmall:                                                                     // m = 2..32
+      return dispatch<2, (int)kMaxSmallMfmaM - 1>(p.m, none, [&](auto m) { return launch_mfma_small_m<decltype(m)::value>(p, grid, s); });
+    case kVarRandom: return p.rd_a ? launch_random_bern(p, grid, s) : launch_random_floyd(p, grid, s);
+    case kVarMfma:                                                                          // W = 17..64, W = 2..16
+      if (mfma_big_batch(p)) return launch_mfma_big(p, grid, s);
+      return dispatch<2, (int)kMfmaRegMaxW - 1>(p.W, none, [&](auto w) { return launch_mfma<decltype(w)::value>(p, grid, s); });
+    case kVarW:                                                                             // W = 2..32
+      return dispatch<2, kMaxWSpecialised - 1>(p.W, none, [&](auto w) { return launch_w<decltype(w)::value>(p, grid, s); });
+    default:                                                          // kVarBlocked, W in 33..64: G in 11..22 (plan_geometry)
+      return dispatch<11, 12>(p.G, none, [&](auto g) { return launch_b<decltype(g)::value>(p, grid, s); });
+  }
+}
+
+// The big-network matrix-core kernel holds 9-33 KB of LDS per wave; its
+// workgroup size is chosen for occupancy (mfma_big_block_waves).  Every other
+// kernel: kWavesPerBlock.
+uint32_t block_waves(const KParams &plan) {
+  const KParams p = launched(plan);
+  if (mfma_big_coop(p)) return mfma_coop_block_waves(p);
+  return mfma_big_batch(p) ? mfma_big_block_waves(p) : (uint32_t)kWavesPerBlock;
+}
+
+uint64_t defer_units(const KParams &p, int grid) {
+  return mfma_big_coop(p) ? (uint64_t)grid : (uint64_t)grid * block_waves(p);
 }
 
 // Resident workgroups per CU of the KIND 0 matrix-core kernel (W <= 16): the
@@ -894,7 +881,7 @@ static uint32_t mfma_resident_per_cu(const KParams &p) {
   };
   static thread_local Last last = {0u, 0u, 0u, 0u};
   if (last.v && last.W == p.W && last.m == p.m && last.lds == p.hist_bytes) return last.v;
-  const int n = dispatch_mfma_blocks(p, std::make_integer_sequence<int, 15>{});
+  const int n = dispatch<2, (int)kMfmaRegMaxW - 1>(p.W, 0, [&](auto w) { return mfma_sure_blocks_per_cu<decltype(w)::value>(p); });
   const uint32_t v = n >= 1 && n <= 8 ? (uint32_t)n : 8u;
   last = Last{p.W, p.m, p.hist_bytes, v};
   return v;
@@ -904,7 +891,7 @@ static uint32_t mfma_resident_per_cu(const KParams &p) {
 // paired kernel.  BENOR_MFMA_DYNAMIC (validation): "0" static, "1" dynamic on
 // any such launch; BENOR_MFMA_CHUNK (tuning): C of the dynamic form, 1..64.
 uint32_t mfma_chunk(const KParams &p, int device) {
-  if (p.variant != 7 || p.G != 0u || p.W > 16u || p.node_out || p.rounds_out) return 0u;
+  if (!mfma_sure_batch(p)) return 0u;
   const bool forced = knob_is("BENOR_MFMA_DYNAMIC", "1");
   if (knob_is("BENOR_MFMA_DYNAMIC", "0") || knob_is("BENOR_MFMA_PAIR", "0")) return 0u;
   int cus = 256;
@@ -921,73 +908,65 @@ uint32_t mfma_chunk(const KParams &p, int device) {
   return c;
 }
 
-// Resident workgroups per CU of a count-level variant's kernel (0 = unknown).
-static int count_level_blocks_per_cu(const KParams &p) {
-  const CountLevelKernel *k = count_level_kernel(p.variant);
-  return k ? k->blocks_per_cu(p) : 0;
+// ---- lockstep_grid, family by family (p: the launched kernel's parameters; cus: the device's CU count)
+static int at_least_one(uint64_t grid) { return (int)(grid < 1u ? 1u : grid); }
+
+// Event level, one wave or workgroup per trial: grid = the scratch's trial slots
+static int event_wave_grid(const KParams &p) { return at_least_one(p.trial_count < p.ev_lanes ? p.trial_count : p.ev_lanes); }
+
+// Event level, one lane per trial: grid = the scratch's lane count
+static int event_lane_grid(const KParams &p) {
+  const uint64_t blocks_needed = (p.trial_count + 255u) / 256u;
+  uint64_t grid = p.ev_lanes / 256u;
+  if (blocks_needed < grid) grid = blocks_needed;
+  return at_least_one(grid);
 }
 
-int lockstep_grid(const KParams &p, int device) {
-  int cus = 256;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-  if (p.variant == 5) {   // big event level: one wave per trial, grid = the scratch's trial slots
-    const uint64_t g = p.trial_count < p.ev_lanes ? p.trial_count : p.ev_lanes;
-    return (int)(g < 1u ? 1u : g);
+// Packed matrix-core kernel: a wave runs batches of 64 S trials (fresh
+// round-1 batches strided over the waves, then its own round lists), so
+// each wave gets ~3 fresh batches, at most 4 workgroups per CU.
+static int mfma_small_grid(const KParams &p, int cus) {
+  const uint64_t batch = 64u * small_slots(p.m);
+  const uint64_t groups = (p.trial_count + batch - 1u) / batch;
+  uint64_t per_cu = groups / ((uint64_t)cus * kWavesPerBlock * 3u);
+  uint64_t cap = lds_groups_per_cu(p.lds_bytes);
+  if (cap > 4u) cap = 4u;
+  if (per_cu > cap) per_cu = cap;
+  if (per_cu < 1u) per_cu = 1u;
+  {                                        // tuning knob
+    const uint64_t v = knob_u32("BENOR_BLOCKS_PER_CU", 0u);
+    if (v >= 1u && v <= lds_groups_per_cu(p.lds_bytes)) per_cu = v;
   }
-  if (p.variant == 4) {   // event mode: one lane per trial, grid = the scratch's lane count
-    const uint64_t blocks_needed = (p.trial_count + 255u) / 256u;
-    uint64_t grid = p.ev_lanes / 256u;
-    if (blocks_needed < grid) grid = blocks_needed;
-    return (int)(grid < 1 ? 1 : grid);
-  }
-  if (p.variant == 8) {
-    if (small_on_lane(p)) {                  // state launch or short launch: the lane kernel
-      KParams q = p;
-      q.variant = p.base_variant;
-      q.G = p.base_G;
-      q.lds_bytes = q.hist_bytes + kWavesPerBlock * q.wave_bytes;
-      return lockstep_grid(q, device);
-    }
-    // Packed matrix-core kernel: a wave runs batches of 64 S trials (fresh
-    // round-1 batches strided over the waves, then its own round lists), so
-    // each wave gets ~3 fresh batches, at most 4 workgroups per CU.
-    const uint64_t batch = 64u * small_slots(p.m);
-    const uint64_t groups = (p.trial_count + batch - 1u) / batch;
-    uint64_t per_cu = groups / ((uint64_t)cus * kWavesPerBlock * 3u);
-    uint64_t cap = lds_groups_per_cu(p.lds_bytes);
-    if (cap > 4u) cap = 4u;
-    if (per_cu > cap) per_cu = cap;
-    if (per_cu < 1u) per_cu = 1u;
-    {                                        // tuning knob
-      const uint64_t v = knob_u32("BENOR_BLOCKS_PER_CU", 0u);
-      if (v >= 1u && v <= lds_groups_per_cu(p.lds_bytes)) per_cu = v;
-    }
-    uint64_t grid = (uint64_t)cus * per_cu;
-    const uint64_t need = (groups + kWavesPerBlock - 1u) / kWavesPerBlock;
-    if (need < grid) grid = need;
-    return (int)(grid < 1u ? 1u : grid);
-  }
-  if (mfma_big_coop(p)) {   // cooperative big-network form: one 32-trial group per workgroup at a time
-    const uint64_t groups = (p.trial_count + 31u) / 32u;
-    uint64_t grid = (uint64_t)cus * (uint64_t)mfma_coop_blocks_per_cu(p);
-    if (groups < grid) grid = groups;
-    return (int)(grid < 1u ? 1u : grid);
-  }
-  // 32 waves per CU when registers and LDS allow it.
-  const bool mfma = p.variant == 7 && !p.node_out && !p.rounds_out;
-  const uint64_t per_wave = p.variant == 6 ? 64u : (mfma ? 32u : 1u);   // trials a wave runs at once
+  uint64_t grid = (uint64_t)cus * per_cu;
+  const uint64_t need = (groups + kWavesPerBlock - 1u) / kWavesPerBlock;
+  if (need < grid) grid = need;
+  return at_least_one(grid);
+}
+
+// Cooperative big-network form: one 32-trial group per workgroup at a time
+static int mfma_coop_grid(const KParams &p, int cus) {
+  const uint64_t groups = (p.trial_count + 31u) / 32u;
+  uint64_t grid = (uint64_t)cus * (uint64_t)mfma_coop_blocks_per_cu(p);
+  if (groups < grid) grid = groups;
+  return at_least_one(grid);
+}
+
+// Every other kernel: 32 waves per CU when registers and LDS allow it.
+static int wave_slot_grid(const KParams &p, int cus) {
+  const bool mfma = mfma_batch(p);
+  const uint64_t per_wave = p.variant == kVarLane ? 64u : (mfma ? 32u : 1u);   // trials a wave runs at once
   const uint64_t waves_needed = (p.trial_count + per_wave - 1u) / per_wave;
   const uint32_t bw = block_waves(p);
   const uint64_t blocks_needed = (waves_needed + bw - 1) / bw;
   uint64_t per_cu = 32u / bw;
   // the matrix-core kernel uses no wave slices (its big-network form: proposal planes)
-  const uint32_t lds = mfma ? (p.W > 16u ? mfma_big_lds_bytes(p, bw) : p.hist_bytes) : p.lds_bytes;
+  const uint32_t lds = mfma ? (mfma_big_batch(p) ? mfma_big_lds_bytes(p, bw) : p.hist_bytes) : p.lds_bytes;
   if (lds > 0) {
     const uint64_t lds_fit = lds_groups_per_cu(lds);
     if (lds_fit < per_cu) per_cu = lds_fit ? lds_fit : 1;
   }
-  if (variant_count_level(p.variant)) {   // the count-level kernels are register-bound (benor_tally.hip: per unroll)
-    const uint64_t fit = (uint64_t)count_level_blocks_per_cu(p);
+  if (const CountLevelKernel *k = count_level_kernel(p.variant)) {   // the count-level kernels are register-bound
+    const uint64_t fit = (uint64_t)k->blocks_per_cu(p);               // (benor_tally.hip: per unroll; 0 = unknown)
     if (fit >= 1u && fit < per_cu) per_cu = fit;
   }
   // Lane kernel: a short launch spread over every wave slot (~2 trials per
@@ -999,8 +978,8 @@ int lockstep_grid(const KParams &p, int device) {
   // 10^6 trials 41-57 us at 8 per CU, 22.5 us at 2; N=64 F=21 (KIND 2) 28.9 ->
   // 18.6 us; N=10 F=5 (KIND 1, k_max rounds per trial) keeps 8; at 10^7
   // trials 8 per CU stays best).
-  if (p.variant == 6) {
-    const uint64_t rounds = p.G == 1u ? (p.m <= p.F ? p.k_max : 2u) : 1u;   // per trial, roughly
+  if (p.variant == kVarLane) {
+    const uint64_t rounds = p.G == 1u ? (p.m <= p.F ? p.k_max : 2u) : 1u;   // per trial, roughly (G: the lane kernel's KIND)
     const uint64_t want = p.trial_count * rounds / ((uint64_t)cus * 64u * kWavesPerBlock * 8u);
     const uint64_t v = want < 2u ? 2u : want;
     if (v < per_cu) per_cu = v;
@@ -1008,16 +987,25 @@ int lockstep_grid(const KParams &p, int device) {
   // Matrix-core kernel, dynamic form (p.mfma_chunk, benor_mfma_sched.h): the
   // resident workgroups, which claim their groups; the static form keeps 8 per
   // CU, in rounds of the resident ones.
-  const bool mfma_small_w = mfma && p.W <= 16u;
+  const bool mfma_small_w = mfma_small_w_batch(p);
   if (mfma_small_w && p.mfma_chunk) per_cu = mfma_resident_per_cu(p);
   {                                          // tuning knob (tools/lane_grid_sweep.py); matrix-core kernel: 1..16
     const uint64_t v = knob_u32("BENOR_BLOCKS_PER_CU", 0u);
     if (mfma_small_w ? v >= 1u && v <= 16u : v >= 1u && v < per_cu) per_cu = v;
   }
-  uint64_t grid = (uint64_t)cus * per_cu;
-  if (blocks_needed < grid) grid = blocks_needed;
-  if (grid < 1) grid = 1;
-  return (int)grid;
+  const uint64_t grid = (uint64_t)cus * per_cu;
+  return at_least_one(blocks_needed < grid ? blocks_needed : grid);
+}
+
+int lockstep_grid(const KParams &plan, int device) {
+  const KParams p = launched(plan);
+  int cus = 256;
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+  if (p.variant == kVarEventWave) return event_wave_grid(p);
+  if (p.variant == kVarEventLane) return event_lane_grid(p);
+  if (p.variant == kVarMfmaSmall) return mfma_small_grid(p, cus);
+  if (mfma_big_coop(p)) return mfma_coop_grid(p, cus);
+  return wave_slot_grid(p, cus);
 }
 
 hipError_t launch_popc_peak(uint32_t *sink, int grid, int iters, hipStream_t s, double *words) {

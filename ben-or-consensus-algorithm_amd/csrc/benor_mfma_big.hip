@@ -391,7 +391,7 @@ static hipError_t launch_big_nt(const KParams &p, int grid, hipStream_t s) {
 // x1.01; N=2049 F=1024 (W=17, KIND 2) x0.93.  BENOR_BIG_FORM=wave / coop
 // forces one (validation knob: tests run both forms at every W).
 bool mfma_big_coop(const KParams &p) {
-  if (p.variant != 7 || p.W <= 16u || p.node_out || p.rounds_out) return false;
+  if (!mfma_big_batch(p)) return false;
   if (knob_is("BENOR_BIG_FORM", "wave")) return false;
   if (knob_is("BENOR_BIG_FORM", "coop")) return true;
   return p.W >= kCoopMinW;

@@ -1,7 +1,8 @@
 // benor_modes.h -- the one place that knows the delivery modes (BO_MODE_*, include/benor.h)
-// and the count-level kernels' variant numbers (KParams::variant 9..21): which family a mode
-// belongs to, what it is called in an error text, which plan a shared-coin mode becomes
-// without its coin, and which variant runs which rule and coin.  The runtime's validation and
+// and the kernels' variant numbers (KParams::variant 0..21): which family a mode belongs to,
+// what it is called in an error text, which plan a shared-coin mode becomes without its coin,
+// which count-level variant runs which rule and coin, and what a launch of a matrix-core plan
+// is (batch or state launch, small or big W, sure or deferring).  The runtime's validation and
 // planning (benor_runtime.cpp), the geometry and dispatch (benor_kernels.hip) and the launch
 // checks of benor_tally_byz.hip and benor_tally_sched.hip ask this header and nothing else.
 // Plain C++17 over benor.h, no HIP: tests/modes_check.cpp checks it on the host against a list
@@ -34,8 +35,20 @@ struct ModeTraits {
   constexpr bool is(uint32_t flag) const { return (flags & flag) != 0u; }
 };
 
-// KParams::variant of the count-level kernels: BO_KERNEL_*'s numbers (bo_plan_kernel reports the variant).
+// KParams::variant: BO_KERNEL_*'s numbers (bo_plan_kernel reports the variant), and one internal value.
 enum : uint32_t {
+  kVarBlocked = BO_KERNEL_BLOCKED,        // blocked popcount lockstep (W > 32)
+  kVarW = BO_KERNEL_W,                    // W-specialised popcount lockstep (W <= 32)
+  kVarRandom = BO_KERNEL_RANDOM,          // random delivery
+  kVarEventLane = BO_KERNEL_EVENT,        // event level, one lane per trial (N <= 256)
+  kVarEventWave = 5,                      // event level, one wave or workgroup per trial (N > 256, live runs): no
+                                          // BO_KERNEL_* of its own, the runtime reports BO_KERNEL_EVENT
+  kVarLane = BO_KERNEL_LANE,              // lane lockstep (m <= 64)
+  kVarMfma = BO_KERNEL_MFMA,              // matrix-core lockstep, round 1; its base popcount kernel (kVarW or
+                                          // kVarBlocked) serves its state launches and the trials it defers
+  kVarMfmaSmall = BO_KERNEL_MFMA_SMALL,   // packed matrix-core lockstep (2 <= m <= 32); the lane kernel serves
+                                          // its state launches and its short launches
+  // the count-level kernels
   kVarTally = BO_KERNEL_TALLY,
   kVarTally3 = BO_KERNEL_TALLY3,
   kVarCrash = BO_KERNEL_TALLY_CRASH,
@@ -78,6 +91,31 @@ static_assert(modes_in_order(), "kModes is indexed by the mode's value");
 
 // The row of a mode, nullptr for a value that is no mode.
 constexpr const ModeTraits *mode_traits(uint32_t mode) { return mode < kModeCount ? &kModes[mode] : nullptr; }
+
+// ---- The matrix-core kernel's KIND (KParams::G of a kVarMfma plan; benor_mfma.h), as plan_geometry picks it
+enum : uint32_t {
+  kKindSure = 0,      // every vote count odd and m > 2F: every trial halts in round 1, nothing is deferred
+  kKindMajority = 1,  // m > 2F: a trial that ties in round 1 is deferred
+  kKindMinority = 2,  // F < m <= 2F: ... and so is one in which a receiver does not decide
+};
+constexpr uint32_t kMfmaRegMaxW = 16;   // W <= 16: operands in registers (benor_mfma.h); beyond, the big-network form
+
+// What a launch of a kVarMfma plan is.  A state launch (per-node state: the network API) runs the plan's base
+// popcount kernel, a batch launch the matrix cores.  Scalar forms over (variant, KIND, W, state launch), so that
+// the host check reaches them; benor_internal.h has the KParams forms.
+constexpr bool mfma_batch(uint32_t v, uint32_t, uint32_t, bool state) { return v == kVarMfma && !state; }
+constexpr bool mfma_small_w_batch(uint32_t v, uint32_t kind, uint32_t W, bool state) {
+  return mfma_batch(v, kind, W, state) && W <= kMfmaRegMaxW;
+}
+constexpr bool mfma_big_batch(uint32_t v, uint32_t kind, uint32_t W, bool state) {   // benor_mfma_big.hip, _coop.hip
+  return mfma_batch(v, kind, W, state) && W > kMfmaRegMaxW;
+}
+constexpr bool mfma_sure_batch(uint32_t v, uint32_t kind, uint32_t W, bool state) {  // the paired kernel and its forms
+  return mfma_small_w_batch(v, kind, W, state) && kind == kKindSure;
+}
+constexpr bool mfma_defers(uint32_t v, uint32_t kind, uint32_t W, bool state) {      // at every W: the deferral passes
+  return mfma_batch(v, kind, W, state) && kind > kKindSure;
+}
 
 // ---- KParams::variant, the count-level kernels
 constexpr bool variant_count_level(uint32_t v) { return v >= kVarTally && v < kVarCountLevelEnd; }

@@ -150,9 +150,48 @@ struct bo_plan {
   unsigned char *d_tally = nullptr;   // RANDOM_TALLY: u32 row offsets [m + 2] (padded to 8 bytes), u64 thresholds;
                                       // CRASH_TALLY: directory, row offsets, explicit schedule list, thresholds
   int device = 0;
+  bo_plan() = default;
+  bo_plan(const bo_plan &) = delete;
+  bo_plan &operator=(const bo_plan &) = delete;
+  // (run_states_lockstep's plan on the stack views a scratch buffer: its d_* are null, and a state launch never
+  // defers, so d_defer stays null too)
+  ~bo_plan() {
+    for (void *d : {(void *)d_live, (void *)d_init, (void *)d_init_x, (void *)d_crash, (void *)d_scratch, (void *)d_defer,
+                    (void *)d_flag, (void *)d_claim, (void *)d_stops, (void *)d_tally})
+      if (d) (void)hipFree(d);
+  }
 };
 
 namespace {
+// A device buffer of `count` T, freed at the end of its scope.
+template <typename T>
+struct DeviceBuf {
+  T *d = nullptr;
+  DeviceBuf() = default;
+  DeviceBuf(const DeviceBuf &) = delete;
+  DeviceBuf &operator=(const DeviceBuf &) = delete;
+  ~DeviceBuf() { if (d) (void)hipFree(d); }
+  hipError_t alloc(size_t count) { return hipMalloc(&d, sizeof(T) * count); }
+};
+
+// The peak probes' clock: one warm-up launch, then `iters` launches between two events on the null stream.
+template <typename Launch>
+float timed_launches_ms(uint32_t iters, Launch launch) {
+  hipEvent_t a, b;
+  (void)hipEventCreate(&a);
+  (void)hipEventCreate(&b);
+  launch();
+  (void)hipEventRecord(a, nullptr);
+  for (uint32_t i = 0; i < iters; ++i) launch();
+  (void)hipEventRecord(b, nullptr);
+  (void)hipEventSynchronize(b);
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, a, b);
+  (void)hipEventDestroy(a);
+  (void)hipEventDestroy(b);
+  return ms;
+}
+
 // The resources of one single-trial event-level run, kept for the next one
 // (r05: the default startConsensus is a live run, and a network of the
 // reference's size spent 0.8 ms of its 0.83 ms creating a stream, pinning a
@@ -1002,7 +1041,7 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
   // batch plan under BENOR_EVENT_FORM=wg gets there (a live run and a network start carry no crash_count, and
   // without the knob such a plan runs the wave-per-trial kernel, whose keys are in global memory): refused here,
   // not rerouted, since the knob exists to put a plan on this kernel.
-  if (kp.variant == 5u && kp.ev_wg && !benor::event_wg_lds_fits(kp))
+  if (kp.variant == benor::kVarEventWave && kp.ev_wg && !benor::event_wg_lds_fits(kp))
     return fail(BO_ERR_UNSUPPORTED,
                 "event level on the workgroup-batched kernel (BENOR_EVENT_FORM=wg): " + std::to_string(kp.lds_bytes) +
                     " bytes of LDS exceed the device's " + std::to_string(benor::kEventWgLdsLimit) +
@@ -1012,10 +1051,10 @@ static int plan_host(const bo_trials_cfg *cfg, std::vector<uint32_t> &live, std:
 }
 
 // BO_KERNEL_* of a plan: its variant, except the wave-per-trial event kernel
-// (variant 5: N > 256 or a live run), which is the event-level family too.
+// (kVarEventWave: N > 256 or a live run), which is the event-level family too.
 static int kernel_family(const benor::KParams &kp) {
   if (kp.m == 0) return BO_KERNEL_NONE;
-  return kp.variant == 5u ? BO_KERNEL_EVENT : (int)kp.variant;
+  return kp.variant == benor::kVarEventWave ? BO_KERNEL_EVENT : (int)kp.variant;
 }
 
 int bo_kernel_for(const bo_trials_cfg *cfg, int *kernel_out) {
@@ -1065,6 +1104,147 @@ static int check_rule_base(const bo_trials_cfg *cfg, const bo_rule *rule) {
   return rule_check(rule);
 }
 
+// ---- What plan_create_impl uploads besides the live map and the init plane, family by family.  Each allocates
+// into the plan's d_* members, which the plan's destructor frees whatever happens after, and points pl->kp there.
+
+// Event level: the initial values, the /stop schedule, the scratch of as many trials as run at once.
+static int upload_event(bo_plan *pl, const bo_trials_cfg *cfg, bool live_run) {
+  benor::KParams &kp = pl->kp;
+  std::vector<int8_t> ix(cfg->N, 0);
+  if (cfg->init_mode == BO_INIT_FIXED)
+    for (uint32_t i = 0; i < cfg->N; ++i) ix[i] = cfg->init[i];
+  int cus = 256;
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pl->device);
+  const uint64_t slot = (uint64_t)kp.ev_stride * 4u;   // scratch bytes of a trial
+  const bool wave = kp.variant == benor::kVarEventWave;
+  std::vector<uint64_t> stops;
+  if (wave) {
+    // one wave per trial, each with a pool of ev_cap messages: as many
+    // concurrent trials as CUs, within ~4 GiB of pools
+    if (cfg->crash_at)
+      for (uint32_t i = 0; i < cfg->N; ++i)
+        if (cfg->crash_at[i] != 0xFFFFFFFFu) stops.push_back(((uint64_t)cfg->crash_at[i] << 12) | i);
+    std::sort(stops.begin(), stops.end());
+    kp.ev_lanes = std::max<uint64_t>(1u, std::min<uint64_t>((uint64_t)cus, (4ull << 30) / slot));
+    if (live_run) kp.ev_lanes = 1u;                // a live run is one trial
+  } else {
+    // scratch: one slice per lane, at most ~4 GiB
+    // Lanes per CU: the mode is bound by the latency of per-lane scratch
+    // accesses, so fewer lanes whose slices stay cache-resident beat full
+    // occupancy: 512 per CU for slices up to 4 KiB (N <= 12), else 256
+    // (tools/ev_sweep.sh, BENOR_EVENT_LANES_PER_CU overrides).
+    uint64_t per_cu = benor::knob_u32("BENOR_EVENT_LANES_PER_CU", slot <= 4096u ? 512u : 256u);
+    if (per_cu < 256u) per_cu = 256u;
+    uint64_t lanes = (uint64_t)cus * per_cu;
+    const uint64_t fit = (4ull << 30) / slot;
+    if (fit < lanes) lanes = fit;
+    lanes = lanes / 256u * 256u;
+    if (lanes < 256u) lanes = 256u;
+    kp.ev_lanes = lanes;
+  }
+  hipError_t e = hipMalloc(&pl->d_init_x, cfg->N);
+  if (e == hipSuccess) e = hipMemcpy(pl->d_init_x, ix.data(), cfg->N, hipMemcpyHostToDevice);
+  if (e == hipSuccess && !stops.empty()) {         // one wave per trial: the sorted /stop schedule
+    e = hipMalloc(&pl->d_stops, sizeof(uint64_t) * stops.size());
+    if (e == hipSuccess)
+      e = hipMemcpy(pl->d_stops, stops.data(), sizeof(uint64_t) * stops.size(), hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess && !wave && cfg->crash_at) {   // one lane per trial: crash_at as it is
+    e = hipMalloc(&pl->d_crash, sizeof(uint32_t) * cfg->N);
+    if (e == hipSuccess) e = hipMemcpy(pl->d_crash, cfg->crash_at, sizeof(uint32_t) * cfg->N, hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess) e = hipMalloc(&pl->d_scratch, kp.ev_lanes * slot);
+  if (e != hipSuccess) return hip_fail(e, "event-mode scratch");
+  kp.init_x = pl->d_init_x;
+  kp.ev_stops = pl->d_stops;
+  kp.ev_nstops = (uint32_t)stops.size();
+  kp.crash_at = pl->d_crash;
+  kp.scratch = pl->d_scratch;
+  return BO_OK;
+}
+
+// The count-level plans of one table: the two- and three-valued modes, the Byzantine family with its additions,
+// and the adversarial scheduler, which has the honest plane and no table.
+static int upload_count_level(bo_plan *pl, const PlanTables &tables) {
+  benor::KParams &kp = pl->kp;
+  const uint32_t m = kp.m;
+  if (benor::variant_sched(kp.variant)) {
+    // An adversarial scheduler: the honest plane alone -- the scheduler's counts are a closed form
+    TableUpload up;
+    const size_t o_plane = up.add(tables.honest.data(), sizeof(uint64_t) * tables.honest.size());
+    const hipError_t e = up.upload(&pl->d_tally);
+    if (e != hipSuccess) return hip_fail(e, "honest plane upload");
+    kp.byz_plane = reinterpret_cast<const unsigned long long *>(pl->d_tally + o_plane);
+    return BO_OK;
+  }
+  // The two- and three-valued modes and the Byzantine family: the whole table HG(m, K, q), K = 0..m: at most
+  // ~3.7 * 10^6 thresholds (30 MB) at m = 4096
+  std::vector<uint32_t> off(m + 2u, 0u);
+  std::vector<uint64_t> thr;
+  std::vector<double> w;
+  for (uint32_t K = 0; K <= m; ++K) {
+    off[K] = (uint32_t)thr.size();
+    (void)tally_row(m, kp.q, K, thr, w);
+  }
+  off[m + 1u] = (uint32_t)thr.size();
+  // ... and, with Byzantine senders, the Binomial thresholds and the honest plane behind it
+  const bool byz = benor::variant_byz(kp.variant);
+  std::vector<uint64_t> lie;
+  if (byz && !benor::byz_heard(kp)) byz_row(kp.byz_n, kp.byz_one, lie);   // (BALANCE, SPLIT, b = 0: no thresholds)
+  TableUpload up;
+  const size_t o_off = up.add(off.data(), sizeof(uint32_t) * off.size());
+  const size_t o_thr = up.add(thr.data(), sizeof(uint64_t) * thr.size(), sizeof(uint64_t));
+  const size_t o_lie = up.add(lie.data(), sizeof(uint64_t) * lie.size());
+  const size_t o_plane = up.add(tables.honest.data(), byz ? sizeof(uint64_t) * tables.honest.size() : 0u);
+  const hipError_t e = up.upload(&pl->d_tally);
+  if (e != hipSuccess) return hip_fail(e, "tally table upload");
+  kp.tally_off = reinterpret_cast<const uint32_t *>(pl->d_tally + o_off);
+  kp.tally_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + o_thr);
+  if (byz) {
+    if (!lie.empty()) kp.byz_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + o_lie);
+    kp.byz_plane = reinterpret_cast<const unsigned long long *>(pl->d_tally + o_plane);
+  }
+  return BO_OK;
+}
+
+// The crash family: one table per reachable live count (pool size), and their directory
+static int upload_crash(bo_plan *pl, const PlanTables &tables) {
+  benor::KParams &kp = pl->kp;
+  const CrashSchedule &crash = tables.crash;
+  std::vector<benor::CrashDir> dir(kp.cr_n + 1u);
+  std::vector<uint32_t> off;
+  std::vector<uint64_t> thr;
+  std::vector<double> w;
+  for (uint32_t d = 0; d <= kp.cr_n; ++d) {
+    if (!crash.reach[d]) {       // never read: the entry of the next larger live count (d = 0 is reachable)
+      dir[d] = dir[d - 1u];
+      continue;
+    }
+    const uint32_t md = kp.m - d;
+    dir[d].thr_base = thr.size();
+    dir[d].off_base = (uint32_t)off.size();
+    dir[d].pad = 0u;
+    const size_t base = thr.size();
+    for (uint32_t K = 0; K <= md; ++K) {
+      off.push_back((uint32_t)(thr.size() - base));
+      (void)tally_row(md, kp.q, K, thr, w);
+    }
+    off.push_back((uint32_t)(thr.size() - base));   // the md + 2nd offset: the last row's end
+  }
+  TableUpload up;
+  const size_t o_dir = up.add(dir.data(), sizeof(benor::CrashDir) * dir.size());
+  const size_t o_off = up.add(off.data(), sizeof(uint32_t) * off.size());
+  const size_t o_list = up.add(crash.list.data(), sizeof(uint32_t) * crash.list.size());
+  const size_t o_thr = up.add(thr.data(), sizeof(uint64_t) * thr.size(), sizeof(uint64_t));
+  const hipError_t e = up.upload(&pl->d_tally);
+  if (e != hipSuccess) return hip_fail(e, "crash tally table upload");
+  kp.cr_dir = reinterpret_cast<const benor::CrashDir *>(pl->d_tally + o_dir);
+  kp.tally_off = reinterpret_cast<const uint32_t *>(pl->d_tally + o_off);
+  kp.cr_list = crash.list.empty() ? nullptr : reinterpret_cast<const uint32_t *>(pl->d_tally + o_list);
+  kp.tally_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + o_thr);
+  return BO_OK;
+}
+
 // `rule`: NULL, or the threshold rule that replaces the plan's own (checked by check_rule_base).
 static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_run, const bo_rule *rule = nullptr) {
   if (!cfg || !out) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
@@ -1080,7 +1260,7 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
   rc = check_device(&dev);
   if (rc) return rc;
 
-  auto *pl = new bo_plan();
+  auto pl = std::make_unique<bo_plan>();            // an error return below frees what was allocated so far
   pl->cfg = *cfg;
   pl->cfg.faulty = nullptr;
   pl->cfg.init = nullptr;
@@ -1090,149 +1270,31 @@ static int plan_create_impl(const bo_trials_cfg *cfg, bo_plan **out, bool live_r
   pl->kp = kp0;
   benor::KParams &kp = pl->kp;
   const uint32_t m = kp.m;
-  {
-    hipError_t e = hipMalloc(&pl->d_flag, sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(pl->d_flag, 0, sizeof(uint32_t));
-    if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "plan flag"); }
-  }
-  if (kp.variant == 7 && kp.G == 0u && kp.W <= 16u) {
+  hipError_t e = hipMalloc(&pl->d_flag, sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMemset(pl->d_flag, 0, sizeof(uint32_t));
+  if (e != hipSuccess) return hip_fail(e, "plan flag");
+  if (benor::mfma_sure_batch(kp.variant, kp.G, kp.W, false)) {   // (the plan-level form: a plan has no node_out)
     // benor.h orders a plan's launches on one stream, and every launch leaves
     // the words 0 (benor_mfma_sched.h): one pair per plan, zeroed once
-    hipError_t e = hipMalloc(&pl->d_claim, sizeof(uint32_t) * benor::sched::kWords);
+    e = hipMalloc(&pl->d_claim, sizeof(uint32_t) * benor::sched::kWords);
     if (e == hipSuccess) e = hipMemset(pl->d_claim, 0, sizeof(uint32_t) * benor::sched::kWords);
-    if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "plan claim words"); }
+    if (e != hipSuccess) return hip_fail(e, "plan claim words");
     kp.mfma_claim = pl->d_claim;
   }
   if (m > 0) {
-    hipError_t e = hipMalloc(&pl->d_live, sizeof(uint32_t) * m);
+    e = hipMalloc(&pl->d_live, sizeof(uint32_t) * m);
     if (e == hipSuccess) e = hipMalloc(&pl->d_init, sizeof(uint4) * kp.W);
     if (e == hipSuccess) e = hipMemcpy(pl->d_live, pl->live_ids.data(), sizeof(uint32_t) * m, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(pl->d_init, plane.data(), sizeof(uint4) * kp.W, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "plan upload"); }
+    if (e != hipSuccess) return hip_fail(e, "plan upload");
     kp.live_ids = pl->d_live;
     kp.init_plane = pl->d_init;
-    if (cfg->mode == BO_MODE_EVENT) {
-      std::vector<int8_t> ix(cfg->N, 0);
-      if (cfg->init_mode == BO_INIT_FIXED)
-        for (uint32_t i = 0; i < cfg->N; ++i) ix[i] = cfg->init[i];
-      int cus = 256;
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-      const uint64_t slot = (uint64_t)kp.ev_stride * 4u;   // scratch bytes of a trial
-      std::vector<uint64_t> stops;
-      if (kp.variant == 5) {
-        // one wave per trial, each with a pool of ev_cap messages: as many
-        // concurrent trials as CUs, within ~4 GiB of pools
-        if (cfg->crash_at)
-          for (uint32_t i = 0; i < cfg->N; ++i)
-            if (cfg->crash_at[i] != 0xFFFFFFFFu) stops.push_back(((uint64_t)cfg->crash_at[i] << 12) | i);
-        std::sort(stops.begin(), stops.end());
-        kp.ev_lanes = std::max<uint64_t>(1u, std::min<uint64_t>((uint64_t)cus, (4ull << 30) / slot));
-        if (live_run) kp.ev_lanes = 1u;                // a live run is one trial
-      } else {
-        // scratch: one slice per lane, at most ~4 GiB
-        // Lanes per CU: the mode is bound by the latency of per-lane scratch
-        // accesses, so fewer lanes whose slices stay cache-resident beat full
-        // occupancy: 512 per CU for slices up to 4 KiB (N <= 12), else 256
-        // (tools/ev_sweep.sh, BENOR_EVENT_LANES_PER_CU overrides).
-        uint64_t per_cu = benor::knob_u32("BENOR_EVENT_LANES_PER_CU", slot <= 4096u ? 512u : 256u);
-        if (per_cu < 256u) per_cu = 256u;
-        uint64_t lanes = (uint64_t)cus * per_cu;
-        const uint64_t fit = (4ull << 30) / slot;
-        if (fit < lanes) lanes = fit;
-        lanes = lanes / 256u * 256u;
-        if (lanes < 256u) lanes = 256u;
-        kp.ev_lanes = lanes;
-      }
-      e = hipMalloc(&pl->d_init_x, cfg->N);
-      if (e == hipSuccess) e = hipMemcpy(pl->d_init_x, ix.data(), cfg->N, hipMemcpyHostToDevice);
-      if (e == hipSuccess && !stops.empty()) {         // one wave per trial: the sorted /stop schedule
-        e = hipMalloc(&pl->d_stops, sizeof(uint64_t) * stops.size());
-        if (e == hipSuccess)
-          e = hipMemcpy(pl->d_stops, stops.data(), sizeof(uint64_t) * stops.size(), hipMemcpyHostToDevice);
-      }
-      if (e == hipSuccess && kp.variant != 5 && cfg->crash_at) {   // one lane per trial: crash_at as it is
-        e = hipMalloc(&pl->d_crash, sizeof(uint32_t) * cfg->N);
-        if (e == hipSuccess) e = hipMemcpy(pl->d_crash, cfg->crash_at, sizeof(uint32_t) * cfg->N, hipMemcpyHostToDevice);
-      }
-      if (e == hipSuccess) e = hipMalloc(&pl->d_scratch, kp.ev_lanes * slot);
-      if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "event-mode scratch"); }
-      kp.init_x = pl->d_init_x;
-      kp.ev_stops = pl->d_stops;
-      kp.ev_nstops = (uint32_t)stops.size();
-      kp.crash_at = pl->d_crash;
-      kp.scratch = pl->d_scratch;
-    } else if (benor::variant_sched(kp.variant)) {
-      // An adversarial scheduler: the honest plane alone -- the scheduler's counts are a closed form
-      TableUpload up;
-      const size_t o_plane = up.add(tables.honest.data(), sizeof(uint64_t) * tables.honest.size());
-      e = up.upload(&pl->d_tally);
-      if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "honest plane upload"); }
-      kp.byz_plane = reinterpret_cast<const unsigned long long *>(pl->d_tally + o_plane);
-    } else if (benor::variant_count_level(kp.variant) && !benor::variant_crash(kp.variant)) {
-      // The two- and three-valued modes and the Byzantine family: the whole table HG(m, K, q), K = 0..m: at most
-      // ~3.7 * 10^6 thresholds (30 MB) at m = 4096
-      std::vector<uint32_t> off(m + 2u, 0u);
-      std::vector<uint64_t> thr;
-      std::vector<double> w;
-      for (uint32_t K = 0; K <= m; ++K) {
-        off[K] = (uint32_t)thr.size();
-        (void)tally_row(m, kp.q, K, thr, w);
-      }
-      off[m + 1u] = (uint32_t)thr.size();
-      // ... and, with Byzantine senders, the Binomial thresholds and the honest plane behind it
-      const bool byz = benor::variant_byz(kp.variant);
-      std::vector<uint64_t> lie;
-      if (byz && !benor::byz_heard(kp)) byz_row(kp.byz_n, kp.byz_one, lie);   // (BALANCE, SPLIT, b = 0: no thresholds)
-      TableUpload up;
-      const size_t o_off = up.add(off.data(), sizeof(uint32_t) * off.size());
-      const size_t o_thr = up.add(thr.data(), sizeof(uint64_t) * thr.size(), sizeof(uint64_t));
-      const size_t o_lie = up.add(lie.data(), sizeof(uint64_t) * lie.size());
-      const size_t o_plane = up.add(tables.honest.data(), byz ? sizeof(uint64_t) * tables.honest.size() : 0u);
-      e = up.upload(&pl->d_tally);
-      if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "tally table upload"); }
-      kp.tally_off = reinterpret_cast<const uint32_t *>(pl->d_tally + o_off);
-      kp.tally_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + o_thr);
-      if (byz) {
-        if (!lie.empty()) kp.byz_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + o_lie);
-        kp.byz_plane = reinterpret_cast<const unsigned long long *>(pl->d_tally + o_plane);
-      }
-    } else if (benor::variant_crash(kp.variant)) {
-      // The crash family: one table per reachable live count (pool size), and their directory
-      const CrashSchedule &crash = tables.crash;
-      std::vector<benor::CrashDir> dir(kp.cr_n + 1u);
-      std::vector<uint32_t> off;
-      std::vector<uint64_t> thr;
-      std::vector<double> w;
-      for (uint32_t d = 0; d <= kp.cr_n; ++d) {
-        if (!crash.reach[d]) {       // never read: the entry of the next larger live count (d = 0 is reachable)
-          dir[d] = dir[d - 1u];
-          continue;
-        }
-        const uint32_t md = m - d;
-        dir[d].thr_base = thr.size();
-        dir[d].off_base = (uint32_t)off.size();
-        dir[d].pad = 0u;
-        const size_t base = thr.size();
-        for (uint32_t K = 0; K <= md; ++K) {
-          off.push_back((uint32_t)(thr.size() - base));
-          (void)tally_row(md, kp.q, K, thr, w);
-        }
-        off.push_back((uint32_t)(thr.size() - base));   // the md + 2nd offset: the last row's end
-      }
-      TableUpload up;
-      const size_t o_dir = up.add(dir.data(), sizeof(benor::CrashDir) * dir.size());
-      const size_t o_off = up.add(off.data(), sizeof(uint32_t) * off.size());
-      const size_t o_list = up.add(crash.list.data(), sizeof(uint32_t) * crash.list.size());
-      const size_t o_thr = up.add(thr.data(), sizeof(uint64_t) * thr.size(), sizeof(uint64_t));
-      e = up.upload(&pl->d_tally);
-      if (e != hipSuccess) { bo_plan_destroy(pl); return hip_fail(e, "crash tally table upload"); }
-      kp.cr_dir = reinterpret_cast<const benor::CrashDir *>(pl->d_tally + o_dir);
-      kp.tally_off = reinterpret_cast<const uint32_t *>(pl->d_tally + o_off);
-      kp.cr_list = crash.list.empty() ? nullptr : reinterpret_cast<const uint32_t *>(pl->d_tally + o_list);
-      kp.tally_thr = reinterpret_cast<const unsigned long long *>(pl->d_tally + o_thr);
-    }
+    if (cfg->mode == BO_MODE_EVENT) rc = upload_event(pl.get(), cfg, live_run);
+    else if (benor::variant_crash(kp.variant)) rc = upload_crash(pl.get(), tables);
+    else if (benor::variant_count_level(kp.variant)) rc = upload_count_level(pl.get(), tables);
+    if (rc) return rc;
   }
-  *out = pl;
+  *out = pl.release();
   return BO_OK;
 }
 
@@ -1252,20 +1314,7 @@ int bo_plan_rule(const bo_plan *pl, bo_rule *out) {
   return 1;
 }
 
-void bo_plan_destroy(bo_plan *pl) {
-  if (!pl) return;
-  if (pl->d_live) (void)hipFree(pl->d_live);
-  if (pl->d_init) (void)hipFree(pl->d_init);
-  if (pl->d_init_x) (void)hipFree(pl->d_init_x);
-  if (pl->d_crash) (void)hipFree(pl->d_crash);
-  if (pl->d_scratch) (void)hipFree(pl->d_scratch);
-  if (pl->d_defer) (void)hipFree(pl->d_defer);
-  if (pl->d_flag) (void)hipFree(pl->d_flag);
-  if (pl->d_claim) (void)hipFree(pl->d_claim);
-  if (pl->d_stops) (void)hipFree(pl->d_stops);
-  if (pl->d_tally) (void)hipFree(pl->d_tally);
-  delete pl;
-}
+void bo_plan_destroy(bo_plan *pl) { delete pl; }
 
 uint32_t bo_plan_live_nodes(const bo_plan *pl) { return pl ? pl->kp.m : 0u; }
 
@@ -1295,21 +1344,20 @@ uint64_t bo_plan_popc_words_per_node_round(const bo_plan *pl) {
 // (tools/timeline_report.py).  Synchronous; not for timing the launch itself.
 static hipError_t launch_with_timeline(benor::KParams kp, int grid, hipStream_t s, const char *path) {
   const size_t words = (size_t)grid * benor::kWavesPerBlock * benor::kTimelineWords;
-  unsigned long long *d = nullptr;
-  hipError_t e = hipMalloc(&d, words * sizeof(unsigned long long));
+  DeviceBuf<unsigned long long> d;
+  hipError_t e = d.alloc(words);
   if (e != hipSuccess) return e;
-  e = hipMemsetAsync(d, 0, words * sizeof(unsigned long long), s);
-  kp.timeline = d;
+  e = hipMemsetAsync(d.d, 0, words * sizeof(unsigned long long), s);
+  kp.timeline = d.d;
   if (e == hipSuccess) e = benor::launch_lockstep(kp, grid, s);
   std::vector<unsigned long long> h(words);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = hipMemcpy(h.data(), d, words * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-  (void)hipFree(d);
+  if (e == hipSuccess) e = hipMemcpy(h.data(), d.d, words * sizeof(unsigned long long), hipMemcpyDeviceToHost);
   if (e != hipSuccess) return e;
   if (FILE *f = std::fopen(path, "a")) {
     std::fprintf(f, "# launch m=%u trials=%llu grid=%d waves=%d", kp.m, (unsigned long long)kp.trial_count, grid,
                  grid * benor::kWavesPerBlock);
-    if (kp.variant == 7) std::fprintf(f, " kernel=mfma chunk=%u strip=%d", kp.mfma_chunk, benor::mfma_strip_form(kp) ? 1 : 0);
+    if (kp.variant == benor::kVarMfma) std::fprintf(f, " kernel=mfma chunk=%u strip=%d", kp.mfma_chunk, benor::mfma_strip_form(kp) ? 1 : 0);
     std::fprintf(f, "\n");
     for (size_t w = 0; w < (size_t)grid * benor::kWavesPerBlock; ++w) {
       const unsigned long long *t = h.data() + w * benor::kTimelineWords;
@@ -1336,7 +1384,7 @@ static int plan_launch_impl(bo_plan *pl, uint64_t trial_begin, uint64_t trial_co
   kp.overflow = pl->d_flag;
   kp.node_out = node_out;
   kp.rounds_out = rounds_out;
-  if (kp.variant == 7 && kp.G > 0u && !node_out && !rounds_out) {
+  if (benor::mfma_defers(kp)) {
     // Matrix-core round 1 with deferral (benor_mfma.h, KIND > 0): per chunk of
     // at most kDeferChunk trials, the matrix-core launch records the trials
     // that do not halt in round 1, and the W kernel runs exactly those from
@@ -1415,9 +1463,7 @@ static int plan_launch_impl(bo_plan *pl, uint64_t trial_begin, uint64_t trial_co
         HIP_TRY(benor::launch_lockstep(kc, g, s));
         r_last = r;
       }
-      benor::KParams kw = kp;
-      kw.variant = kp.base_variant;              // W kernel (W <= 32) or blocked kernel
-      kw.G = kp.base_G;
+      benor::KParams kw = benor::base_kernel(kp);   // W kernel (W <= 32) or blocked kernel
       kw.defer_list = kw.defer_len = kw.defer_seg = nullptr;
       kw.trial_list = lists[(r_last - 1u) & 1u];
       kw.trial_list_len = lens + 16u * (r_last - 1u);
@@ -1433,8 +1479,8 @@ static int plan_launch_impl(bo_plan *pl, uint64_t trial_begin, uint64_t trial_co
     kp.trial_count = n;
     kp.mfma_chunk = benor::mfma_chunk(kp, pl->device);   // KIND 0 matrix-core launch: static (0) or dynamic
     const int grid = benor::lockstep_grid(kp, pl->device);
-    const bool mfma_sure = kp.variant == 7 && kp.G == 0u && kp.W <= 16u && !node_out && !rounds_out;
-    const char *tl_path = kp.variant == 8 || mfma_sure ? benor::knob("BENOR_TIMELINE") : nullptr;
+    const bool stamps = kp.variant == benor::kVarMfmaSmall || benor::mfma_sure_batch(kp);
+    const char *tl_path = stamps ? benor::knob("BENOR_TIMELINE") : nullptr;
     if (tl_path) {
       HIP_TRY(launch_with_timeline(kp, grid, s, tl_path));
     } else {
@@ -1459,14 +1505,14 @@ int plan_flag_error(uint32_t v);
 int bo_plan_run(bo_plan *pl, uint64_t trial_begin, uint64_t trial_count, uint64_t *hist_host) {
   if (!pl || !hist_host) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
   const uint32_t H = bo_hist_len(pl->cfg.k_max);
-  uint64_t *d = nullptr;
-  HIP_TRY(hipMalloc(&d, sizeof(uint64_t) * H));
-  hipError_t e = hipMemset(d, 0, sizeof(uint64_t) * H);
+  DeviceBuf<uint64_t> d;
+  hipError_t e = d.alloc(H);
+  if (e != hipSuccess) return hip_fail(e, "hipMalloc(&d, sizeof(uint64_t) * H)");
+  e = hipMemset(d.d, 0, sizeof(uint64_t) * H);
   int rc = BO_OK;
-  if (e == hipSuccess) rc = plan_launch_impl(pl, trial_begin, trial_count, d, nullptr, nullptr, nullptr);
+  if (e == hipSuccess) rc = plan_launch_impl(pl, trial_begin, trial_count, d.d, nullptr, nullptr, nullptr);
   std::vector<uint64_t> h(H);
-  if (e == hipSuccess && rc == BO_OK) e = hipMemcpy(h.data(), d, sizeof(uint64_t) * H, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
+  if (e == hipSuccess && rc == BO_OK) e = hipMemcpy(h.data(), d.d, sizeof(uint64_t) * H, hipMemcpyDeviceToHost);
   if (e != hipSuccess) return hip_fail(e, "bo_plan_run");
   if (rc) return rc;
   uint32_t flag = 0;
@@ -1617,29 +1663,26 @@ int run_states_lockstep(const bo_trials_cfg *cfg, uint64_t trial, bo_node_state 
 // One trial's per-node states through a plan of its own; `rule`: NULL, or the threshold rule that replaces the plan's.
 static int run_states_plan(const bo_trials_cfg *cfg, const bo_rule *rule, uint64_t trial, bo_node_state *nodes_out,
                            uint32_t *rounds_out) {
-  bo_plan *pl = nullptr;
-  int rc = plan_create_impl(cfg, &pl, false, rule);
+  bo_plan *created = nullptr;
+  int rc = plan_create_impl(cfg, &created, false, rule);
   if (rc) return rc;
+  const std::unique_ptr<bo_plan> pl(created);
   const uint32_t N = cfg->N, H = bo_hist_len(cfg->k_max);
   std::vector<bo_node_state> st(N);
   initial_states(cfg, st.data());
-  bo_node_state *d_st = nullptr;
-  uint64_t *d_h = nullptr;
-  uint32_t *d_r = nullptr;
-  hipError_t e = hipMalloc(&d_st, sizeof(bo_node_state) * N);
-  if (e == hipSuccess) e = hipMalloc(&d_h, sizeof(uint64_t) * H);
-  if (e == hipSuccess) e = hipMalloc(&d_r, sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMemcpy(d_st, st.data(), sizeof(bo_node_state) * N, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(d_h, 0, sizeof(uint64_t) * H);
-  if (e == hipSuccess) e = hipMemset(d_r, 0, sizeof(uint32_t));
-  if (e == hipSuccess) rc = plan_launch_impl(pl, trial, 1, d_h, d_st, d_r, nullptr);
+  DeviceBuf<bo_node_state> d_st;
+  DeviceBuf<uint64_t> d_h;
+  DeviceBuf<uint32_t> d_r;
+  hipError_t e = d_st.alloc(N);
+  if (e == hipSuccess) e = d_h.alloc(H);
+  if (e == hipSuccess) e = d_r.alloc(1);
+  if (e == hipSuccess) e = hipMemcpy(d_st.d, st.data(), sizeof(bo_node_state) * N, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(d_h.d, 0, sizeof(uint64_t) * H);
+  if (e == hipSuccess) e = hipMemset(d_r.d, 0, sizeof(uint32_t));
+  if (e == hipSuccess) rc = plan_launch_impl(pl.get(), trial, 1, d_h.d, d_st.d, d_r.d, nullptr);
   uint32_t rounds = 0;
-  if (e == hipSuccess && rc == BO_OK) e = hipMemcpy(nodes_out, d_st, sizeof(bo_node_state) * N, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && rc == BO_OK) e = hipMemcpy(&rounds, d_r, sizeof(uint32_t), hipMemcpyDeviceToHost);
-  if (d_st) (void)hipFree(d_st);
-  if (d_h) (void)hipFree(d_h);
-  if (d_r) (void)hipFree(d_r);
-  bo_plan_destroy(pl);
+  if (e == hipSuccess && rc == BO_OK) e = hipMemcpy(nodes_out, d_st.d, sizeof(bo_node_state) * N, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && rc == BO_OK) e = hipMemcpy(&rounds, d_r.d, sizeof(uint32_t), hipMemcpyDeviceToHost);
   if (e != hipSuccess) return hip_fail(e, "bo_run_trial_states");
   if (rc) return rc;
   if (rounds & 0x80000000u) return fail(BO_ERR_INTERNAL, "event-level message pool filled up: the run stopped early");
@@ -2035,23 +2078,12 @@ double bo_popc_peak(uint32_t iters) {
   int dev = 0, cus = 256;
   (void)hipGetDevice(&dev);
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  uint32_t *sink = nullptr;
-  if (hipMalloc(&sink, sizeof(uint32_t) * cus * 8) != hipSuccess) return 0.0;
+  DeviceBuf<uint32_t> sink_buf;
+  if (sink_buf.alloc((size_t)cus * 8u) != hipSuccess) return 0.0;
+  uint32_t *const sink = sink_buf.d;
   const int grid = cus * 8, inner = 2048;
   double words = 0;
-  hipEvent_t a, b;
-  (void)hipEventCreate(&a);
-  (void)hipEventCreate(&b);
-  (void)benor::launch_popc_peak(sink, grid, inner, nullptr, &words);   // warm-up
-  (void)hipEventRecord(a, nullptr);
-  for (uint32_t i = 0; i < iters; ++i) (void)benor::launch_popc_peak(sink, grid, inner, nullptr, &words);
-  (void)hipEventRecord(b, nullptr);
-  (void)hipEventSynchronize(b);
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, a, b);
-  (void)hipEventDestroy(a);
-  (void)hipEventDestroy(b);
-  (void)hipFree(sink);
+  const float ms = timed_launches_ms(iters, [&] { (void)benor::launch_popc_peak(sink, grid, inner, nullptr, &words); });
   if (ms <= 0) return 0.0;
   return words * iters / (ms * 1e-3);
 }
@@ -2061,23 +2093,12 @@ double bo_mfma_peak(uint32_t iters) {
   int dev = 0, cus = 256;
   (void)hipGetDevice(&dev);
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  float *sink = nullptr;
   const int grid = cus * 2, inner = 4096;   // 2 waves per SIMD
-  if (hipMalloc(&sink, sizeof(float) * grid) != hipSuccess) return 0.0;
+  DeviceBuf<float> sink_buf;
+  if (sink_buf.alloc((size_t)grid) != hipSuccess) return 0.0;
+  float *const sink = sink_buf.d;
   double terms = 0;
-  hipEvent_t a, b;
-  (void)hipEventCreate(&a);
-  (void)hipEventCreate(&b);
-  (void)benor::launch_mfma_peak(sink, grid, inner, nullptr, &terms);   // warm-up
-  (void)hipEventRecord(a, nullptr);
-  for (uint32_t i = 0; i < iters; ++i) (void)benor::launch_mfma_peak(sink, grid, inner, nullptr, &terms);
-  (void)hipEventRecord(b, nullptr);
-  (void)hipEventSynchronize(b);
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, a, b);
-  (void)hipEventDestroy(a);
-  (void)hipEventDestroy(b);
-  (void)hipFree(sink);
+  const float ms = timed_launches_ms(iters, [&] { (void)benor::launch_mfma_peak(sink, grid, inner, nullptr, &terms); });
   if (ms <= 0) return 0.0;
   return terms * iters / (ms * 1e-3);
 }

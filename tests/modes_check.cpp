@@ -1,7 +1,9 @@
 // Host check of csrc/benor_modes.h (tests/test_modes.py builds it with
 // -fsanitize=address,undefined and runs it): the modes table against a list
 // written out here by hand, the variant predicates against the BO_KERNEL_*
-// comments of include/benor.h, and the Byzantine and scheduler variant functions.
+// comments of include/benor.h, the names of the variants 0..8, the matrix-core
+// launch predicates over their whole grid, and the Byzantine and scheduler
+// variant functions.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -90,6 +92,39 @@ void check_variants() {
              kVarByz == 14u && kVarSched == 18u && kVarCountLevelEnd == 22u, "variant names", 0u);
 }
 
+// The lockstep, random-delivery and event-level variants: BO_KERNEL_*'s numbers (include/benor.h) and 5, the
+// wave-per-trial event kernel, which has no BO_KERNEL_* of its own; none of them is a count-level variant.
+void check_variant_names() {
+  using namespace benor;
+  expect(kVarBlocked == 0u && BO_KERNEL_BLOCKED == 0, "kVarBlocked", kVarBlocked);
+  expect(kVarW == 1u && BO_KERNEL_W == 1, "kVarW", kVarW);
+  expect(kVarRandom == 2u && BO_KERNEL_RANDOM == 2, "kVarRandom", kVarRandom);
+  expect(kVarEventLane == 4u && BO_KERNEL_EVENT == 4, "kVarEventLane", kVarEventLane);
+  expect(kVarEventWave == 5u, "kVarEventWave", kVarEventWave);
+  expect(kVarLane == 6u && BO_KERNEL_LANE == 6, "kVarLane", kVarLane);
+  expect(kVarMfma == 7u && BO_KERNEL_MFMA == 7, "kVarMfma", kVarMfma);
+  expect(kVarMfmaSmall == 8u && BO_KERNEL_MFMA_SMALL == 8, "kVarMfmaSmall", kVarMfmaSmall);
+  for (uint32_t v = 0; v <= 8u; ++v) expect(!variant_count_level(v), "a lockstep variant counted as count-level", v);
+  expect(kKindSure == 0u && kKindMajority == 1u && kKindMinority == 2u, "matrix-core KIND names", 0u);
+}
+
+// What a launch of a matrix-core plan is, against the conditions as the host code spelt them before the
+// predicates existed: variant 7 with no node_out and no rounds_out, then W <= 16 or W > 16, G == 0 or G > 0.
+void check_launch_predicates() {
+  using namespace benor;
+  for (uint32_t v = 0; v <= 21u; ++v)
+    for (uint32_t kind = 0; kind <= 2u; ++kind)
+      for (uint32_t W : {1u, 2u, 16u, 17u, 64u})
+        for (bool state : {false, true}) {
+          const uint32_t id = v << 16 | kind << 8 | W;
+          expect(mfma_batch(v, kind, W, state) == (v == 7u && !state), "mfma_batch", id, state);
+          expect(mfma_small_w_batch(v, kind, W, state) == (v == 7u && !state && W <= 16u), "mfma_small_w_batch", id, state);
+          expect(mfma_big_batch(v, kind, W, state) == (v == 7u && W > 16u && !state), "mfma_big_batch", id, state);
+          expect(mfma_sure_batch(v, kind, W, state) == !(v != 7u || kind != 0u || W > 16u || state), "mfma_sure_batch", id, state);
+          expect(mfma_defers(v, kind, W, state) == (v == 7u && kind > 0u && !state), "mfma_defers", id, state);
+        }
+}
+
 void check_variant_functions() {
   using namespace benor;
   expect(byz_variant(BO_MODE_BYZ_TALLY) == BO_KERNEL_TALLY_BYZ, "byz_variant", BO_MODE_BYZ_TALLY);
@@ -117,6 +152,8 @@ void check_variant_functions() {
 int main() {
   check_modes();
   check_variants();
+  check_variant_names();
+  check_launch_predicates();
   check_variant_functions();
   std::printf("%lu checks, %lu failures\n", checks, failures);
   return failures ? 1 : 0;

@@ -21,5 +21,8 @@ def test_modes_on_the_host(tmp_path):
                     os.path.join(ROOT, "tests", "modes_check.cpp"), "-o", str(exe)], check=True)
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
-    # 14 modes x 10 facts and 6 values that are no mode, 40 variants x 7, the variant functions
-    assert int(r.stdout.split()[0]) >= 14 * 10 + 6 + 40 * 7 + 8 and " 0 failures" in r.stdout, r.stdout
+    # 14 modes x 10 facts and 6 values that are no mode, 40 variants x 7, the variant functions; the eight names of
+    # the variants 0..8, nine variants that are not count-level and the KIND names; five launch predicates over
+    # 22 variants x 3 KINDs x 5 widths x batch and state launch
+    want = 14 * 10 + 6 + 40 * 7 + 8 + (8 + 9 + 1) + 5 * 22 * 3 * 5 * 2
+    assert int(r.stdout.split()[0]) >= want and " 0 failures" in r.stdout, r.stdout
