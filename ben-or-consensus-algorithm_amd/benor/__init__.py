@@ -151,6 +151,7 @@ EXPORTED_SYMBOLS = (
     "bo_lumped_check", "bo_lumped_run", "bo_lumped_trial", "bo_binom_half_cdf",
     "bo_rule_protocol_a", "bo_rule_protocol_b", "bo_plan_create_rule", "bo_run_trial_states_rule", "bo_plan_rule",
     "bo_lumped_check_rule", "bo_lumped_run_rule", "bo_lumped_trial_rule",
+    "bo_plan_delivery_masks",
 )
 
 
@@ -319,6 +320,8 @@ def lib() -> ctypes.CDLL:
     L.bo_lumped_check_rule.argtypes = [P(LumpedCfgC), P(Rule)]
     L.bo_lumped_run_rule.argtypes = [P(LumpedCfgC), P(Rule), ctypes.c_uint64, ctypes.c_uint64, P(ctypes.c_uint64)]
     L.bo_lumped_trial_rule.argtypes = [P(LumpedCfgC), P(Rule), ctypes.c_uint64, P(LumpedStateC)]
+    L.bo_plan_delivery_masks.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                         P(ctypes.c_uint64)]
     L.bo_last_error.restype = ctypes.c_char_p
     L.bo_abi_version.restype = ctypes.c_int
     L.bo_kernel_version.restype = ctypes.c_char_p
@@ -761,6 +764,18 @@ class TrialsPlan:
         _check(lib().bo_plan_run(self._h, trial_begin, trial_count,
                                  h.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
         return h
+
+    def delivery_masks(self, trial: int, round: int, phase: int):
+        """The delivered-sender masks the plan's random-delivery kernel draws in one phase of one trial
+        (bo_plan_delivery_masks; tests and diagnosis): an [m, ceil(m / 64)] uint64 array, row c the mask of the
+        receiver with compact live index c over compact sender indices."""
+        import numpy as np
+
+        m = self.live_nodes
+        out = np.zeros((m, (m + 63) // 64), dtype=np.uint64)
+        _check(lib().bo_plan_delivery_masks(self._h, trial, round, phase,
+                                            out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        return out
 
 
 def run_trial_states(N: int, F: int, faulty: Sequence[bool], *, seed: int = 0, trial: int = 0,

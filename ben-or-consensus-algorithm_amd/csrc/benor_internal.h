@@ -256,6 +256,12 @@ hipError_t launch_lockstep(const KParams &p, int grid_blocks, hipStream_t stream
 // Random delivery, Bernoulli + fix-up sampler (benor_random.hip, r04).
 uint32_t random_bern_rows(uint32_t m, uint32_t b);
 hipError_t launch_random_bern(const KParams &p, int grid_blocks, hipStream_t stream);
+// One phase's delivered-sender masks of trial p.trial_begin, out[m][W] (bo_plan_delivery_masks): the read-out
+// kernels around random_tally (benor_kernels.hip) and bern_tally<NW, B> (benor_random.hip).
+hipError_t launch_delivery_masks(const KParams &p, uint32_t round, uint32_t phase, unsigned long long *out,
+                                 hipStream_t stream);
+hipError_t launch_random_bern_masks(const KParams &p, uint32_t round, uint32_t phase, unsigned long long *out,
+                                    hipStream_t stream);
 
 // The count-level kernels (their per-wave LDS sizes: benor_tally_common.h).
 // *_blocks_per_cu: resident workgroups per CU (registers, LDS); 0 = unknown.

@@ -265,6 +265,43 @@ __global__ void __launch_bounds__(256) benor_random_kernel(KParams p) {
   flush_hist(lhist, p);
 }
 
+// Read-out of one phase's masks for tests and diagnosis (bo_plan_delivery_masks; on no hot path).  random_tally
+// clears the bitset while it tallies, so the mask is read through its counts: over a plane whose only vote is
+// sender s's 1, c1 is bit s of the receiver's mask.  Wave (j, y) -- receiver group j, blockIdx.y = y -- runs
+// random_tally once per sender of word y for trial p.trial_begin, in the trial kernel's own LDS layout, and
+// writes out[c][y].
+__global__ void __launch_bounds__(256) benor_random_masks_kernel(KParams p, uint32_t round, uint32_t phase,
+                                                                 unsigned long long *__restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wv = threadIdx.x >> 6;
+  const uint32_t m = p.m, W = p.W, q = p.q;
+  const uint32_t j = blockIdx.x * kWavesPerBlock + wv, y = blockIdx.y;
+  if (j >= W) return;
+
+  uint4 *X = reinterpret_cast<uint4 *>(smem + p.hist_bytes + wv * p.wave_bytes);   // [W]: the one-hot plane
+  uint32_t *B = reinterpret_cast<uint32_t *>(X + 2u * W);                           // [2W][64] bitset
+  for (uint32_t w = lane; w < W; w += 64u) X[w] = make_uint4(0u, 0u, 0u, 0u);
+  for (uint32_t w = 0; w < 2u * W; ++w) B[w * 64u + lane] = 0u;
+
+  const uint32_t k0 = (uint32_t)p.seed, k1 = (uint32_t)(p.seed >> 32);
+  const uint32_t tlo = (uint32_t)p.trial_begin, thi = (uint32_t)(p.trial_begin >> 32);
+  const uint32_t c = j * 64u + lane;
+  const bool active = c < m;
+  const uint32_t node = active ? p.live_ids[c] : 0u;
+  const uint32_t ns = m - y * 64u < 64u ? m - y * 64u : 64u;                       // senders of word y
+  uint64_t word = 0ull;
+  for (uint32_t s = 0; s < ns; ++s) {
+    if (lane == 0) X[y] = rec(0ull, 1ull << s);
+    __builtin_amdgcn_wave_barrier();
+    uint32_t a0, a1;
+    random_tally(X, B, W, m, q, active, k0, k1, tlo, thi, node, round, phase, a0, a1);
+    word |= (uint64_t)(a1 & 1u) << s;
+    __builtin_amdgcn_wave_barrier();
+  }
+  if (active) out[(size_t)c * W + y] = word;
+}
+
 
 // ------------------------------------------------ event-level kernel (N <= 256)
 // message-granular simulation with the reference's literal
@@ -832,6 +869,22 @@ static hipError_t launch_random_floyd(const KParams &p, int grid, hipStream_t s)
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL(benor_random_kernel, dim3(grid), dim3(64 * kWavesPerBlock), p.lds_bytes, s, p);
+  return hipGetLastError();
+}
+
+// bo_plan_delivery_masks: the read-out kernel of the plan's sampler, chosen as launch_lockstep chooses the
+// trial kernel.
+hipError_t launch_delivery_masks(const KParams &p, uint32_t round, uint32_t phase, unsigned long long *out,
+                                 hipStream_t s) {
+  if (p.variant != kVarRandom) return hipErrorInvalidValue;
+  if (p.rd_a) return launch_random_bern_masks(p, round, phase, out, s);
+  if (p.lds_bytes > 64u * 1024u) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&benor_random_masks_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(benor_random_masks_kernel, dim3((p.W + kWavesPerBlock - 1u) / kWavesPerBlock, p.W),
+                     dim3(64 * kWavesPerBlock), p.lds_bytes, s, p, round, phase, out);
   return hipGetLastError();
 }
 

@@ -291,6 +291,18 @@ __device__ __forceinline__ void bern_tally(const uint4 *__restrict__ plane, uint
   c1 = a1;
 }
 
+// a's bits above tz(a), as the wave-uniform masks bern_tally passes to cmp_step (the trial kernel and the read-out)
+struct BernA {
+  uint32_t m1, m2, m3;
+};
+template <int NW>
+__device__ __forceinline__ BernA bern_a_masks(uint32_t a) {
+  const uint32_t tz = 4u - (uint32_t)NW;
+  return BernA{((a >> (tz + 1u)) & 1u) ? ~0u : 0u,   // used when NW = 4 (bit 1)
+               ((a >> (4u - 2u)) & 1u) ? ~0u : 0u,   // bit 2 (NW >= 3)
+               ((a >> 3u) & 1u) ? ~0u : 0u};         // bit 3 (NW >= 2)
+}
+
 template <int NW, int B>
 __global__ void __launch_bounds__(256) benor_random_bern_kernel(KParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -311,11 +323,8 @@ __global__ void __launch_bounds__(256) benor_random_bern_kernel(KParams p) {
   uint64_t expect = 0ull;                          // groups holding a live receiver for this lane
   for (uint32_t j = 0; j < W; ++j)
     if (j * 64u + lane < m) expect |= 1ull << j;
-  // a's bits above tz(a), as wave-uniform masks (cmp_step)
-  const uint32_t a = p.rd_a, tz = 4u - (uint32_t)NW;
-  const uint32_t am1 = ((a >> (tz + 1u)) & 1u) ? ~0u : 0u;   // used when NW = 4 (bit 1)
-  const uint32_t am2 = ((a >> (4u - 2u)) & 1u) ? ~0u : 0u;   // bit 2 (NW >= 3)
-  const uint32_t am3 = ((a >> 3u) & 1u) ? ~0u : 0u;          // bit 3 (NW >= 2)
+  const BernA am = bern_a_masks<NW>(p.rd_a);
+  const uint32_t am1 = am.m1, am2 = am.m2, am3 = am.m3;
 
   const uint32_t k0 = (uint32_t)p.seed, k1 = (uint32_t)(p.seed >> 32);
   const uint64_t waves_total = (uint64_t)gridDim.x * kWavesPerBlock;
@@ -421,26 +430,93 @@ __global__ void __launch_bounds__(256) benor_random_bern_kernel(KParams p) {
   flush_hist(lhist, p);
 }
 
+// Read-out of one phase's masks for tests and diagnosis (bo_plan_delivery_masks; on no hot path): wave j of
+// the launch runs bern_tally<NW, B> once for receiver group j of trial p.trial_begin, in the trial kernel's
+// own LDS layout and with the plan's parameters, over an all-zero plane, and copies what the function left in
+// each lane's bitset column -- rows [0, W32), the last row's padding cleared -- to out[c][W].
 template <int NW, int B>
-hipError_t launch_nw_b(const KParams &p, int grid, hipStream_t s) {
-  const void *fn = reinterpret_cast<const void *>(&benor_random_bern_kernel<NW, B>);
+__global__ void __launch_bounds__(256) benor_random_bern_masks_kernel(KParams p, uint32_t round, uint32_t phase,
+                                                                      unsigned long long *__restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wv = threadIdx.x >> 6;
+  const uint32_t m = p.m, W = p.W, q = p.q;
+  const uint32_t W32 = (m + 31u) >> 5, rows = p.rd_rows;
+  const uint32_t j = blockIdx.x * kWavesPerBlock + wv;                              // this wave's receiver group
+  if (j >= W) return;
+
+  uint4 *X = reinterpret_cast<uint4 *>(smem + p.hist_bytes + wv * p.wave_bytes);   // [W], no vote
+  uint32_t *bits = reinterpret_cast<uint32_t *>(X + 2u * W);                        // [rows][64] bitset
+  const uint32_t lb = (uint32_t)(uintptr_t)(lds_word *)bits + lane * 4u;
+  for (uint32_t w = lane; w < W; w += 64u) X[w] = make_uint4(0u, 0u, 0u, 0u);
+  __builtin_amdgcn_wave_barrier();
+
+  const BernA am = bern_a_masks<NW>(p.rd_a);
+  const uint32_t am1 = am.m1, am2 = am.m2, am3 = am.m3;
+
+  const uint32_t k0 = (uint32_t)p.seed, k1 = (uint32_t)(p.seed >> 32);
+  const uint32_t tlo = sgpr((uint32_t)p.trial_begin), thi = sgpr((uint32_t)(p.trial_begin >> 32));
+  const DlvUni u = dlv_uniforms(k0, k1, tlo, thi, round, phase);
+  const uint32_t c = j * 64u + lane;
+  const bool active = c < m;
+  const uint32_t node = active ? p.live_ids[c] : 0u;
+  uint32_t a0, a1;
+  bern_tally<NW, B>(X, lb, m, q, W32, rows, am1, am2, am3, active, true, u, node, a0, a1);
+  if (active) {
+    const uint32_t tail = m & 31u ? (1u << (m & 31u)) - 1u : ~0u;
+    for (uint32_t w = 0; w < W; ++w) {
+      uint32_t lo = *(const lds_word *)(uintptr_t)(lb + 2u * w * 256u), hi = 0u;
+      if (2u * w + 1u < W32) hi = *(const lds_word *)(uintptr_t)(lb + (2u * w + 1u) * 256u);
+      if (2u * w + 1u == W32) lo &= tail;
+      if (2u * w + 2u == W32) hi &= tail;
+      out[(size_t)c * W + w] = (unsigned long long)hi << 32 | lo;
+    }
+  }
+}
+
+// What a launch of an instantiation runs: the trial kernel, or (masks != nullptr) the read-out of one phase.
+struct MaskArgs {
+  uint32_t round, phase;
+  unsigned long long *out;
+};
+
+template <int NW, int B>
+hipError_t launch_nw_b(const KParams &p, int grid, hipStream_t s, const MaskArgs *masks) {
+  const void *fn = masks ? reinterpret_cast<const void *>(&benor_random_bern_masks_kernel<NW, B>)
+                         : reinterpret_cast<const void *>(&benor_random_bern_kernel<NW, B>);
   if (p.lds_bytes > 64u * 1024u) {
     const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((benor_random_bern_kernel<NW, B>), dim3(grid), dim3(64 * kWavesPerBlock), p.lds_bytes, s, p);
+  if (masks)
+    hipLaunchKernelGGL((benor_random_bern_masks_kernel<NW, B>), dim3(grid), dim3(64 * kWavesPerBlock), p.lds_bytes, s,
+                       p, masks->round, masks->phase, masks->out);
+  else
+    hipLaunchKernelGGL((benor_random_bern_kernel<NW, B>), dim3(grid), dim3(64 * kWavesPerBlock), p.lds_bytes, s, p);
   return hipGetLastError();
 }
 
 template <int NW>
-hipError_t launch_nw(const KParams &p, int grid, hipStream_t s) {
+hipError_t launch_nw(const KParams &p, int grid, hipStream_t s, const MaskArgs *masks) {
   switch (p.rd_b) {   // m in [128, 4096]: b = ceil(log2 m) in 7..12 (b = 7 only at m = 128, q = 64)
-    case 7: return launch_nw_b<NW, 7>(p, grid, s);
-    case 8: return launch_nw_b<NW, 8>(p, grid, s);
-    case 9: return launch_nw_b<NW, 9>(p, grid, s);
-    case 10: return launch_nw_b<NW, 10>(p, grid, s);
-    case 11: return launch_nw_b<NW, 11>(p, grid, s);
-    default: return launch_nw_b<NW, 12>(p, grid, s);
+    case 7: return launch_nw_b<NW, 7>(p, grid, s, masks);
+    case 8: return launch_nw_b<NW, 8>(p, grid, s, masks);
+    case 9: return launch_nw_b<NW, 9>(p, grid, s, masks);
+    case 10: return launch_nw_b<NW, 10>(p, grid, s, masks);
+    case 11: return launch_nw_b<NW, 11>(p, grid, s, masks);
+    default: return launch_nw_b<NW, 12>(p, grid, s, masks);
+  }
+}
+
+hipError_t launch_bern(const KParams &p, int grid, hipStream_t s, const MaskArgs *masks) {
+  if (p.rd_a == 0u || p.rd_b < 7u || p.rd_b > 12u || p.rd_rows < random_bern_rows(p.m, p.rd_b))
+    return hipErrorInvalidValue;
+  const uint32_t tz = (uint32_t)__builtin_ctz(p.rd_a);
+  switch (4u - tz) {
+    case 4: return launch_nw<4>(p, grid, s, masks);
+    case 3: return launch_nw<3>(p, grid, s, masks);
+    case 2: return launch_nw<2>(p, grid, s, masks);
+    default: return launch_nw<1>(p, grid, s, masks);
   }
 }
 
@@ -451,16 +527,12 @@ uint32_t random_bern_rows(uint32_t m, uint32_t b) {
   return r > W32 ? r : W32;
 }
 
-hipError_t launch_random_bern(const KParams &p, int grid, hipStream_t s) {
-  if (p.rd_a == 0u || p.rd_b < 7u || p.rd_b > 12u || p.rd_rows < random_bern_rows(p.m, p.rd_b))
-    return hipErrorInvalidValue;
-  const uint32_t tz = (uint32_t)__builtin_ctz(p.rd_a);
-  switch (4u - tz) {
-    case 4: return launch_nw<4>(p, grid, s);
-    case 3: return launch_nw<3>(p, grid, s);
-    case 2: return launch_nw<2>(p, grid, s);
-    default: return launch_nw<1>(p, grid, s);
-  }
+hipError_t launch_random_bern(const KParams &p, int grid, hipStream_t s) { return launch_bern(p, grid, s, nullptr); }
+
+hipError_t launch_random_bern_masks(const KParams &p, uint32_t round, uint32_t phase, unsigned long long *out,
+                                    hipStream_t s) {
+  const MaskArgs masks{round, phase, out};
+  return launch_bern(p, (int)((p.W + kWavesPerBlock - 1u) / kWavesPerBlock), s, &masks);
 }
 
 }  // namespace benor

@@ -1323,6 +1323,35 @@ int bo_plan_kernel(const bo_plan *pl) {
   return kernel_family(pl->kp);
 }
 
+// Tests and diagnosis: what the plan's random-delivery kernel draws for one (trial, round, phase), read out by a
+// kernel that calls the trial kernel's own device function with the plan's own parameters (benor_internal.h
+// launch_delivery_masks).  Synchronous, on the null stream; no histogram, no flag.
+int bo_plan_delivery_masks(bo_plan *pl, uint64_t trial, uint32_t round, uint32_t phase, uint64_t *masks_out) {
+  if (!pl || !masks_out) return fail(BO_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (pl->kp.m == 0u || pl->kp.variant != benor::kVarRandom)
+    return fail(BO_ERR_INVALID_ARGUMENT, "bo_plan_delivery_masks: the plan's kernel is not BO_KERNEL_RANDOM");
+  if (phase > 1u || round == 0u || round > 0x7FFFu)
+    return fail(BO_ERR_INVALID_ARGUMENT, "bo_plan_delivery_masks: phase is 0 or 1 and round 1 .. 0x7FFF");
+  benor::KParams kp = pl->kp;
+  kp.trial_begin = trial;
+  kp.trial_count = 1;
+  const size_t words = (size_t)kp.m * kp.W;
+  int cur = 0;
+  HIP_TRY(hipGetDevice(&cur));
+  if (cur != pl->device) HIP_TRY(hipSetDevice(pl->device));
+  hipError_t e;
+  {
+    DeviceBuf<unsigned long long> d;
+    e = d.alloc(words);
+    if (e == hipSuccess) e = hipMemset(d.d, 0, sizeof(unsigned long long) * words);
+    if (e == hipSuccess) e = benor::launch_delivery_masks(kp, round, phase, d.d, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(masks_out, d.d, sizeof(unsigned long long) * words, hipMemcpyDeviceToHost);
+  }
+  if (cur != pl->device) (void)hipSetDevice(cur);
+  if (e != hipSuccess) return hip_fail(e, "bo_plan_delivery_masks");
+  return BO_OK;
+}
+
 // Lockstep: the R-phase needs c1 only (c0 = M - c1, M binary votes,
 // node.ts:52,56-62).  The P-phase needs c0 and c1 (node.ts:92-98) unless M
 // is odd: then no R-phase count can tie, no proposal is "?" (node.ts:63-69),

@@ -614,6 +614,18 @@ int bo_plan_kernel(const bo_plan *plan);
  * bo_plan_create's validation error for an invalid cfg. */
 int bo_kernel_for(const bo_trials_cfg *cfg, int *kernel_out);
 
+/* Tests and diagnosis (no reference counterpart: SURVEY §8f #4's "first N-F arrivals", drawn as
+ * oracle/benor_oracle.c oracle_delivery_mask defines them): the delivered-sender masks that the plan's
+ * random-delivery kernel draws in one phase of one trial, masks_out[m][W], m = bo_plan_live_nodes and
+ * W = ceil(m / 64).  Row c is the mask of the receiver with compact live index c over compact sender
+ * indices -- oracle_delivery_mask(seed, trial, live_ids[c], round, phase, m, N - F, D)'s D, bits >= m
+ * clear.  The read-out kernel calls the trial kernel's own sampling function (Floyd or Bernoulli +
+ * fix-up, the instantiation the plan dispatches to) with the plan's own parameters and LDS layout.
+ * Only for a plan whose bo_plan_kernel is BO_KERNEL_RANDOM, phase 0 (R) or 1 (P) and round 1 .. 0x7FFF
+ * (the counter's round field); anything else is BO_ERR_INVALID_ARGUMENT.  Synchronous; on no hot path.
+ * An added entry: the ABI version and every struct are unchanged. */
+int bo_plan_delivery_masks(bo_plan *plan, uint64_t trial, uint32_t round, uint32_t phase, uint64_t *masks_out);
+
 void bo_plan_destroy(bo_plan *plan);
 
 /* One-shot convenience: create plan, run trial ids [trial_begin, +trial_count), destroy. */

@@ -61,8 +61,10 @@ def test_lockstep_fuzz(case):
     np.testing.assert_array_equal(got, ref, err_msg=f"N={N} F={F} k_max={k_max} init={'fixed' if init else 'random'}")
 
 
-@pytest.mark.parametrize("case", range(40))
+@pytest.mark.parametrize("case", range(56))
 def test_random_delivery_fuzz(case):
+    """Cases 40 and up also compare the per-node states of their first trial, and every other one of them starts
+    at a trial id above 2^32 (drawn after everything else, so that cases 0..39 are what they were)."""
     rng = np.random.default_rng(5000 + case)
     N, F = _shape(rng, 4, 700 if case % 3 else 2200)
     f = int(rng.integers(0, F + 1))
@@ -72,10 +74,16 @@ def test_random_delivery_fuzz(case):
     seed = int(rng.integers(0, 2**63))
     m = N - f
     T = 400 if m <= 64 else (40 if m <= 512 else 6)
-    got = benor.TrialsPlan(N, F, fl, seed=seed, k_max=k_max, initial_values=init, mode=RD).run(77, T)
-    ref = oracle.run_trials(N, F, fl, seed=seed, trial_begin=77, trial_count=T, k_max=k_max, initial_values=init,
+    begin = int(rng.integers(2**32, 2**48)) if case >= 40 and case % 2 else 77
+    got = benor.TrialsPlan(N, F, fl, seed=seed, k_max=k_max, initial_values=init, mode=RD).run(begin, T)
+    ref = oracle.run_trials(N, F, fl, seed=seed, trial_begin=begin, trial_count=T, k_max=k_max, initial_values=init,
                             mode=oracle.MODE_RANDOM_DELIVERY).hist
     np.testing.assert_array_equal(got, ref, err_msg=f"N={N} F={F} f={f}")
+    if case >= 40:
+        _, st = benor.run_trial_states(N, F, fl, seed=seed, trial=begin, k_max=k_max, initial_values=init, mode=RD)
+        want = oracle.run_trials(N, F, fl, seed=seed, trial_begin=begin, trial_count=1, k_max=k_max,
+                                 initial_values=init, mode=oracle.MODE_RANDOM_DELIVERY, want_states=True)
+        assert st == want.states, f"N={N} F={F} f={f} trial={begin}"
 
 
 @pytest.mark.parametrize("case", range(24))
